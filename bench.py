@@ -10,6 +10,10 @@ steps of num_envs (1024) envs per GPU (policy inference + physics + obs/reward) 
 with the SHIPPED hyper-parameters (minibatch_size 4, 5 mini-epochs, central value; cfg/lego/ppo_continuous_grasp.yaml).
 value = total env-steps of all ranks / max-over-ranks wall time of exactly K steps = rl_games' "fps total" (PS:136-140).
 Rank 0 prints ONE JSON line; see DESIGN.md §7 for every field.
+
+A plain run sets up, warms up, times the K steps and reports them.  --full adds what takes runs of its own: the rooflines of
+k_physics and of the update kernel, the labelled large-minibatch variants and the CPU baseline.  --dump-outputs DIR writes what
+the last timed step computed as DIR/<name>.npy (dump_outputs below).
 """
 import argparse
 import json
@@ -66,7 +70,46 @@ def parse():
     ap.add_argument("--cpu-baseline-envs", type=int, default=1024)
     ap.add_argument("--cpu-baseline-steps", type=int, default=16)
     ap.add_argument("--cpu-baseline-ppo-envs", type=int, default=128, help="PPO leg: envs of the sample dataset (x horizon rows; 128 -> 1280 optimiser steps, a few seconds)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also the measurements beside the headline: rooflines (runs of their own), "
+                    "large-minibatch variants, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BUDGET = 60_000_000     # bytes of --dump-outputs in all (64 MB at most, .npy headers included)
+
+
+def dump_outputs(path, agent, last):
+    """--dump-outputs: what a caller of train_epoch holds after the last timed step, as float32 / float64 arrays - the parameters of
+    the three networks and the central value's input statistics after the update, the epoch's experience buffer (env-major [N, H, ...],
+    mu / sigma as the update rewrote them) with its returns and normalised advantages, the observation the next epoch starts from, and
+    the loss statistics train_epoch returned.  Per-env arrays hold every env while they fit the budget, else a fixed seeded sample."""
+    import numpy as np
+    import torch
+    t, n, h = agent.ppo.t, agent.num_actors, agent.horizon_length
+    whole = {"ac_params": t["AC_PARAMS"], "cv_params": t["CV_PARAMS"], "cv_rms_mean": t["CV_RMS_MEAN"], "cv_rms_var": t["CV_RMS_VAR"]}
+    per_env = {"rollout_obs": t["MB_OBS"], "rollout_states": t["MB_STATES"], "rollout_actions": t["MB_ACTIONS"], "rollout_mus": t["MB_MUS"],
+               "rollout_sigmas": t["MB_SIGMAS"], "rollout_neglogp": t["MB_NEGLOGP"], "rollout_values": t["MB_VALUES"],
+               "rollout_rewards": t["MB_REWARDS"], "rollout_dones": t["MB_DONES"], "returns": t["RETURNS"].view(n, h),
+               "advantages": t["ADVANTAGES"].view(n, h), "next_obs": agent.obs["obs"], "next_states": agent.obs["states"]}
+    size = lambda x: x.numel() * (8 if x.dtype == torch.float64 else 4)
+    fixed = sum(size(x) for x in whole.values()) + 6 * 8
+    k = min(n, (DUMP_BUDGET - fixed) // sum(size(x) // n for x in per_env.values()))
+    rows = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+    rows = torch.as_tensor(rows, device=t["AC_PARAMS"].device)
+    arrays = {name: x.detach() for name, x in whole.items()}
+    arrays.update((name, x.detach()[rows]) for name, x in per_env.items())
+    out = {name: x.cpu().numpy() for name, x in arrays.items()}
+    out = {name: a if a.dtype == np.float64 else a.astype(np.float32) for name, a in out.items()}
+    # train_epoch's (a_losses, c_losses, b_losses, entropies, kls) of the epoch and its last_lr
+    out["losses"] = np.array([float(v[0]) for v in last[4:9]] + [float(last[9])], np.float64)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BUDGET
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(args, scene_desc, root0, dof0, targets0, horizon, minibatch, mini_epochs):
@@ -251,6 +294,8 @@ def main():
         train["params"]["config"]["central_value_config"]["minibatch_size"] = args.minibatch
     train["params"]["config"]["mixed_precision"] = bool(args.mixed_precision)
     seed = 22 + rank
+    # torch's default device generator is seeded differently in every process, and the first env reset draws from it
+    torch.manual_seed(seed)
     task = BlockAssemblyGraspSim(cfg, device_type="cuda", device_id=local_rank, headless=True, seed=seed, piles_per_type=args.piles_per_type)
     env = RLgamesVecTaskPython(task, "cuda:%d" % local_rank)
     pc = train["params"]["config"]
@@ -286,6 +331,33 @@ def main():
     if rank != 0:
         if dist is not None:
             dist.destroy_process_group()
+        return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, agent, r)
+    out = {
+        "metric": "env-steps/sec BlockAssemblyGraspSim num_envs=%d/GPU" % n, "value": value, "unit": "env-steps/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "bf16 trunk GEMMs / f32" if (args.mixed_precision and agent.minibatch_size > 8) else "f32", "data": "synthetic",
+        "config": {"workload": "BlockAssemblyGraspSim num_envs=%d per GPU, fp32, PPO MLP policy [1024,512,256], horizon 8, "
+                               "minibatch_size %d, mini_epochs 5, central value (configs[1])" % (n, agent.minibatch_size),
+                   "step": "one rl_games epoch = 8 env steps x num_envs + full PPO update", "global_envs": n * world,
+                   "piles": "synthetic settled piles, %d per brick-type group" % args.piles_per_type,
+                   "policy": "random init, seed 22+rank" + (", then %d untimed training epochs" % args.pretrain_epochs if args.pretrain_epochs else "")},
+        "fps_step": n * horizon * args.steps / step_t, "fps_step_and_inference": n * horizon * args.steps / play_t,
+        "fps_total_rank0": n * horizon * args.steps / (play_t + upd_t),
+        "update_ms_per_epoch": upd_t / args.steps * 1e3, "rollout_ms_per_epoch": play_t / args.steps * 1e3,
+        "update_path": ("multi-rank: hipGraph of [forward/backward -> RCCL all-gather of the rank-MB factors -> rebuild + clip + Adam]" if agent.multi_gpu
+                        else agent.ppo.update_impl()),
+    }
+
+    def finish():
+        os.write(json_fd, (json.dumps(out) + "\n").encode())
+        if dist is not None:
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish()
         return
     # ---- roofline of the dominant rollout kernel (k_physics): HIP events on the stream the kernel is launched on
     sim = task.sim
@@ -369,28 +441,14 @@ def main():
                                       "frac_of_floor": (floor / (upd_ms_step * 1e3)) if floor else None, "floor_quoted_from": fl_.get("source"),
                                       "floor_note": fl_.get("note")}
     dominant = roof_upd if upd_t > step_t else roof_phys
-    out = {
-        "metric": "env-steps/sec BlockAssemblyGraspSim num_envs=%d/GPU" % n, "value": value, "unit": "env-steps/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "bf16 trunk GEMMs / f32" if (args.mixed_precision and agent.minibatch_size > 8) else "f32", "data": "synthetic",
-        "config": {"workload": "BlockAssemblyGraspSim num_envs=%d per GPU, fp32, PPO MLP policy [1024,512,256], horizon 8, "
-                               "minibatch_size %d, mini_epochs 5, central value (configs[1])" % (n, agent.minibatch_size),
-                   "step": "one rl_games epoch = 8 env steps x num_envs + full PPO update", "global_envs": n * world,
-                   "piles": "synthetic settled piles, %d per brick-type group" % args.piles_per_type,
-                   "policy": "random init, seed 22+rank" + (", then %d untimed training epochs" % args.pretrain_epochs if args.pretrain_epochs else "")},
-        "fps_step": n * horizon * args.steps / step_t, "fps_step_and_inference": n * horizon * args.steps / play_t,
-        "fps_total_rank0": n * horizon * args.steps / (play_t + upd_t),
-        "update_ms_per_epoch": upd_t / args.steps * 1e3, "rollout_ms_per_epoch": play_t / args.steps * 1e3,
-        "update_path": ("multi-rank: hipGraph of [forward/backward -> RCCL all-gather of the rank-MB factors -> rebuild + clip + Adam]" if agent.multi_gpu
-                        else agent.ppo.update_impl()),
+    out.update({
         "roofline": {"bound": dominant["bound"], "achieved": dominant["achieved"], "peak": dominant["peak"],
                      "unit": dominant["unit"], "frac": dominant["frac"], "traffic": dominant["traffic"], "kernel": dominant["kernel"],
                      "bound_actual": dominant.get("bound_actual"),
                      "traffic_is": "quoted from the committed rocprofv3 PMC passes (see traffic_counters.quoted_from), not measured in this run"
                                    if dominant["traffic"] is not None else "not available for this configuration"},
         "roofline_physics": roof_phys, "roofline_update": roof_upd,
-    }
+    })
     if world == 1 and not force_multi and args.minibatch is None and not args.no_large_minibatch:
         try:    # BASELINE.md's labelled variant: the same epoch with ONE minibatch of n x horizon samples per mini-epoch
             out["large_minibatch_variant"] = large_minibatch_variant(train, env, n, horizon, args)
@@ -408,9 +466,7 @@ def main():
             out["cpu_baseline"] = cpu_baseline(args, sim._desc, root, dof, tg, horizon, agent.minibatch_size, agent.mini_epochs_num)
         except Exception as ex:   # the checker is optional for the measurement itself
             out["cpu_baseline"] = {"value": None, "error": str(ex)}
-    os.write(json_fd, (json.dumps(out) + "\n").encode())
-    if dist is not None:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":
