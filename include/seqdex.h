@@ -139,7 +139,16 @@ typedef enum {
                             *                    13 bits | box pair 9 | direction 1 | sample 5, age in the 4 bits above), ascending; rows are valid up to
                             *                    SDX_T_WARM_COUNT; [1] when scene.warm_start == 0 (the cold solver keeps no cache) */
   SDX_T_WARM_LAMBDA = 50,  /* f32 [N,3,1536]   the accumulated impulses (normal, two tangents) of those contacts */
-  SDX_T_COUNT = 51
+  /* domain randomization (sdx_set_randomization below): the per-env physics parameters k_physics reads while randomization is on.  They
+   * always exist and hold the scene's values (factors 1) until a randomization writes them; the caller may also write them directly */
+  SDX_T_DR_DOF = 51,       /* f32 [N,4,23]      kp, kd, lower, upper of every DOF - the limits the PHYSICS enforces (the task's action scaling keeps the
+                            *                    scene's, as the reference reads them from the asset before randomizing, GS:561-590)              */
+  SDX_T_DR_LINK = 52,      /* f32 [N,2,24]      hand link mass factor (inertia scales with it), hand link friction coefficient                     */
+  SDX_T_DR_BRICK = 53,     /* f32 [N,2,72]      free brick mass factor (inertia scales with it; composes with seg_mass_scale), brick friction      */
+  SDX_T_DR_GRAVITY = 54,   /* f32 [3]           gravity of every env                                                                             */
+  SDX_T_DR_FRAME = 55,     /* i64 [2]           [0] frame = physics launches made while randomization was on (gym.get_frame_count), [1] the frame
+                            *                    of the last gravity ("non-env") randomization (BT:237,248)                                      */
+  SDX_T_COUNT = 56
 } sdx_tensor_id;
 
 /* Compact scene constants (row A0/A1 of SURVEY.md §8(a)); produced by tools/compile_scene.py from the
@@ -258,6 +267,43 @@ typedef struct {
   float search_finger_pose[16];        /* finger joints (radians) of the default AND the prepare pose, SE:205-206,220-222 */
 } sdx_scene_desc;
 
+/* ---- domain randomization (BaseTask.apply_randomizations, BT:229-420; called by every BlockAssembly task at create and in each
+ * reset_idx, GS:106-107,515-516,1395-1396).  The definition restates Isaac Gym's gymutil sampling rules:
+ *   schedule factor s: linear = min(frame, schedule_steps) / schedule_steps, constant = (frame < schedule_steps ? 0 : 1), none = 1
+ *   range transform:   additive: both ends x s; scaling: end x s + (1 - s).  gaussian range = [mu, sigma]: mu as an end, sigma x s
+ *   distribution:      gaussian mu + sigma z (z from Box-Muller), uniform lo + (hi - lo) u, loguniform exp(log lo + (log hi - log lo) u)
+ *   buckets:           num_buckets > 0 snaps the sample down to the grid lo + (hi - lo) k / num_buckets, k in [0, num_buckets), with
+ *                      [lo, hi] = the UNtransformed range (gaussian: mu -+ 2 sqrt(sigma)); below the grid: k = 0
+ *   operation:         value = default + sample (additive) or default x sample (scaling); default = the sdx_scene_desc value
+ *   s == 0:            the attribute is not sampled, value = default (deviation: gymutil snaps the identity sample to a bucket)
+ * When: sdx_set_randomization samples every env and gravity at the current frame.  Afterwards, at the start of sdx_step /
+ * sdx_pre_physics (before any reset physics, Orient's and Search's settling launches included), an env with reset_buf != 0 and
+ * randomize_buf >= frequency is re-sampled and its randomize_buf set to 0; gravity is re-sampled when some env resets and
+ * frame - last_rand_frame >= frequency.  sdx_reset_idx applies the same rule with its env mask in place of reset_buf, before it
+ * resets the envs.  All on the device, no host synchronisation.
+ * Randomness: u = hash(seed, env x 287 + slot, draw) (the counter RNG of DESIGN.md section 6; draw = how many times this env was sampled):
+ * a sample depends on seed, env, slot and draw only, not on N or launch order. */
+typedef enum { SDX_DR_NONE = 0, SDX_DR_GAUSSIAN = 1, SDX_DR_UNIFORM = 2, SDX_DR_LOGUNIFORM = 3 } sdx_dr_distribution;
+typedef enum { SDX_DR_ADDITIVE = 1, SDX_DR_SCALING = 2 } sdx_dr_operation;
+typedef enum { SDX_DR_SCHED_NONE = 0, SDX_DR_SCHED_LINEAR = 1, SDX_DR_SCHED_CONSTANT = 2 } sdx_dr_schedule;
+typedef struct {
+  int32_t distribution;      /* sdx_dr_distribution; SDX_DR_NONE = this quantity is not randomized (keeps its current row value) */
+  int32_t operation;         /* sdx_dr_operation */
+  int32_t schedule;          /* sdx_dr_schedule */
+  int32_t schedule_steps;
+  int32_t num_buckets;       /* 0 = continuous */
+  float range[2];            /* [lo, hi] or [mu, sigma] */
+} sdx_dr_attr;
+typedef struct {
+  int32_t frequency;         /* randomization_params.frequency (BT:231: default 1) */
+  sdx_dr_attr gravity;       /* sim_params.gravity: one sample per component                                  */
+  sdx_dr_attr dof_stiffness, dof_damping, dof_lower, dof_upper;   /* actor_params.hand.dof_properties, per env and DOF */
+  sdx_dr_attr link_mass;     /* actor_params.hand.rigid_body_properties.mass, per env and link                */
+  sdx_dr_attr link_friction; /* actor_params.hand.rigid_shape_properties.friction, per env and link           */
+  sdx_dr_attr brick_mass;    /* actor_params.lego.rigid_body_properties.mass: every free brick                 */
+  sdx_dr_attr brick_friction;/* actor_params.lego.rigid_shape_properties.friction: every free brick            */
+} sdx_dr_desc;
+
 typedef struct sdx_sim* sdx_handle;
 
 /* Scene build: replaces create_sim/add_ground/load_asset/create_env/create_actor/prepare_sim
@@ -318,6 +364,14 @@ int sdx_refresh_kinematics(sdx_handle h, void* stream);
  * it in place, as the reference does with root_state_tensor / dof_state) or a tensor of the caller's (as the reference's cur_targets).
  * actor_ids_dev: device i32 [n]; actor index = env * SDX_ACTORS + slot.  Out-of-range ids are ignored. */
 int sdx_set_indexed(sdx_handle h, int32_t id, const float* src_dev, const int32_t* actor_ids_dev, int32_t n, void* stream);
+
+/* Domain randomization on (desc != NULL) or off (NULL).  On: k_physics reads the per-env rows SDX_T_DR_* instead of the scene constants
+ * (contact friction = the mean of the two bodies' coefficients, PhysX's default combine mode; static bodies keep sdx_scene_desc.friction)
+ * and the first randomization is enqueued on `stream`.  A desc whose attributes are all SDX_DR_NONE turns the per-env path on without
+ * sampling (the rows keep what they hold: a caller-supplied sampler writes them).  Off: the rows are reset to the scene's values and the
+ * physics returns to the scene constants.  Stream-ordered; frequency >= 1, enums, finite ranges, lo <= hi (uniform, loguniform: lo > 0),
+ * sigma >= 0 (gaussian) are checked (SDX_ERR_INVALID). */
+int sdx_set_randomization(sdx_handle h, const sdx_dr_desc* desc, void* stream);
 
 int sdx_num_envs(sdx_handle h);
 const char* sdx_last_error(sdx_handle h);   /* never NULL; h may be NULL for create-time errors */

@@ -30,6 +30,7 @@ struct sdx_sim {
   std::vector<void*> allocs;
   struct TensorInfo { void* ptr; int64_t shape[4]; int ndim; int dtype; } tinfo[SDX_T_COUNT];
   bool has_piles = false;
+  sdx_dr_desc dr{};           // the randomization in force (meaningful while buf.dr_on != nullptr)
   std::string err;
 };
 
@@ -74,6 +75,133 @@ static void qrot_host(const float q[4], const float v[3], float out[3]) {
   out[0] = v[0] + q[3] * t[0] + (u[1] * t[2] - u[2] * t[1]);
   out[1] = v[1] + q[3] * t[1] + (u[2] * t[0] - u[0] * t[2]);
   out[2] = v[2] + q[3] * t[2] + (u[0] * t[1] - u[1] * t[0]);
+}
+
+// ---------------------------------------------------------------- domain randomization (include/seqdex.h sdx_set_randomization,
+// DESIGN.md section 18).  Samples are pure functions of (seed, env, slot, draw): sdx_hash(seed ^ SDX_DR_TAG, env * SDX_DR_SLOTS + slot, draw).
+#define SDX_DR_TAG 0xD0A1ull
+#define SDX_DR_SLOT_LINK (4 * SDX_NDOF)                        // 92: 24 link masses, then 24 link frictions
+#define SDX_DR_SLOT_BRICK (SDX_DR_SLOT_LINK + 2 * SDX_NLINK)   // 140: 72 brick masses, then 72 brick frictions
+#define SDX_DR_SLOT_GRAV (SDX_DR_SLOT_BRICK + 2 * SDX_NFREE)   // 284..286: gravity (env 0's row)
+__device__ __forceinline__ float dr_u(uint64_t hs, int which) {   // uniform in (0, 1): 24 bits of the hash, +0.5
+  const uint32_t b = which ? (uint32_t)(hs >> 16) & 0xffffffu : (uint32_t)(hs >> 40);
+  return ((float)b + 0.5f) * (1.0f / 16777216.0f);
+}
+__device__ __forceinline__ float dr_sched(const sdx_dr_attr& a, long long frame) {
+  if (a.schedule == SDX_DR_SCHED_LINEAR) return (float)(frame < a.schedule_steps ? frame : (long long)a.schedule_steps) / (float)a.schedule_steps;
+  if (a.schedule == SDX_DR_SCHED_CONSTANT) return frame < a.schedule_steps ? 0.0f : 1.0f;
+  return 1.0f;
+}
+__device__ __forceinline__ float dr_bucket(float lo, float hi, int k, int nb) { return lo + (hi - lo) * (float)k / (float)nb; }
+// the randomized value of a quantity whose scene value is v0 (s > 0; s == 0 leaves v0)
+__device__ float dr_value(const sdx_dr_attr& a, float s, uint64_t hs, float v0) {
+#pragma clang fp contract(off)
+  const bool scaling = a.operation == SDX_DR_SCALING;
+  const float lo = a.range[0], hi = a.range[1];
+  float x;
+  if (a.distribution == SDX_DR_GAUSSIAN) {
+    const float mu = scaling ? lo * s + (1.0f - s) : lo * s, sig = hi * s;
+    const float z = sqrtf(-2.0f * logf(dr_u(hs, 0))) * cosf(6.28318530718f * dr_u(hs, 1));
+    x = mu + sig * z;
+  } else {
+    const float a0 = scaling ? lo * s + (1.0f - s) : lo * s, a1 = scaling ? hi * s + (1.0f - s) : hi * s;
+    const float u = dr_u(hs, 0);
+    if (a.distribution == SDX_DR_UNIFORM) x = a0 + (a1 - a0) * u;
+    else x = a0 == a1 ? a0 : expf(logf(a0) + (logf(a1) - logf(a0)) * u);
+  }
+  if (a.num_buckets > 0) {   // snap down to lo + (hi - lo) k / nb of the untransformed range (gaussian: mu -+ 2 sqrt(sigma))
+    const float blo = a.distribution == SDX_DR_GAUSSIAN ? lo - 2.0f * sqrtf(hi) : lo;
+    const float bhi = a.distribution == SDX_DR_GAUSSIAN ? lo + 2.0f * sqrtf(hi) : hi;
+    const int nb = a.num_buckets;
+    int k = (int)floorf((x - blo) / (bhi - blo) * (float)nb);
+    k = k < 0 ? 0 : (k > nb - 1 ? nb - 1 : k);
+    while (k > 0 && dr_bucket(blo, bhi, k, nb) > x) --k;
+    while (k + 1 < nb && dr_bucket(blo, bhi, k + 1, nb) <= x) ++k;
+    x = dr_bucket(blo, bhi, k, nb);
+  }
+  return scaling ? v0 * x : v0 + x;
+}
+// rows <- the scene's values (factors 1)
+__global__ void k_dr_defaults(const SdxConst* __restrict__ C, SdxBuf B) {
+  const int e = blockIdx.x, t = threadIdx.x;
+  const sdx_scene_desc& sc = C->sc;
+  for (int i = t; i < 4 * SDX_NDOF; i += blockDim.x) {
+    const int r = i / SDX_NDOF, j = i % SDX_NDOF;
+    B.dr_dof[(size_t)e * 4 * SDX_NDOF + i] = r == 0 ? sc.kp[j] : r == 1 ? sc.kd[j] : r == 2 ? sc.lower[j] : sc.upper[j];
+  }
+  for (int i = t; i < 2 * SDX_NLINK; i += blockDim.x) B.dr_link[(size_t)e * 2 * SDX_NLINK + i] = i < SDX_NLINK ? 1.0f : sc.friction;
+  for (int i = t; i < 2 * SDX_NFREE; i += blockDim.x) B.dr_brick[(size_t)e * 2 * SDX_NFREE + i] = i < SDX_NFREE ? 1.0f : sc.friction;
+  if (e == 0 && t < 3) B.dr_grav[t] = sc.gravity[t];
+}
+// gravity ("non-env", BT:241,248): on the first randomization, else when some env resets and frame - last_rand_frame >= frequency
+// mask: the envs being reset (sdx_reset_idx's env mask), nullptr = reset_buf (sdx_step / sdx_pre_physics)
+__global__ __launch_bounds__(256) void k_dr_gravity(const SdxConst* __restrict__ C, SdxBuf B, sdx_dr_desc d, int first, const uint8_t* mask) {
+  __shared__ int any;
+  const int t = threadIdx.x;
+  if (t == 0) any = first;
+  __syncthreads();
+  for (int e = t; e < B.N && !first; e += 256) if (mask ? mask[e] != 0 : B.reset[e] != 0) any = 1;
+  __syncthreads();
+  const long long frame = B.dr_frame[0];
+  if (!any || (!first && frame - B.dr_frame[1] < d.frequency)) return;
+  const uint64_t draw = (uint64_t)B.dr_draw[B.N];
+  __syncthreads();
+  if (t < 3 && d.gravity.distribution != SDX_DR_NONE) {
+    const float s = dr_sched(d.gravity, frame);
+    const uint64_t hs = sdx_hash(B.seed ^ SDX_DR_TAG, (uint64_t)(SDX_DR_SLOT_GRAV + t), draw);
+    B.dr_grav[t] = s > 0.0f ? dr_value(d.gravity, s, hs, C->sc.gravity[t]) : C->sc.gravity[t];
+  }
+  if (t == 0) { B.dr_frame[1] = frame; B.dr_draw[B.N] = (int32_t)(draw + 1); }
+}
+// per env (BT:238-245): every env on the first randomization, else the envs that reset now with randomize_buf >= frequency (-> 0)
+__global__ __launch_bounds__(128) void k_dr_sample(const SdxConst* __restrict__ C, SdxBuf B, sdx_dr_desc d, int first, const uint8_t* mask) {
+  const int e = blockIdx.x, t = threadIdx.x;
+  if (!first && !((mask ? mask[e] != 0 : B.reset[e] != 0) && B.randomize[e] >= d.frequency)) return;
+  const sdx_scene_desc& sc = C->sc;
+  const long long frame = B.dr_frame[0];
+  const uint64_t draw = (uint64_t)B.dr_draw[e];
+  __syncthreads();
+  for (int k = t; k < SDX_DR_SLOT_GRAV; k += blockDim.x) {
+    const sdx_dr_attr* a;
+    float v0;
+    float* out;
+    bool factor = false;
+    if (k < SDX_DR_SLOT_LINK) {
+      const int r = k / SDX_NDOF, j = k % SDX_NDOF;
+      a = r == 0 ? &d.dof_stiffness : r == 1 ? &d.dof_damping : r == 2 ? &d.dof_lower : &d.dof_upper;
+      v0 = r == 0 ? sc.kp[j] : r == 1 ? sc.kd[j] : r == 2 ? sc.lower[j] : sc.upper[j];
+      out = &B.dr_dof[(size_t)e * 4 * SDX_NDOF + k];
+    } else if (k < SDX_DR_SLOT_BRICK) {
+      const int i = k - SDX_DR_SLOT_LINK, l = i % SDX_NLINK;
+      factor = i < SDX_NLINK;
+      a = factor ? &d.link_mass : &d.link_friction;
+      v0 = factor ? sc.link_mass[l] : sc.friction;
+      out = &B.dr_link[(size_t)e * 2 * SDX_NLINK + i];
+    } else {
+      const int i = k - SDX_DR_SLOT_BRICK, b = i % SDX_NFREE;
+      factor = i < SDX_NFREE;
+      a = factor ? &d.brick_mass : &d.brick_friction;
+      v0 = factor ? sc.brick_mass[sc.brick_type[b]] : sc.friction;
+      out = &B.dr_brick[(size_t)e * 2 * SDX_NFREE + i];
+    }
+    if (a->distribution == SDX_DR_NONE) continue;   // not randomized: the row keeps what it holds
+    // masses are stored as factors of the scene's mass (inertia scales with them): a scaling sample IS the factor
+    const bool scaled = a->operation == SDX_DR_SCALING;
+    const float base = factor && scaled ? 1.0f : v0;
+    const float s = dr_sched(*a, frame);
+    float v = base;
+    if (s > 0.0f) v = dr_value(*a, s, sdx_hash(B.seed ^ SDX_DR_TAG, (uint64_t)e * SDX_DR_SLOTS + k, draw), base);
+    *out = factor && !scaled ? (v0 != 0.0f ? v / v0 : 1.0f) : v;
+  }
+  __syncthreads();
+  if (t == 0) {
+    B.dr_draw[e] = (int32_t)(draw + 1);
+    if (!first) B.randomize[e] = 0;
+  }
+}
+static void dr_sample(sdx_sim* h, int first, hipStream_t st, const uint8_t* mask = nullptr) {
+  hipLaunchKernelGGL(k_dr_gravity, dim3(1), dim3(256), 0, st, h->d_const, h->buf, h->dr, first, mask);
+  hipLaunchKernelGGL(k_dr_sample, dim3(h->buf.N), dim3(128), 0, st, h->d_const, h->buf, h->dr, first, mask);
 }
 
 extern "C" int sdx_create(const sdx_scene_desc* scene, int32_t num_envs, int32_t device, uint64_t seed, sdx_handle* out) {
@@ -194,6 +322,13 @@ extern "C" int sdx_create(const sdx_scene_desc* scene, int32_t num_envs, int32_t
   // the solver's impulse cache (24.5 KB per env) only exists when the scene asks for the warm start; k_physics<.., false> never reads it
   ALLOC(wkey, scene->warm_start > 0.0f ? (size_t)N * SDX_MAXC : 1);
   ALLOC(wlam, scene->warm_start > 0.0f ? (size_t)N * 3 * SDX_MAXC : 1);
+  ALLOC(dr_dof, (size_t)N * 4 * SDX_NDOF);
+  ALLOC(dr_link, (size_t)N * 2 * SDX_NLINK);
+  ALLOC(dr_brick, (size_t)N * 2 * SDX_NFREE);
+  ALLOC(dr_grav, 3);
+  ALLOC(dr_frame, 2);
+  ALLOC(dr_draw, (size_t)N + 1);
+  B.dr_on = nullptr;
   if (scene->task_kind == 3) {
     ALLOC(tvt_buf, (size_t)N * 652);
     ALLOC(tvt_w, (size_t)1024 * 652 + 1024 + 512 * 1024 + 512 + 128 * 512 + 128 + 2 * 128 + 2);
@@ -255,6 +390,11 @@ extern "C" int sdx_create(const sdx_scene_desc* scene, int32_t num_envs, int32_t
     set_tensor(h, SDX_T_WARM_LAMBDA, B.wlam, SDX_F32, {1});
   }
   set_tensor(h, SDX_T_CAM_ROT, B.cam_rot, SDX_F32, {N, 4});
+  set_tensor(h, SDX_T_DR_DOF, B.dr_dof, SDX_F32, {N, 4, SDX_NDOF});
+  set_tensor(h, SDX_T_DR_LINK, B.dr_link, SDX_F32, {N, 2, SDX_NLINK});
+  set_tensor(h, SDX_T_DR_BRICK, B.dr_brick, SDX_F32, {N, 2, SDX_NFREE});
+  set_tensor(h, SDX_T_DR_GRAVITY, B.dr_grav, SDX_F32, {3});
+  set_tensor(h, SDX_T_DR_FRAME, B.dr_frame, SDX_I64, {2});
   set_tensor(h, SDX_T_JACOBIAN, B.jac_full, SDX_F32, {N, SDX_NLINK - 1, 6, SDX_NDOF});
   if (scene->task_kind == 3) set_tensor(h, SDX_T_TVALUE_OBS, B.tvt_buf, SDX_F32, {N, 652});
   else set_tensor(h, SDX_T_TVALUE_OBS, B.seg_pix, SDX_F32, {1, 1});   // placeholder: the temporal buffer belongs to Search
@@ -296,6 +436,7 @@ extern "C" int sdx_create(const sdx_scene_desc* scene, int32_t num_envs, int32_t
     std::vector<int64_t> ones(N, 1);  // reset_buf = ONES: every env resets on the first step (BT:63)
     HIPCHK(h, hipMemcpy(B.reset, ones.data(), (size_t)N * 8, hipMemcpyHostToDevice));
   }
+  hipLaunchKernelGGL(k_dr_defaults, dim3(N), dim3(128), 0, 0, h->d_const, B);   // the randomization rows hold the scene's values
   sdxk_kinematics(h->d_const, &h->buf, 0);  // first refresh (GS:243-246)
   HIPCHK(h, hipDeviceSynchronize());
   *out = h;
@@ -378,8 +519,39 @@ static int check_launch(sdx_handle h, const char* what) {
   return SDX_OK;
 }
 
+static bool dr_attr_ok(const sdx_dr_attr& a) {
+  if (a.distribution == SDX_DR_NONE) return true;
+  if (a.distribution < SDX_DR_NONE || a.distribution > SDX_DR_LOGUNIFORM) return false;
+  if (a.operation != SDX_DR_ADDITIVE && a.operation != SDX_DR_SCALING) return false;
+  if (a.schedule < SDX_DR_SCHED_NONE || a.schedule > SDX_DR_SCHED_CONSTANT || (a.schedule != SDX_DR_SCHED_NONE && a.schedule_steps <= 0)) return false;
+  if (a.num_buckets < 0 || !std::isfinite(a.range[0]) || !std::isfinite(a.range[1])) return false;
+  if (a.distribution == SDX_DR_LOGUNIFORM && !(a.range[0] > 0.0f && a.range[1] > 0.0f)) return false;
+  if (a.distribution == SDX_DR_GAUSSIAN && a.range[1] < 0.0f) return false;   // sigma (its square root makes the bucket grid)
+  if (a.distribution != SDX_DR_GAUSSIAN && a.range[0] > a.range[1]) return false;
+  return true;
+}
+extern "C" int sdx_set_randomization(sdx_handle h, const sdx_dr_desc* desc, void* stream) {
+  if (!h) return SDX_ERR_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  if (!desc) {
+    h->buf.dr_on = nullptr;
+    hipLaunchKernelGGL(k_dr_defaults, dim3(h->buf.N), dim3(128), 0, st, h->d_const, h->buf);
+    return check_launch(h, "sdx_set_randomization");
+  }
+  const sdx_dr_attr* at[9] = {&desc->gravity, &desc->dof_stiffness, &desc->dof_damping, &desc->dof_lower, &desc->dof_upper,
+                              &desc->link_mass, &desc->link_friction, &desc->brick_mass, &desc->brick_friction};
+  bool ok = desc->frequency >= 1;
+  for (int i = 0; i < 9; ++i) ok = ok && dr_attr_ok(*at[i]);
+  if (!ok) { h->err = "sdx_set_randomization: bad desc (frequency >= 1, known distribution / operation / schedule, schedule_steps > 0, finite ranges)"; return SDX_ERR_INVALID; }
+  h->dr = *desc;
+  h->buf.dr_on = h->buf.dr_draw;
+  dr_sample(h, 1, st);
+  return check_launch(h, "sdx_set_randomization");
+}
+
 extern "C" int sdx_pre_physics(sdx_handle h, const float* actions_dev, void* stream) {
   if (!h || !actions_dev) return SDX_ERR_INVALID;
+  if (h->buf.dr_on) dr_sample(h, 0, (hipStream_t)stream);   // before this step's resets (BT:229-260 runs inside reset_idx)
   sdxk_pre_physics(h->d_const, &h->buf, actions_dev, nullptr, nullptr, 1 | 4, (hipStream_t)stream);
   return check_launch(h, "sdx_pre_physics");
 }
@@ -456,6 +628,7 @@ static int search_reset_if_needed(sdx_handle h, hipStream_t st, int64_t* progres
 extern "C" int sdx_step(sdx_handle h, const float* actions_dev, void* stream) {
   if (!h || !actions_dev) return SDX_ERR_INVALID;
   hipStream_t st = (hipStream_t)stream;
+  if (h->buf.dr_on) dr_sample(h, 0, st);   // before any reset physics of this step, Orient's / Search's settling launches included
   if (h->h_const.sc.task_kind == 3) {
     int64_t p0 = 0;
     const int rc = search_reset_if_needed(h, st, &p0);
@@ -493,6 +666,7 @@ extern "C" int sdxk_scripted_grasp_actions(sdx_handle h, float* close_state_dev,
 }
 extern "C" int sdx_reset_idx(sdx_handle h, const uint8_t* env_mask_dev, const int32_t* pile_choice_dev, void* stream) {
   if (!h || !env_mask_dev) return SDX_ERR_INVALID;
+  if (h->buf.dr_on) dr_sample(h, 0, (hipStream_t)stream, env_mask_dev);   // reset_idx -> apply_randomizations (GS:1395-1396)
   sdxk_pre_physics(h->d_const, &h->buf, nullptr, env_mask_dev, pile_choice_dev, 2, (hipStream_t)stream);
   return check_launch(h, "sdx_reset_idx");
 }

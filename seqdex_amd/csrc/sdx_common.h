@@ -71,7 +71,17 @@ struct SdxBuf {
   uint32_t* wkey;          // [N, SDX_MAXC] contact identity (pair rank << 6 | direction << 5 | sample), ascending pair rank
   float* wlam;             // [N, 3, SDX_MAXC] accumulated impulses (normal, two tangents)
   float* insert_aux;       // [N,8] InsertSim: 0..2 rot_err of the last pre_physics_step (IS:1539), 3 |brick - site|, 4 rot_dist
+  // domain randomization (include/seqdex.h sdx_set_randomization): per-env physics parameters, read by k_physics_dr only.  dr_on == nullptr:
+  // randomization is off and k_physics<512> runs on the scene constants (a zeroed SdxBuf - the emulator's physics driver - is "off")
+  const int32_t* dr_on;    // non-null (= dr_draw) while randomization is on
+  float* dr_dof;           // [N,4,23] kp, kd, lower, upper
+  float* dr_link;          // [N,2,24] link mass factor, link friction
+  float* dr_brick;         // [N,2,72] free brick mass factor, brick friction
+  float* dr_grav;          // [3]
+  long long* dr_frame;     // [2] frame (physics launches while on), frame of the last gravity randomization
+  int32_t* dr_draw;        // [N + 1] samplings of each env so far, [N] = of gravity (the counter of the RNG)
 };
+#define SDX_DR_SLOTS 287   // RNG slots per env: 4 x 23 DOF, 2 x 24 link, 2 x 72 brick quantities (284), gravity in slots 284..286 of env 0
 
 // An empty asm the compiler must assume rewrites x: values derived from x afterwards (LDS addresses of the same rows in every
 // solver iteration) are recomputed where they are used instead of being kept in registers across the loop.  (tests/hipemu compiles

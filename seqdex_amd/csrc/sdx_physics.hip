@@ -138,6 +138,7 @@ struct PhysLds {
   // matrix; the unsorted CSR fill order during the solver set-up; and the per-contact impulse P of the current iteration
   float P[3][MAXC];
   unsigned short ent[2 * MAXC];   // CSR entries: contact index | side << 15, grouped by body (bricks, then links), ascending contact index
+  float lmf[NL];        // k_physics<.. | SDX_PHYS_DR> only: this env's link mass (and inertia) factors (last: nothing above moves)
 };
 #define S_T(S) (reinterpret_cast<float (*)[HP]>(&(S).P[0][0]))                       // L^-1 (mass matrix phase)
 #define S_PAIRS(S) (reinterpret_cast<uint32_t*>(&(S).P[2][0]))                       // candidate body pairs (collide)
@@ -155,6 +156,9 @@ static_assert(MAXSP + MAXP + 1 <= 3 * MAXC, "box pairs and body-pair offsets fit
 static_assert(3 * 8 * 33 < 1024, "box-pair counts of three body pairs per lane in 10 bits");
 static_assert(2 * MAXC * sizeof(unsigned short) == MAXC * sizeof(uint32_t), "contact keys alias the CSR entries");
 static_assert(sizeof(PhysLds) <= 80 * 1024, "two workgroups per CU need <= 80 KiB of LDS each");
+// The randomization variant (k_physics<512 | SDX_PHYS_DR>) uses the same layout: PhysLds leaves ~50 bytes of the 80 KiB besides lmf, too few
+// for this env's other parameter rows (include/seqdex.h SDX_T_DR_*), which are read from HBM where they are used - once per step or
+// substep per DOF, once per solve per contact (friction): no access inside the solver's iteration loop
 
 struct Box { f3 c; f4 q; f3 h; };
 // phase clock of env B.dbg_env (tools/time_physics.py): compiled in only with -DSDX_PHASE_CLOCK (make prof -> lib/libseqdex_prof.so, selected
@@ -515,7 +519,9 @@ __device__ __forceinline__ void twists_wave0(PhysLds& S, int tid);
 // w_k = w_p + a_k qd_k, al_k = al_p + w_p x (a_k qd_k), ao_k = ao_p + al_p x r + w_p x (w_p x r) (recursive Newton-Euler at zero joint
 // acceleration, fixed base, no gravity on the robot).  with_bias: the velocity-product wrenches the drive needs; with_inertia: the world
 // inertia tensors the mass matrix needs.
-__device__ __forceinline__ void fk_wave0(const SdxConst* C, PhysLds& S, int tid, bool with_inertia, bool with_bias, long long* dbg = nullptr) {
+// lmf: scale link masses and inertias by S.lmf (domain randomization; false = the scene's masses and inertias)
+__device__ __forceinline__ void fk_wave0(const SdxConst* C, PhysLds& S, int tid, bool with_inertia, bool with_bias, long long* dbg = nullptr,
+                                         bool lmf = false) {
   const sdx_scene_desc& sc = C->sc;
   const bool link = tid > 0 && tid < NL;
   // this lane's link constants, fetched once (all loads in flight together)
@@ -638,8 +644,14 @@ __device__ __forceinline__ void fk_wave0(const SdxConst* C, PhysLds& S, int tid,
       st3(S.lao[tid], aok);
       const f3 wk = ld3(S.bw[NF + tid]);
       const f3 acom = aok + cross(alk, dk) + cross(wk, cross(wk, dk));
-      st3(S.lF[tid], acom * mass);
-      st3(S.lN[tid], inertia_mul(qk, I6, alk) + cross(wk, inertia_mul(qk, I6, wk)));
+      if (lmf) {   // the link's mass and inertia x its factor, applied where they are stored (loaded early, they cost the variant scratch)
+        const float f = S.lmf[tid];
+        st3(S.lF[tid], acom * (mass * f));
+        st3(S.lN[tid], (inertia_mul(qk, I6, alk) + cross(wk, inertia_mul(qk, I6, wk))) * f);
+      } else {
+        st3(S.lF[tid], acom * mass);
+        st3(S.lN[tid], inertia_mul(qk, I6, alk) + cross(wk, inertia_mul(qk, I6, wk)));
+      }
     }
   }
   SSTAMP(12);
@@ -661,6 +673,11 @@ __device__ __forceinline__ void fk_wave0(const SdxConst* C, PhysLds& S, int tid,
     S.lI[tid][3] = c0.x * ex.y + c1.x * ey.y + c2.x * ez.y;
     S.lI[tid][4] = c0.x * ex.z + c1.x * ey.z + c2.x * ez.z;
     S.lI[tid][5] = c0.y * ex.z + c1.y * ey.z + c2.y * ez.z;
+    if (lmf) {
+      const float f = S.lmf[tid];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) S.lI[tid][i] *= f;
+    }
   }
   WAVE_SYNC();
 }
@@ -712,8 +729,8 @@ __device__ __forceinline__ void tri_index(int idx, int* i, int* j) {   // idx ->
 template <int NT>
 __device__ __forceinline__ void broad_mask_part(const SdxConst* C, PhysLds& S, int tid, int part);
 
-template <int NT>
-__device__ __forceinline__ void mass_matrix(const SdxConst* C, PhysLds& S, int tid, float h, long long* dbg) {
+template <int NT, bool DR = false>
+__device__ __forceinline__ void mass_matrix(const SdxConst* C, PhysLds& S, int tid, float h, long long* dbg, const float* drow = nullptr) {
   const sdx_scene_desc& sc = C->sc;
   for (int idx = tid; idx < ND * (ND + 1) / 2; idx += NT) {
     int i, j;
@@ -750,7 +767,8 @@ __device__ __forceinline__ void mass_matrix(const SdxConst* C, PhysLds& S, int t
         }
       }
     }
-    if (i == j) s += sc.armature[i] + h * sc.kd[i] + h * h * sc.kp[i];
+    if (DR) { if (i == j) s += sc.armature[i] + h * drow[ND + i] + h * h * drow[i]; }   // drow: this env's [kp; kd; lower; upper]
+    else if (i == j) s += sc.armature[i] + h * sc.kd[i] + h * h * sc.kp[i];
     S.A[i][j] = s;
     S.A[j][i] = s;
   }
@@ -1213,13 +1231,13 @@ __device__ __forceinline__ float robot_w(const PhysLds& S, int k, f3 p, f3 d) {
   return 2.0f * acc;
 }
 
-template <int NT, bool WARM>
+template <int NT, bool WARM, bool DR = false>
 // Warm start (oracle: solve()): wcount / wkey / wlam are THIS env's impulse cache in HBM.  A contact that existed
 // in the previous solve (same pair, direction and sample) starts from sc.warm_start x the impulses it ended with; iteration -1 of the
 // loop below spreads those impulses over the bodies with the gather machinery of a normal iteration.  WARM is a template parameter:
 // the default (cold) solver carries none of this code (it cost 2.6 % of the kernel as a run-time switch).
 __device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, float h, bool last_substep, long long* dbg,
-                                      int32_t* wcount, uint32_t* wkey, float* wlam, int abl_bits) {
+                                      int32_t* wcount, uint32_t* wkey, float* wlam, int abl_bits, const float* bfr = nullptr, const float* lfr = nullptr) {
   constexpr int CPT = MAXC / NT;   // contact rows owned by one lane
   constexpr int NB = NF + NL;      // bodies with a CSR list: bricks 0..71, links 72..95
   static_assert(CPT * NT == MAXC, "NT must divide SDX_MAXC");
@@ -1232,6 +1250,7 @@ __device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, fl
   // impulses, un-split inverse masses of both sides
   int ab[CPT];
   float vtgt[CPT];
+  float muq[CPT];   // DR: friction of each contact = mean of its two bodies' coefficients (PhysX's default combine mode)
   uint32_t ckey[CPT];
   const float beta = sc.warm_start;
   const float inv_age = sc.warm_age > 0.0f ? 1.0f / sc.warm_age : 1e30f;
@@ -1645,11 +1664,17 @@ __device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, fl
     const int a = ab[q] & 0xff, b = (ab[q] >> 8) & 0xff;
     const int sa = a < NF ? a : (a != BODY_W ? NF : NF + 1), sb = b < NF ? b : (b != BODY_W ? NF : NF + 1);
     ab[q] = (ab[q] & 0xffff) | (sa << 16) | (sb << 24);
+    if (DR) {   // coefficients by body-table row: bricks (bfr), links (lfr), the static world keeps the scene's
+      const float fa = a < NF ? bfr[a] : (a != BODY_W ? lfr[a - NF] : sc.friction);
+      const float fb = b < NF ? bfr[b] : (b != BODY_W ? lfr[b - NF] : sc.friction);
+      muq[q] = 0.5f * (fa + fb);
+    }
   }
   // fresh values for the loop: whatever the set-up phases above did to these registers, inside the loop they are plain registers again
 #pragma unroll
   for (int q = 0; q < CPT; ++q) {
     SDX_OPAQUE(ab[q]); SDX_OPAQUE(vtgt[q]);
+    if (DR) SDX_OPAQUE(muq[q]);
 #pragma unroll
     for (int r = 0; r < 3; ++r) { SDX_OPAQUE(lam[q][r]); SDX_OPAQUE(wA[q][r]); SDX_OPAQUE(wB[q][r]); }
   }
@@ -1705,7 +1730,7 @@ __device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, fl
             const float w1 = na * wA[q][1] + nb * wB[q][1];
             const float w2 = na * wA[q][2] + nb * wB[q][2];
             const float ln = fmaxf(0.0f, lam0 - relax * (vn - vtgt[q]) * SDX_RCP(w0));
-            const float lim = mu * ln;
+            const float lim = (DR ? muq[q] : mu) * ln;
             float l1 = lam1 - relax * dot(vr, t1) * SDX_RCP(w1);
             l1 = fminf(lim, fmaxf(-lim, l1));
             float l2 = lam2 - relax * dot(vr, t2) * SDX_RCP(w2);
@@ -1938,15 +1963,20 @@ __device__ __forceinline__ void write_kinematics(const SdxConst* C, PhysLds& S, 
 }
 
 // per-env constants into LDS (bricks, robot boxes, statics, ancestor masks)
-template <int NT>
-__device__ __forceinline__ void load_constants(const SdxConst* C, PhysLds& S, int e, int tid) {
+template <int NT, bool DR = false>
+__device__ __forceinline__ void load_constants(const SdxConst* C, PhysLds& S, int e, int tid, const SdxBuf* Bp = nullptr) {
   const sdx_scene_desc& sc = C->sc;
   const int segb = seg_actor(e) - SDX_ACTOR_BRICK0;
   if (tid == 0) {
     S.seg_brick = segb;
     st3(S.bp[BODY_W], F3(0, 0, 0)); st3(S.bv[BODY_W], F3(0, 0, 0)); st3(S.bw[BODY_W], F3(0, 0, 0));   // the static world
   }
-  if (tid < NL) { S.anc[tid] = C->anc[tid]; S.lmass[tid] = sc.link_mass[tid]; }
+  if (DR) {   // this env's link mass factors (SDX_T_DR_LINK row 0)
+    if (tid < NL) {
+      const float f = Bp->dr_link[(size_t)e * 2 * NL + tid];
+      S.anc[tid] = C->anc[tid]; S.lmass[tid] = sc.link_mass[tid] * f; S.lmf[tid] = f;
+    }
+  } else if (tid < NL) { S.anc[tid] = C->anc[tid]; S.lmass[tid] = sc.link_mass[tid]; }
   if (tid < ND) {
     uint32_t d = 0;
     for (int k = 1; k < NL; ++k) d |= ((C->anc[k] >> tid) & 1u) << k;
@@ -1959,6 +1989,7 @@ __device__ __forceinline__ void load_constants(const SdxConst* C, PhysLds& S, in
     const int t = sc.brick_type[i];
     S.btype[i] = (unsigned char)t;
     S.bim[i] = (i == segb ? 1.0f / sc.seg_mass_scale : 1.0f) / sc.brick_mass[t];
+    if (DR) S.bim[i] /= Bp->dr_brick[(size_t)e * 2 * NF + i];
   }
   // collision compounds of the 8 brick types (centre-of-mass frame) and the hollow compound of this env's target brick
   if (tid < SDX_NBRICK_TYPES) {
@@ -1992,8 +2023,22 @@ __device__ __forceinline__ void load_constants(const SdxConst* C, PhysLds& S, in
 }
 
 // ---------------------------------------------------------------- the step kernel
-template <int NT>
-__global__ __launch_bounds__(NT, 2 * NT / 256) void k_physics(const SdxConst* __restrict__ C, SdxBuf B) {
+// NTD = threads | SDX_PHYS_DR.  k_physics<512 | SDX_PHYS_DR> is the domain-randomization variant: drive gains, joint limits, link / brick
+// masses, friction and gravity come from this env's rows of SDX_T_DR_* instead of the scene constants.  (The flag rides in the low bit of
+// the thread count so that k_physics<512> keeps its symbol and its code: a second template parameter renames the symbol, a __global__
+// wrapper around a shared body changes the default kernel's register allocation.)
+#define SDX_PHYS_DR 1
+// k_physics<.. | SDX_PHYS_DR>: row e of one of the SDX_T_DR_* tensors, addressed from an opaque copy of e at the point of use (nothing is
+// hoisted to the kernel's entry and kept alive over the substeps)
+__device__ __forceinline__ const float* dr_row(const float* base, int e, int width, int off) {
+  int ee = e;
+  SDX_OPAQUE_S(ee);
+  return base + (size_t)ee * width + off;
+}
+template <int NTD>
+__global__ __launch_bounds__(NTD & ~SDX_PHYS_DR, 2 * (NTD & ~SDX_PHYS_DR) / 256) void k_physics(const SdxConst* __restrict__ C, SdxBuf B) {
+  constexpr int NT = NTD & ~SDX_PHYS_DR;
+  constexpr bool DR = (NTD & SDX_PHYS_DR) != 0;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   PhysLds& S = *reinterpret_cast<PhysLds*>(smem);
   // launch order: B.order lists the envs by the cost of their previous step, longest first (k_order below)
@@ -2029,7 +2074,11 @@ __global__ __launch_bounds__(NT, 2 * NT / 256) void k_physics(const SdxConst* __
   const f3 r_p = ld3(srow), r_v = ld3(srow + 7), r_w = ld3(srow + 10);
   const f4 r_o = ld4(srow + 3);
   const f3 r_com = ld3(sc.brick_com[sc.brick_type[tid < NF ? tid : 0]]);
-  load_constants<NT>(C, S, e, tid);
+  load_constants<NT, DR>(C, S, e, tid, &B);
+  if (DR && blockIdx.x == 0 && tid == 0) B.dr_frame[0] += 1;   // gym.get_frame_count: one per launch (read by the next launch's sampling)
+  // this env's rows of SDX_T_DR_* (include/seqdex.h): [kp; kd; lower; upper], [link mass factor; link friction], [brick mass factor; friction].
+  // Addressed where they are used (DR_ROW): pointers and gravity held over the whole kernel pushed the variant into scratch
+#define DR_ROW(field, width, off) (DR ? dr_row(B.field, e, (width), (off)) : nullptr)
   if (tid < ND) { S.q[tid] = r_q; S.qd[tid] = r_qd; S.tgt[tid] = r_tg; }
   if (tid < NF) {
     const f4 q = qnormalize(r_o);
@@ -2056,11 +2105,11 @@ __global__ __launch_bounds__(NT, 2 * NT / 256) void k_physics(const SdxConst* __
     if (sub == 0) {   // M(q) is evaluated once per step (frozen over the substeps)
       // wave 0: forward kinematics + inertias; waves 1..7 meanwhile: the broadphase tests of the brick / brick and brick / static
       // candidates (part 0), which depend on nothing the robot does in this substep
-      if (tl < 64) fk_wave0(Cs, S, tl, true, true, e == B.dbg_env ? B.dbg : nullptr);
+      if (tl < 64) fk_wave0(Cs, S, tl, true, true, e == B.dbg_env ? B.dbg : nullptr, DR);
       else if (!ABL(32)) broad_mask_part<NT>(Cs, S, tl, 0);
       __syncthreads();
       PSTAMP(1);
-      if (!ABL(512)) mass_matrix<NT>(Cs, S, tl, h, e == B.dbg_env ? B.dbg : nullptr);   // (part 1 of the mask beside its wave-0 section)
+      if (!ABL(512)) mass_matrix<NT, DR>(Cs, S, tl, h, e == B.dbg_env ? B.dbg : nullptr, DR_ROW(dr_dof, 4 * ND, 0));   // (part 1 of the mask beside its wave-0 section)
       else { if (tl >= 64) broad_mask_part<NT>(Cs, S, tl, 1); __syncthreads(); }
       PSTAMP(2);
     }
@@ -2068,9 +2117,11 @@ __global__ __launch_bounds__(NT, 2 * NT / 256) void k_physics(const SdxConst* __
     if (ABL(256) && sub != 0) {
       if (tl >= 64) { broad_mask_part<NT>(Cs, S, tl, 0); broad_mask_part<NT>(Cs, S, tl, 1); }
     } else if (tl < 64) {
-      if (sub != 0) { fk_wave0(Cs, S, tl, false, true); WAVE_SIGNAL(&S.fkflag, sub); }   // (the robot boxes are placed: part 1 of the mask may start)
+      if (sub != 0) { fk_wave0(Cs, S, tl, false, true, nullptr, DR); WAVE_SIGNAL(&S.fkflag, sub); }   // (the robot boxes are placed: part 1 of the mask may start)
       if (tl < ND) {
-        const float t = scl.kp[tl] * (S.tgt[tl] - S.q[tl]) - (scl.kd[tl] + h * scl.kp[tl]) * S.qd[tl];
+        const float* drow = DR_ROW(dr_dof, 4 * ND, 0);
+        const float t = DR ? drow[tl] * (S.tgt[tl] - S.q[tl]) - (drow[ND + tl] + h * drow[tl]) * S.qd[tl]   // (drow: kp, kd rows)
+                           : scl.kp[tl] * (S.tgt[tl] - S.q[tl]) - (scl.kd[tl] + h * scl.kp[tl]) * S.qd[tl];
         // velocity-product bias torque of dof tl: inertial wrenches of the links below it, projected on its axis
         float tc = 0.0f;
         const f3 aj = ld3(S.la[tl + 1]), oj = ld3(S.bp[NF + tl + 1]);
@@ -2103,7 +2154,12 @@ __global__ __launch_bounds__(NT, 2 * NT / 256) void k_physics(const SdxConst* __
       twists_wave0(S, tl);
     } else {
       for (int i = tl - 64; i < NF; i += NT - 64) {
-        S.bv[i][0] += scl.gravity[0] * h; S.bv[i][1] += scl.gravity[1] * h; S.bv[i][2] += scl.gravity[2] * h;
+        if (DR) {   // (opaque per brick: a product hoisted out of the loop is not fused with the add - the default kernel's v_fma here)
+          float g0 = B.dr_grav[0], g1 = B.dr_grav[1], g2 = B.dr_grav[2];
+          SDX_OPAQUE(g0); SDX_OPAQUE(g1); SDX_OPAQUE(g2);
+          S.bv[i][0] += g0 * h; S.bv[i][1] += g1 * h; S.bv[i][2] += g2 * h;
+        }
+        else { S.bv[i][0] += scl.gravity[0] * h; S.bv[i][1] += scl.gravity[1] * h; S.bv[i][2] += scl.gravity[2] * h; }
       }
       // later substeps: both parts of the broadphase mask beside wave 0's FK + drive (the first substep had them beside FK and the factorisation)
       if (sub != 0 && !ABL(32)) {
@@ -2123,17 +2179,19 @@ __global__ __launch_bounds__(NT, 2 * NT / 256) void k_physics(const SdxConst* __
     }
     PSTAMP(4);
     if (scl.warm_start > 0.0f)
-      solve<NT, true>(Cs, S, tl, h, sub == nsub - 1, (sub == 0 && e == B.dbg_env) ? B.dbg : nullptr, B.wcount + e, B.wkey + (size_t)e * MAXC, B.wlam + (size_t)e * 3 * MAXC, abl_bits);
+      solve<NT, true, DR>(Cs, S, tl, h, sub == nsub - 1, (sub == 0 && e == B.dbg_env) ? B.dbg : nullptr, B.wcount + e, B.wkey + (size_t)e * MAXC, B.wlam + (size_t)e * 3 * MAXC, abl_bits, DR_ROW(dr_brick, 2 * NF, NF), DR_ROW(dr_link, 2 * NL, NL));
     else
-      solve<NT, false>(Cs, S, tl, h, sub == nsub - 1, (sub == 0 && e == B.dbg_env) ? B.dbg : nullptr, nullptr, nullptr, nullptr, abl_bits);
+      solve<NT, false, DR>(Cs, S, tl, h, sub == nsub - 1, (sub == 0 && e == B.dbg_env) ? B.dbg : nullptr, nullptr, nullptr, nullptr, abl_bits, DR_ROW(dr_brick, 2 * NF, NF), DR_ROW(dr_link, 2 * NL, NL));
     PSTAMP(5);
     // F: integrate
     if (tl < ND) {
       float v = S.qd[tl] * (1.0f - h * scl.robot_angular_damping);   // GS:546
       v = fminf(scl.vel_limit[tl], fmaxf(-scl.vel_limit[tl], v));
       float qn = S.q[tl] + h * v;
-      if (qn < scl.lower[tl]) { qn = scl.lower[tl]; v = fmaxf(v, 0.0f); }
-      if (qn > scl.upper[tl]) { qn = scl.upper[tl]; v = fminf(v, 0.0f); }
+      const float* drow = DR_ROW(dr_dof, 4 * ND, 0);
+      const float lo = DR ? drow[2 * ND + tl] : scl.lower[tl], up = DR ? drow[3 * ND + tl] : scl.upper[tl];
+      if (qn < lo) { qn = lo; v = fmaxf(v, 0.0f); }
+      if (qn > up) { qn = up; v = fminf(v, 0.0f); }
       S.q[tl] = qn;
       S.qd[tl] = v;
     }
@@ -2152,6 +2210,7 @@ __global__ __launch_bounds__(NT, 2 * NT / 256) void k_physics(const SdxConst* __
     PSTAMP(6);
   }
 
+#undef DR_ROW
 #ifdef SDX_PHASE_CLOCK
   if (threadIdx.x == 0 && e == B.dbg_env) B.dbg[15] = (long long)__builtin_readcyclecounter();   // end of the last substep
 #endif
@@ -2265,13 +2324,15 @@ static void physics_init() {
   if (!done) {
     done = true;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_physics<512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PhysLds));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_physics<512 | SDX_PHYS_DR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PhysLds));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_kinematics), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PhysLds));
   }
 }
 extern "C" int sdxk_physics_threads() { return 512; }
 extern "C" void sdxk_physics(const SdxConst* C, const SdxBuf* B, hipStream_t st) {
   physics_init();
-  hipLaunchKernelGGL(k_physics<512>, dim3(B->N), dim3(512), sizeof(PhysLds), st, C, *B);
+  if (B->dr_on) hipLaunchKernelGGL(k_physics<512 | SDX_PHYS_DR>, dim3(B->N), dim3(512), sizeof(PhysLds), st, C, *B);   // domain randomization on
+  else hipLaunchKernelGGL(k_physics<512>, dim3(B->N), dim3(512), sizeof(PhysLds), st, C, *B);
   if (B->order && B->cost) hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, st, *B);
 }
 extern "C" void sdxk_kinematics(const SdxConst* C, const SdxBuf* B, hipStream_t st) {

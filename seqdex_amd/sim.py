@@ -181,6 +181,24 @@ class SdxSim:
         self._check(self.lib.sdx_set_indexed(self.h, _abi.T[name], C.c_void_p(src.data_ptr()), C.c_void_p(actor_ids.data_ptr()),
                                              int(actor_ids.numel()), _stream_ptr(self.device)))
 
+    def set_randomization(self, spec):
+        """domain randomization (include/seqdex.h sdx_set_randomization): `spec` = a task YAML's
+        randomization_params mapping, a ready domain_randomization.DrDesc, or None (off: the physics returns to the scene constants).
+        On: the first randomization is sampled on the device at once.  Returns the parse report (None for a DrDesc / None)."""
+        from . import domain_randomization as dr
+        report = None
+        if spec is None:
+            desc = None
+        elif isinstance(spec, dr.DrDesc):
+            desc = spec
+        else:
+            desc, report = dr.parse(spec)
+        self._dr_desc = desc                  # (kept alive for the call)
+        ptr = C.cast(C.pointer(desc), C.c_void_p) if desc is not None else None
+        stream = _stream_ptr(self.device) if self.device.type == "cuda" else None
+        self._check(self.lib.sdx_set_randomization(self.h, ptr, stream))
+        return report
+
     def close(self):
         if getattr(self, "h", None) is not None and self.h.value:
             self._tensors.clear()

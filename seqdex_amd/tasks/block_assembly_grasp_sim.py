@@ -92,6 +92,11 @@ class BlockAssemblyGraspSim:
             flat.append(((torch.rand(fout, fin, generator=g) * 2 - 1) * b).reshape(-1))
             flat.append((torch.rand(fout, generator=g) * 2 - 1) * b)
         s.set_tvalue_weights(torch.cat(flat).numpy())
+        # domain randomization (BT:229-420; the reference's tasks call apply_randomizations at create and in every reset_idx,
+        # GS:106-107,515-516,1395-1396): sampled on the device, the later draws happen inside sdx_step
+        self.randomize = bool(cfg.get("task", {}).get("randomize", False))
+        self.randomization_params = cfg.get("task", {}).get("randomization_params", {})
+        self.randomization_report = s.set_randomization(self.randomization_params) if self.randomize else None
 
     # ------------------------------------------------------------------ BaseTask.step, BT:130-150
     def step(self, actions):

@@ -1,6 +1,7 @@
 """Static check of k_physics<512>'s gfx950 code: registers, scratch bytes per lane, and the scratch / LDS / VALU instruction counts of the
 solver's iteration loop (the ISA between the source lines of the loop head and of its closing stamp, via -gline-tables-only).
-usage: python tools/isa_check.py [extra hipcc flags...]      (cross-compiles; no GPU needed)"""
+usage: python tools/isa_check.py [--randomize] [extra hipcc flags...]      (cross-compiles; no GPU needed)
+--randomize: the same report for the domain-randomization variant k_physics<512 | SDX_PHYS_DR> (= k_physics<513>)"""
 import os
 import re
 import subprocess
@@ -9,7 +10,10 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "seqdex_amd", "csrc", "sdx_physics.hip")
-KERN = "_Z9k_physicsILi512EEvPK8SdxConst6SdxBuf"
+RANDOMIZE = "--randomize" in sys.argv
+if RANDOMIZE:
+    sys.argv.remove("--randomize")
+KERN = "_Z9k_physicsILi513EEvPK8SdxConst6SdxBuf" if RANDOMIZE else "_Z9k_physicsILi512EEvPK8SdxConst6SdxBuf"
 
 src = open(SRC).read().split("\n")
 lo = next(i for i, l in enumerate(src) if "for (int it = it0;" in l) + 1
@@ -19,7 +23,7 @@ with tempfile.TemporaryDirectory() as td:
            "-Rpass-analysis=kernel-resource-usage", "-save-temps=obj", "-c", SRC, "-o", os.path.join(td, "p.o")] + sys.argv[1:]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=td)
     rem = r.stderr
-    blk = rem[rem.index("k_physicsILi512"):]
+    blk = rem[rem.index("k_physicsILi513" if RANDOMIZE else "k_physicsILi512"):]
     for key in ("VGPRs:", "ScratchSize [bytes/lane]:", "SGPRs Spill:", "VGPRs Spill:", "Occupancy [waves/SIMD]:"):
         m = re.search(re.escape(key) + r"\s*(\d+)", blk)
         print(key, m.group(1) if m else "?")

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """k_physics timing on one MI355X: average launch time at N envs (HIP events) and the phase clock of env 0 (SDX_T_DEBUG stamps).
-usage: python tools/time_physics.py [N] [warm-steps]"""
+usage: python tools/time_physics.py [N] [warm-steps] [--randomize]
+--randomize: the randomization variant of k_physics with the shipped randomization_params sampled past their schedules"""
 import json
 import os
 import sys
@@ -12,6 +13,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from seqdex_amd.tasks.block_assembly_grasp_sim import BlockAssemblyGraspSim  # noqa: E402
 
+randomize = "--randomize" in sys.argv
+if randomize:
+    sys.argv.remove("--randomize")
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 warm = int(sys.argv[2]) if len(sys.argv) > 2 else 24
 cfg = yaml.safe_load(open(os.path.join(ROOT, "seqdex_amd/cfg/allegro_hand_block_assembly_grasp_sim.yaml")))
@@ -20,6 +24,9 @@ if os.environ.get("SDX_TP_ITERS"):          # ablation: solver iterations per su
     cfg.setdefault("sim", {}).setdefault("physx", {})["num_position_iterations"] = int(os.environ["SDX_TP_ITERS"])
 task = BlockAssemblyGraspSim(cfg, device_type="cuda", device_id=0, headless=True, seed=22, piles_per_type=8)
 s = task.sim
+if randomize:
+    s.DR_FRAME[0] = 50000
+    s.set_randomization(cfg["task"]["randomization_params"])
 g = torch.Generator().manual_seed(0)
 for _ in range(warm):                         # random flailing: the contact-rich workload of the bench
     task.step((torch.rand(n, 23, generator=g) * 2 - 1).cuda())
@@ -56,7 +63,7 @@ if len(d) >= 64 + 2 * n and d[64:].any():     # profiling build: (entry, exit) s
              "env_cycles_mean_without": float(dur[~heavy].mean()) if (~heavy).any() else None,
              "corr(env_cycles, contacts)": float(np.corrcoef(dur, nc)[0, 1])}
 denv = int(os.environ.get("SDX_DEBUG_ENV", "0"))
-print(json.dumps({"debug_env": denv, "debug_env_contacts": int(nc[denv]), "debug_env_has_robot_contact": bool(cf[denv] > 0),
+print(json.dumps({"randomize": randomize, "debug_env": denv, "debug_env_contacts": int(nc[denv]), "debug_env_has_robot_contact": bool(cf[denv] > 0),
                   "envs_with_robot_contact": int((cf > 0).sum()), "first_robot_contact_envs": [int(i) for i in (cf > 0).nonzero()[0][:6]],
                   "solver_iters": int(os.environ.get("SDX_TP_ITERS", 16)), "threads_per_env": int(s.lib.sdxk_physics_threads()), "n_envs": n, "k_physics_ms": ms,
                   "env_steps_per_s": n / (ms * 1e-3), "contacts_mean": float(nc.mean()), "contacts_max": int(nc.max()),
