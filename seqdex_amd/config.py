@@ -80,11 +80,24 @@ def get_args(argv=None):
     return args
 
 
+def _load_yaml(path):
+    with open(path) as f:
+        return yaml.safe_load(f)
+
+
+def task_cfg(task):
+    """the shipped task YAML of `task` as a fresh dict"""
+    return _load_yaml(os.path.join(HERE, TASK_CFG[task]))
+
+
+def train_cfg(task):
+    """the shipped rl_games YAML of `task` as a fresh dict"""
+    return _load_yaml(os.path.join(HERE, TRAIN_CFG[task]))
+
+
 def load_cfg(args):
-    with open(args.cfg_train) as f:
-        cfg_train = yaml.safe_load(f)
-    with open(args.cfg_env) as f:
-        cfg = yaml.safe_load(f)
+    cfg_train = _load_yaml(args.cfg_train)
+    cfg = _load_yaml(args.cfg_env)
     if args.num_envs > 0:                                                                                   # CF:101-102
         cfg["env"]["numEnvs"] = args.num_envs
     if args.episode_length > 0:                                                                             # CF:104-105

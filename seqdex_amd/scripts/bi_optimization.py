@@ -19,6 +19,8 @@ import torch
 from ..config import get_args
 from ..train_rlgames import build
 from ..tvalue_trainer import TValue_Trainer, flat_from_state_dict
+from ..vec_task_rlgames import RLgamesVecTaskPython
+from .scripted_grasp import scripted_grasp_controller
 
 
 def main_rlgames(task, num_envs, use_t_value=False, policy_path="", max_iterations=0, task_kwargs=None, tvalue_state=None, keep=False,
@@ -112,7 +114,7 @@ def block_assembly(rounds=10, num_envs=512, epochs=0, tvalue_rollout=10000, inse
     gates: {"orient": 0.99, "grasp": 0.8} harvest thresholds on the transition value (OR:1203, GS:1406) while no transition value has been
     fitted yet; gates_after_fit: the same once one has (default: the reference's thresholds).
     grasp_harvest_stand_in: when the freshly trained grasp policy has not carried a single brick to the insertion side yet (the reference's
-    grasp checkpoint is from epoch 19 000, README.md:90), play two episodes of evaluation.scripted_grasp_controller on the same task so that
+    grasp checkpoint is from epoch 19 000, README.md:90), play two episodes of scripted_grasp.scripted_grasp_controller on the same task so that
     InsertSim starts from REAL terminal states of this engine; brick-type groups still empty get InsertSim's synthetic stand-ins.  Both are
     named in the report.  Without it such a round hands `None` on and InsertSim synthesises all of its states (round-3 behaviour).  The same
     stand-in plays two episodes at the end of the BACKWARD grasp leg when that leg logged too few successful outcomes for a fit (the trainer
@@ -127,8 +129,6 @@ def block_assembly(rounds=10, num_envs=512, epochs=0, tvalue_rollout=10000, inse
         return ({"tvalue_gate": g["orient"]} if "orient" in g else {}), ({"harvest_tvalue_gate": g["grasp"]} if "grasp" in g else {})
 
     def scripted_episodes(task_obj, episodes=2):
-        from .evaluation import scripted_grasp_controller
-        from ..vec_task_rlgames import RLgamesVecTaskPython
         env = RLgamesVecTaskPython(task_obj, "cuda:0")
         env.reset()
         for step in range(episodes * 160):
@@ -158,7 +158,7 @@ def block_assembly(rounds=10, num_envs=512, epochs=0, tvalue_rollout=10000, inse
         if cnt.min() == 0 and grasp_harvest_stand_in:
             scripted_episodes(grasp)
             cnt = grasp.sim.HARVEST_COUNT.cpu().numpy()
-            harvest_by = "evaluation.scripted_grasp_controller, two episodes on the trained task (STAND-IN: the policy of %d epochs harvested nothing)" % se("grasp")
+            harvest_by = "scripted_grasp.scripted_grasp_controller, two episodes on the trained task (STAND-IN: the policy of %d epochs harvested nothing)" % se("grasp")
         # the harvest is handed on as it is: a brick-type group that harvested nothing makes BlockAssemblyInsertSim raise (as IS:1449
         # samples an empty list) unless grasp_harvest_stand_in asks for synthetic stand-ins for exactly those groups; only a harvest that
         # is empty altogether leaves the task to synthesise all its start states, and the report says so (a partial harvest
@@ -202,7 +202,7 @@ def block_assembly(rounds=10, num_envs=512, epochs=0, tvalue_rollout=10000, inse
         outcomes_by = "the fine-tuned grasp policy"
         if grasp_harvest_stand_in and int(grasp.sim.TV_COUNT[0]) <= 100:
             scripted_episodes(grasp)
-            outcomes_by = "the fine-tuned grasp policy + two episodes of evaluation.scripted_grasp_controller (STAND-IN: the policy alone logged too few successes for a fit)"
+            outcomes_by = "the fine-tuned grasp policy + two episodes of scripted_grasp.scripted_grasp_controller (STAND-IN: the policy alone logged too few successes for a fit)"
         tv_before = tv
         tv = transition_value_trainer(grasp, tvalue_rollout, tv, seed=100 + i)            # bi_optimization.py:122: fit on GraspSim's own outcomes
         _handoff(report, "T-value fitted on GraspSim's outcomes -> Orient", None if tv is tv_before or tv is None else list(tv.values()), "no fit")
@@ -275,7 +275,7 @@ def one_round_at_size(num_envs=4096, mixed_precision=True, stage_epochs=None, tv
            "stage_epochs": stage_epochs, "tvalue_fit_iterations": tvalue_rollout,
            "stand_ins": ["harvest gates 0.0 in the forward pass of this first round: no transition value has been fitted before it; 0.5 / 0.28 "
                          "(not the reference's 0.99 / 0.8) in the backward legs",
-                         "grasp terminal states, and the successes of the backward grasp leg's fit, from evaluation.scripted_grasp_controller on the "
+                         "grasp terminal states, and the successes of the backward grasp leg's fit, from scripted_grasp.scripted_grasp_controller on the "
                          "trained task when the %d-epoch policy produced (almost) none: %s" % (stage_epochs["grasp"], "; ".join(
                              "%s = %s" % (k, h[k]) for h in hand for k in ("harvested_by", "outcomes_by") if k in h))],
            "runs": runs, "handoffs": hand, "checkpoints": paths, "tvalue_fitted": tv is not None}

@@ -7,20 +7,13 @@ args -> cfg (utils/config.py semantics) -> task + VecTask adapter (utils/parse_t
 rl_games Runner is replaced by seqdex_amd.a2c_agent, same YAML schema)."""
 import os
 
-import yaml
-
 
 def build(args, task_kwargs=None, minibatch_size=0, config_overrides=None):
     """args (config.get_args) -> (task, env, agent, logdir, rank): everything main() does before agent.train() / agent.play().
     config_overrides: keys written into the YAML's params.config before the agent is built (e.g. mixed_precision: True, rl_games' own key)"""
     import torch
-    from .a2c_agent import A2CAgent
     from .config import load_cfg, set_seed
-    from .tasks.block_assembly_grasp_sim import BlockAssemblyGraspSim
-    from .tasks.block_assembly_orient import BlockAssemblyOrient
-    from .tasks.block_assembly_insert_sim import BlockAssemblyInsertSim
-    from .tasks.block_assembly_search import BlockAssemblySearch
-    from .vec_task_rlgames import RLgamesVecTaskPython
+    from .stage import task_class, wrap_and_build_agent
     args.algo = "lego"                                                                    # TR:36
     args.task_type = "RLgames"                                                            # TR:56
     print("Loading config: ", args.cfg_train)
@@ -35,26 +28,13 @@ def build(args, task_kwargs=None, minibatch_size=0, config_overrides=None):
         dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))       # RCCL over xGMI
     cfg["env"]["test"] = args.play                                                        # TR:68
     set_seed(seed + rank, args.torch_deterministic)                                       # TR:70 (+ rank, App. C)
-    task_cls = {"BlockAssemblyGraspSim": BlockAssemblyGraspSim, "BlockAssemblyOrient": BlockAssemblyOrient,
-                "BlockAssemblyInsertSim": BlockAssemblyInsertSim, "BlockAssemblySearch": BlockAssemblySearch}[args.task]   # eval(args.task), PT:162
-    task = task_cls(cfg, None, None, "cuda", local_rank, True, seed=seed + rank, **(task_kwargs or {}))   # PT:162-170
-    env = RLgamesVecTaskPython(task, args.rl_device)                                      # PT:178
-    rl = cfg_train                                                                        # TR:78-85
-    if minibatch_size:     # programmatic override (the reference parses --minibatch_size but never applies it, CF:43)
-        rl["params"]["config"]["minibatch_size"] = minibatch_size
-        rl["params"]["config"]["central_value_config"]["minibatch_size"] = minibatch_size
-    rl["params"]["config"].update(config_overrides or {})
-    rl["params"]["config"]["name"] = args.task
-    rl["params"]["config"]["num_actors"] = env.num_environments
-    rl["params"]["seed"] = seed
-    rl["params"]["config"]["seed"] = seed
-    rl["params"]["config"]["env_config"]["seed"] = seed
-    rl["params"]["config"]["vec_env"] = env
-    rl["params"]["config"]["env_info"] = env.get_env_info()
-    rl["params"]["config"]["multi_gpu"] = world > 1
-    agent = A2CAgent("run", rl["params"])                                                 # TR:88-94 (Runner.run -> agent.train)
-    if rl["params"].get("load_path"):
-        agent.restore(rl["params"]["load_path"])
+    task = task_class(args.task)(cfg, None, None, "cuda", local_rank, True, seed=seed + rank, **(task_kwargs or {}))   # PT:162-170
+    cfg_train["params"]["seed"] = seed                                                    # TR:78-85 (the agent adds the rank itself)
+    cfg_train["params"]["config"]["env_config"]["seed"] = seed
+    env, agent = wrap_and_build_agent(task, cfg_train, seed, args.rl_device, minibatch_size,
+                                      {**(config_overrides or {}), "name": args.task, "multi_gpu": world > 1})
+    if cfg_train["params"].get("load_path"):       # (resumes the checkpoint's epoch counter, as rl_games does)
+        agent.restore(cfg_train["params"]["load_path"])
     return task, env, agent, logdir, rank
 
 

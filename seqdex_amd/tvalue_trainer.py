@@ -35,6 +35,14 @@ def state_dict_from_flat(flat):
     return sd
 
 
+def open_gate_weights():
+    """flat GraspInsertTValue weights whose output is (0, 10) for every orientation: sigmoid(10) = 1 passes every gate, so a harvest
+    counts the PHYSICAL criterion alone (what a forward leg of the bi-optimisation loop does before any transition value exists)"""
+    flat = np.zeros(_abi.TV_PARAMS, np.float32)
+    flat[-1] = 10.0                                                    # the last entry is output_layer.bias[1] (success)
+    return flat
+
+
 class TValue_Trainer:
     def __init__(self, data, device="cuda:0", seed=0, valid_holdout=100):
         if not torch.cuda.is_available():

@@ -12,12 +12,12 @@ N = 1024
 
 
 def _closed_chain(seed):
-    from seqdex_amd.scripts.evaluation import block_assembly_chain_closed
+    from seqdex_amd.scripts.chain_training import block_assembly_chain_closed
     return block_assembly_chain_closed(N, 1500, 1500, 4000, 600, seed=seed, orient_gates=(0.99, 0.9, 0.8, 0.5), grasp_gates=(0.8, 0.65, 0.5))
 
 
 def test_chain_hand_offs_at_1024_envs():
-    """The chain with EVERY stage on a learned policy (round 6, VERDICT r5 items 5b / 5c / 6; evaluation.py::block_assembly_chain_closed):
+    """The chain with EVERY stage on a learned policy (round 6, VERDICT r5 items 5b / 5c / 6; chain_training.py::block_assembly_chain_closed):
     stage 0 trains the insert policy (1 500 epochs) and fits the transition value to its outcomes; a GraspSim policy is trained (1 500 epochs of
     2 048-row minibatches) under that value's gate; it is played from settled piles until every brick-type group has >= 100 harvested grasp
     states (round 5 handed on 32 in all), the insert policy is fine-tuned on them (4 000 epochs) and the value REFITTED to its outcomes; an Orient

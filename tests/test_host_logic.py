@@ -101,8 +101,10 @@ def test_insert_sim_scene_desc_places_three_plate_variants(scene):
 
 
 def test_launcher_maps_the_four_tasks():
-    from seqdex_amd import config
+    from seqdex_amd import config, stage
     assert set(config.TASK_CFG) == {"BlockAssemblyGraspSim", "BlockAssemblyOrient", "BlockAssemblyInsertSim", "BlockAssemblySearch"}
+    assert set(stage.TASK_MODULES) == set(config.TASK_CFG) == set(config.TRAIN_CFG)        # the one name -> class table covers the launcher's tasks
+    assert all(stage.task_class(t).__name__ == t for t in config.TASK_CFG)
     for t, rel in config.TASK_CFG.items():
         cfg = yaml.safe_load(open(os.path.join(os.path.dirname(config.__file__), rel)))
         assert cfg["env"]["episodeLength"] == {"BlockAssemblyGraspSim": 150, "BlockAssemblyOrient": 75, "BlockAssemblyInsertSim": 125,

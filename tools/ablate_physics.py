@@ -10,17 +10,14 @@ import os
 import sys
 
 import torch
-import yaml
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from seqdex_amd.tasks.block_assembly_grasp_sim import BlockAssemblyGraspSim  # noqa: E402
+from seqdex_amd.stage import make_task  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 warm = int(sys.argv[2]) if len(sys.argv) > 2 else 24
-cfg = yaml.safe_load(open(os.path.join(ROOT, "seqdex_amd/cfg/allegro_hand_block_assembly_grasp_sim.yaml")))
-cfg["env"]["numEnvs"] = n
-task = BlockAssemblyGraspSim(cfg, device_type="cuda", device_id=0, headless=True, seed=22, piles_per_type=8)
+task = make_task("BlockAssemblyGraspSim", n, 22, piles_per_type=8)
 s = task.sim
 g = torch.Generator().manual_seed(0)
 for _ in range(warm):

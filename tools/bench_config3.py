@@ -21,7 +21,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from seqdex_amd.scripts.evaluation import CHAIN_GRASP_GATES, CHAIN_ORIENT_GATES, block_assembly_chain, prepare_tvalue_and_insert_policy, scripted_grasp_controller  # noqa: E402
+from seqdex_amd.scripts.chain_training import prepare_tvalue_and_insert_policy  # noqa: E402
+from seqdex_amd.scripts.evaluation import CHAIN_GRASP_GATES, CHAIN_ORIENT_GATES, block_assembly_chain  # noqa: E402
+from seqdex_amd.scripts.scripted_grasp import scripted_grasp_controller  # noqa: E402
 
 
 if __name__ == "__main__":

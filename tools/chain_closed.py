@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """BASELINE.json configs[2] with every stage on a learned policy, several seeds:
-seqdex_amd/scripts/evaluation.py::block_assembly_chain_closed per seed, then mean / min / max of the numbers that matter.
+seqdex_amd/scripts/chain_training.py::block_assembly_chain_closed per seed, then mean / min / max of the numbers that matter.
 usage: python tools/chain_closed.py [N] --seeds 22,23,24 [--insert-epochs 1500] [--grasp-epochs 1500] [--refit-epochs 4000] [--orient-epochs 600]
        [--gates 0.99,0.9,0.8] [--min-grasp-states 100] --out file.json"""
 import argparse
@@ -13,7 +13,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from seqdex_amd.scripts.evaluation import block_assembly_chain_closed  # noqa: E402
+from seqdex_amd.scripts.chain_training import block_assembly_chain_closed  # noqa: E402
 
 
 def main():

@@ -1,4 +1,4 @@
-"""BASELINE.json configs[2] on LEARNED policies (seqdex_amd/scripts/evaluation.py::block_assembly_chain_learned): insert
+"""BASELINE.json configs[2] on LEARNED policies (seqdex_amd/scripts/chain_training.py::block_assembly_chain_learned): insert
 policy + transition value from stage 0, a GraspSim policy of this engine trained under that transition value's gate, then Orient ->
 GraspSim -> InsertSim with no scripted stage and no synthetic grasp states.  Prints one JSON line.
 usage: python tools/chain_learned.py [N] [grasp_epochs] [insert_epochs] [--refit insert_refit_epochs] [--out file]"""
@@ -9,7 +9,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from seqdex_amd.scripts.evaluation import block_assembly_chain_learned  # noqa: E402
+from seqdex_amd.scripts.chain_training import block_assembly_chain_learned  # noqa: E402
 
 if __name__ == "__main__":
     pos = [a for i, a in enumerate(sys.argv[1:], 1) if a.isdigit() and sys.argv[i - 1] not in ("--refit", "--out")]

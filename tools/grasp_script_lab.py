@@ -1,4 +1,4 @@
-"""how often does the scripted stand-in grasp (seqdex_amd/scripts/evaluation.py::scripted_grasp_controller) carry the target brick to the
+"""how often does the scripted stand-in grasp (seqdex_amd/scripts/scripted_grasp.py::scripted_grasp_controller) carry the target brick to the
 insertion side?  N envs, one episode + reset, harvest gate's T-value opened.  python tools/grasp_script_lab.py [N]"""
 import json
 import os
@@ -9,8 +9,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from seqdex_amd.scripts.evaluation import main_rlgames, scripted_grasp_controller  # noqa: E402
-from tools.grasp_long_run import open_gate_tvalue  # noqa: E402,F401
+from seqdex_amd.scripts.evaluation import main_rlgames  # noqa: E402
+from seqdex_amd.scripts.scripted_grasp import scripted_grasp_controller  # noqa: E402
+from seqdex_amd.tvalue_trainer import open_gate_weights  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 trace = []
@@ -37,7 +38,7 @@ def ctrl(task, step):
     return scripted_grasp_controller(task, step)
 
 
-task, st = main_rlgames("BlockAssemblyGraspSim", n, tvalue_state=open_gate_tvalue(), controller=ctrl, steps=160, task_kwargs={"piles_per_type": 16})
+task, st = main_rlgames("BlockAssemblyGraspSim", n, tvalue_state=open_gate_weights(), controller=ctrl, steps=160, task_kwargs={"piles_per_type": 16})
 st["harvested_per_type"] = task.sim.HARVEST_COUNT.cpu().tolist()
 st["trace(step, mean brick pos, mean hand base, max brick z, bricks above 0.8, bricks at y<0, mean finger dist)"] = trace
 print(json.dumps(st))

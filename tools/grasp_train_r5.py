@@ -12,15 +12,11 @@ import time
 
 import numpy as np
 import torch
-import yaml
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from seqdex_amd.a2c_agent import A2CAgent  # noqa: E402
-from seqdex_amd.config import TASK_CFG, TRAIN_CFG  # noqa: E402
-from seqdex_amd.tasks.block_assembly_grasp_sim import BlockAssemblyGraspSim  # noqa: E402
-from seqdex_amd.vec_task_rlgames import RLgamesVecTaskPython  # noqa: E402
-from tools.grasp_long_run import open_gate_tvalue  # noqa: E402
+from seqdex_amd.stage import make_stage  # noqa: E402
+from seqdex_amd.tvalue_trainer import open_gate_weights  # noqa: E402
 
 
 def main():
@@ -29,23 +25,12 @@ def main():
     out = sys.argv[6] if len(sys.argv) > 6 else os.path.join(ROOT, "gpurun_out", "grasp_train_r5.txt")
     max_s = float(sys.argv[7]) if len(sys.argv) > 7 else 1e9
     os.makedirs(os.path.dirname(out), exist_ok=True)
-    cfg = yaml.safe_load(open(os.path.join(ROOT, "seqdex_amd", TASK_CFG["BlockAssemblyGraspSim"])))
-    cfg["env"]["numEnvs"] = n
-    tr = yaml.safe_load(open(os.path.join(ROOT, "seqdex_amd", TRAIN_CFG["BlockAssemblyGraspSim"])))
-    pc = tr["params"]["config"]
-    pc["minibatch_size"] = mb
-    pc["central_value_config"]["minibatch_size"] = mb
-    if lr != "adaptive":
-        pc["lr_schedule"] = "constant"
-        pc["learning_rate"] = float(lr)
-    task = BlockAssemblyGraspSim(cfg, device_type="cuda", device_id=0, headless=True, seed=22, piles_per_type=16)
-    task.sim.set_tvalue_weights(open_gate_tvalue())
-    env = RLgamesVecTaskPython(task, "cuda:0")
-    pc.update(num_actors=n, vec_env=env, env_info=env.get_env_info(), seed=22)
-    agent = A2CAgent("run", tr["params"])
+    task, env, agent = make_stage("BlockAssemblyGraspSim", n, 22, task_kwargs={"piles_per_type": 16}, minibatch_size=mb,
+                                  config_overrides={} if lr == "adaptive" else {"lr_schedule": "constant", "learning_rate": float(lr)})
+    task.sim.set_tvalue_weights(open_gate_weights())
     log = open(out, "w")
     head = "# BlockAssemblyGraspSim, %d envs, horizon 8, minibatch %d (%s update path), %d mini-epochs, lr %s (kl threshold %s), %d epochs" % (
-        n, mb, "persistent rank-4" if mb <= 8 else "large-minibatch MFMA", agent.mini_epochs_num, lr, pc.get("kl_threshold"), epochs)
+        n, mb, "persistent rank-4" if mb <= 8 else "large-minibatch MFMA", agent.mini_epochs_num, lr, agent.config.get("kl_threshold"), epochs)
     print(head, flush=True); log.write(head + "\n")
     t0 = time.time()
     rew_max = -1e9

@@ -9,40 +9,25 @@ import time
 
 import numpy as np
 import torch
-import yaml
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from seqdex_amd.a2c_agent import A2CAgent  # noqa: E402
-from seqdex_amd.config import TASK_CFG, TRAIN_CFG, set_seed  # noqa: E402
+from seqdex_amd.stage import make_stage  # noqa: E402
 from seqdex_amd.tasks.block_assembly_insert_sim import BlockAssemblyInsertSim  # noqa: E402
-from seqdex_amd.vec_task_rlgames import RLgamesVecTaskPython  # noqa: E402
 
 n, epochs, every = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3])
 states = None
 if "--grasp" in sys.argv:
-    from seqdex_amd.scripts.evaluation import train_grasp_policy
+    from seqdex_amd.scripts.chain_training import train_grasp_policy
     ge = int(sys.argv[sys.argv.index("--grasp") + 1])
     _, gtask, gst = train_grasp_policy(n, ge, seed=22)
     states = gtask.grasp_terminal_states()
     gtask.sim.close()
     print("grasp policy:", json.dumps(gst), flush=True)
-set_seed(22)
-cfg = yaml.safe_load(open(os.path.join(ROOT, "seqdex_amd", TASK_CFG["BlockAssemblyInsertSim"])))
-cfg["env"]["numEnvs"] = n
-tr = yaml.safe_load(open(os.path.join(ROOT, "seqdex_amd", TRAIN_CFG["BlockAssemblyInsertSim"])))
-if "--no-hollow" in sys.argv:
-    class T(BlockAssemblyInsertSim):
-        def _scene_overrides(self, scene):
-            d = super()._scene_overrides(scene)
-            d["seg_hollow"] = 0
-            return d
-    task = T(cfg, device_type="cuda", device_id=0, headless=True, seed=22, grasp_states=states)
-else:
-    task = BlockAssemblyInsertSim(cfg, device_type="cuda", device_id=0, headless=True, seed=22, grasp_states=states)
-env = RLgamesVecTaskPython(task, "cuda:0")
-tr["params"]["config"].update(num_actors=n, vec_env=env, env_info=env.get_env_info(), seed=22)
-agent = A2CAgent("run", tr["params"])
+if "--no-hollow" in sys.argv:       # patched on the class itself: make_stage builds the task by name
+    hollow = BlockAssemblyInsertSim._scene_overrides
+    BlockAssemblyInsertSim._scene_overrides = lambda self, scene: dict(hollow(self, scene), seg_hollow=0)
+task, env, agent = make_stage("BlockAssemblyInsertSim", n, 22, task_kwargs={"grasp_states": states})
 t0 = time.time()
 for ep in range(epochs):
     agent.train_epoch()

@@ -1,8 +1,8 @@
 """Can BlockAssemblyInsertSim learn to insert from LEARNED grasp states once a transition value has filtered them (the second forward pass
 of the bi-optimisation loop, scripts/bi_optimization.py:115-121)?
 
-  0  insert policy + transition value from synthetic grasp states (evaluation.prepare_tvalue_and_insert_policy)
-  1  grasp policy trained under that value's gate (evaluation.train_grasp_policy)
+  0  insert policy + transition value from synthetic grasp states (chain_training.prepare_tvalue_and_insert_policy)
+  1  grasp policy trained under that value's gate (chain_training.train_grasp_policy)
   2  the grasp policy played until `want` states per brick-type group passed the gate `gate` (or `max_steps` env steps per env)
   3  where those states start InsertSim from: distance / rotation error to the site right after the reset
   4  the insert policy trained on those states (from scratch, and fine-tuned from stage 0's checkpoint), `epochs` epochs each; outcome counts
@@ -19,15 +19,12 @@ import time
 
 import numpy as np
 import torch
-import yaml
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from seqdex_amd.a2c_agent import A2CAgent  # noqa: E402
-from seqdex_amd.config import TASK_CFG, TRAIN_CFG, set_seed  # noqa: E402
-from seqdex_amd.scripts.evaluation import main_rlgames, prepare_tvalue_and_insert_policy, train_grasp_policy  # noqa: E402
-from seqdex_amd.tasks.block_assembly_insert_sim import BlockAssemblyInsertSim  # noqa: E402
-from seqdex_amd.vec_task_rlgames import RLgamesVecTaskPython  # noqa: E402
+from seqdex_amd.scripts.chain_training import prepare_tvalue_and_insert_policy, train_grasp_policy  # noqa: E402
+from seqdex_amd.scripts.evaluation import main_rlgames  # noqa: E402
+from seqdex_amd.stage import make_stage  # noqa: E402
 
 
 def opt(name, default, cast=float):
@@ -43,19 +40,9 @@ def aux_line(task):
 
 
 def train_insert(n, states, epochs, every, restore=""):
-    set_seed(22)
-    cfg = yaml.safe_load(open(os.path.join(ROOT, "seqdex_amd", TASK_CFG["BlockAssemblyInsertSim"])))
-    cfg["env"]["numEnvs"] = n
-    tr = yaml.safe_load(open(os.path.join(ROOT, "seqdex_amd", TRAIN_CFG["BlockAssemblyInsertSim"])))
-    task = BlockAssemblyInsertSim(cfg, device_type="cuda", device_id=0, headless=True, seed=22, grasp_states=states, synthetic_fallback=True)
+    task, env, agent = make_stage("BlockAssemblyInsertSim", n, 22, task_kwargs={"grasp_states": states, "synthetic_fallback": True}, restore=restore)
     real = torch.tensor([(e % 8) not in task.synthetic_groups for e in range(n)], device="cuda:0")
     print("  grasp states: %s" % task.grasp_states_source, flush=True)
-    env = RLgamesVecTaskPython(task, "cuda:0")
-    tr["params"]["config"].update(num_actors=n, vec_env=env, env_info=env.get_env_info(), seed=22)
-    agent = A2CAgent("run", tr["params"])
-    if restore:
-        agent.restore(restore)
-        agent.epoch_num = 0
     # ---- stage 3: where the states start the task from
     env.reset()
     task.sim.compute_observations()

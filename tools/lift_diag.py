@@ -1,4 +1,4 @@
-"""Does the hand lift a brick?  N GraspSim envs under the scripted reach - descend - pinch controller (evaluation.py::scripted_grasp_controller;
+"""Does the hand lift a brick?  N GraspSim envs under the scripted reach - descend - pinch controller (scripted_grasp.py::scripted_grasp_controller;
 after step 75 the task lifts the hand itself, GS:1596-1609), one episode; prints what the target brick, the fingertips and the fingertip
 contact forces do over the episode and how many envs end with the brick lifted >= 5 cm and finger_dist < 0.5.
 python tools/lift_diag.py [N] [--dump K]   (--dump: per-step trace of the first K envs of type group 0)"""
@@ -8,23 +8,20 @@ import sys
 
 import numpy as np
 import torch
-import yaml
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from seqdex_amd.scripts.evaluation import scripted_grasp_controller  # noqa: E402
-from seqdex_amd.tasks.block_assembly_grasp_sim import BlockAssemblyGraspSim  # noqa: E402
+from seqdex_amd.scripts.scripted_grasp import scripted_grasp_controller  # noqa: E402
+from seqdex_amd.stage import make_task  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 and not sys.argv[1].startswith("-") else 1024
 dump = int(sys.argv[sys.argv.index("--dump") + 1]) if "--dump" in sys.argv else 0
 variants = sys.argv[sys.argv.index("--variants") + 1].split(";") if "--variants" in sys.argv else [os.environ.get("SDX_SG_PARAMS", "")]
-cfg = yaml.safe_load(open(os.path.join(ROOT, "seqdex_amd/cfg/allegro_hand_block_assembly_grasp_sim.yaml")))
-cfg["env"]["numEnvs"] = n
 
 
 def run(variant, dump):
     os.environ["SDX_SG_PARAMS"] = variant
-    task = BlockAssemblyGraspSim(cfg, device_type="cuda", device_id=0, headless=True, seed=22, piles_per_type=16)
+    task = make_task("BlockAssemblyGraspSim", n, 22, piles_per_type=16)
     s = task.sim
     dev = task.device
     seg = torch.as_tensor([s.scene.seg_index(i) for i in range(n)], device=dev)

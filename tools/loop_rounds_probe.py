@@ -12,8 +12,8 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from seqdex_amd.scripts.evaluation import (CHAIN_LEARNED_ORIENT_GATES, block_assembly_chain, main_rlgames, prepare_tvalue_and_insert_policy,  # noqa: E402
-                                           train_grasp_policy)
+from seqdex_amd.scripts.chain_training import CHAIN_LEARNED_ORIENT_GATES, prepare_tvalue_and_insert_policy, train_grasp_policy  # noqa: E402
+from seqdex_amd.scripts.evaluation import block_assembly_chain, main_rlgames  # noqa: E402
 
 n, rounds = int(sys.argv[1]), int(sys.argv[2])
 ie = int(sys.argv[3]) if len(sys.argv) > 3 else 1500

@@ -1,26 +1,14 @@
-import sys, time, yaml, torch
+"""A few training epochs of a task with per-epoch timings (does it run, how fast).
+usage: python tools/quick_train.py [num_envs] [epochs] [Task] [minibatch_size]"""
+import sys, time
 sys.path.insert(0,'.')
-from seqdex_amd.tasks.block_assembly_grasp_sim import BlockAssemblyGraspSim
-from seqdex_amd.vec_task_rlgames import RLgamesVecTaskPython
-from seqdex_amd.a2c_agent import A2CAgent
+from seqdex_amd.stage import make_stage
 n=int(sys.argv[1]) if len(sys.argv)>1 else 1024
 task_name=sys.argv[3] if len(sys.argv)>3 else 'BlockAssemblyGraspSim'
-if task_name=='BlockAssemblyInsertSim':
-    from seqdex_amd.tasks.block_assembly_insert_sim import BlockAssemblyInsertSim as BlockAssemblyGraspSim
-elif task_name=='BlockAssemblyOrient':
-    from seqdex_amd.tasks.block_assembly_orient import BlockAssemblyOrient as BlockAssemblyGraspSim
-from seqdex_amd.config import TASK_CFG, TRAIN_CFG
-cfg=yaml.safe_load(open('seqdex_amd/'+TASK_CFG[task_name])); cfg['env']['numEnvs']=n
-tr=yaml.safe_load(open('seqdex_amd/'+TRAIN_CFG[task_name]))
-if len(sys.argv)>4:
-    tr['params']['config']['minibatch_size']=int(sys.argv[4]); tr['params']['config']['central_value_config']['minibatch_size']=int(sys.argv[4])
-print('minibatch_size', tr['params']['config']['minibatch_size'])
 t0=time.time()
-task=BlockAssemblyGraspSim(cfg, device_type='cuda', device_id=0, headless=True, piles_per_type=4)
-print('task create s', time.time()-t0)
-env=RLgamesVecTaskPython(task,'cuda:0')
-tr['params']['config'].update(num_actors=n, vec_env=env, env_info=env.get_env_info(), seed=22)
-agent=A2CAgent('run', tr['params'])
+task, env, agent = make_stage(task_name, n, 22, task_kwargs={'piles_per_type': 4}, minibatch_size=int(sys.argv[4]) if len(sys.argv)>4 else 0)
+print('minibatch_size', agent.minibatch_size)
+print('stage create s', time.time()-t0)
 for ep in range(int(sys.argv[2]) if len(sys.argv)>2 else 4):
     r=agent.train_epoch()
     print('epoch',ep,'step %.4f play %.4f update %.4f total %.4f'%r[:4], 'a %.4f c %.4f kl %.5f lr %.2e'%(r[4][0],r[5][0],r[8][0],r[9]),

@@ -5,15 +5,15 @@ import os
 import sys
 
 import torch
-import yaml
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from seqdex_amd import _abi  # noqa: E402
+from seqdex_amd.config import train_cfg  # noqa: E402
 from seqdex_amd.ppo import SdxPPO  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-tr = yaml.safe_load(open(os.path.join(ROOT, "seqdex_amd/cfg/lego/ppo_continuous_grasp.yaml")))
+tr = train_cfg("BlockAssemblyGraspSim")
 ppo = SdxPPO(n, params=tr["params"], obs_dim=396, state_dim=564)
 lib = _abi.load_library()
 lib.sdxpk_linear_force_shape.argtypes = [C.c_int]

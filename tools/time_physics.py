@@ -7,22 +7,21 @@ import os
 import sys
 
 import torch
-import yaml
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from seqdex_amd.tasks.block_assembly_grasp_sim import BlockAssemblyGraspSim  # noqa: E402
+from seqdex_amd.config import task_cfg  # noqa: E402
+from seqdex_amd.stage import make_task  # noqa: E402
 
 randomize = "--randomize" in sys.argv
 if randomize:
     sys.argv.remove("--randomize")
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 warm = int(sys.argv[2]) if len(sys.argv) > 2 else 24
-cfg = yaml.safe_load(open(os.path.join(ROOT, "seqdex_amd/cfg/allegro_hand_block_assembly_grasp_sim.yaml")))
-cfg["env"]["numEnvs"] = n
+cfg = task_cfg("BlockAssemblyGraspSim")
 if os.environ.get("SDX_TP_ITERS"):          # ablation: solver iterations per substep (the YAML ships 16)
     cfg.setdefault("sim", {}).setdefault("physx", {})["num_position_iterations"] = int(os.environ["SDX_TP_ITERS"])
-task = BlockAssemblyGraspSim(cfg, device_type="cuda", device_id=0, headless=True, seed=22, piles_per_type=8)
+task = make_task("BlockAssemblyGraspSim", n, 22, cfg=cfg, piles_per_type=8)
 s = task.sim
 if randomize:
     s.DR_FRAME[0] = 50000

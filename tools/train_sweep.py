@@ -15,35 +15,21 @@ import time
 
 import numpy as np
 import torch
-import yaml
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from seqdex_amd.a2c_agent import A2CAgent  # noqa: E402
-from seqdex_amd.config import TASK_CFG, TRAIN_CFG  # noqa: E402
-from seqdex_amd.tasks.block_assembly_grasp_sim import BlockAssemblyGraspSim  # noqa: E402
-from seqdex_amd.vec_task_rlgames import RLgamesVecTaskPython  # noqa: E402
-from tools.grasp_long_run import open_gate_tvalue  # noqa: E402
+from seqdex_amd.stage import make_stage  # noqa: E402
+from seqdex_amd.tvalue_trainer import open_gate_weights  # noqa: E402
 
 
 def one_run(n, mb, lr, seed, epochs, every, max_s):
-    cfg = yaml.safe_load(open(os.path.join(ROOT, "seqdex_amd", TASK_CFG["BlockAssemblyGraspSim"])))
-    cfg["env"]["numEnvs"] = n
-    tr = yaml.safe_load(open(os.path.join(ROOT, "seqdex_amd", TRAIN_CFG["BlockAssemblyGraspSim"])))
-    pc = tr["params"]["config"]
-    pc["minibatch_size"] = mb
-    pc["central_value_config"]["minibatch_size"] = mb
+    over = {}
     if lr.startswith("adaptive@"):          # the shipped adaptive rule from another initial learning rate
-        pc["learning_rate"] = float(lr.split("@")[1])
+        over = {"learning_rate": float(lr.split("@")[1])}
     elif lr != "adaptive":
-        pc["lr_schedule"] = "constant"
-        pc["learning_rate"] = float(lr)
-    torch.manual_seed(seed)
-    task = BlockAssemblyGraspSim(cfg, device_type="cuda", device_id=0, headless=True, seed=seed, piles_per_type=16)
-    task.sim.set_tvalue_weights(open_gate_tvalue())
-    env = RLgamesVecTaskPython(task, "cuda:0")
-    pc.update(num_actors=n, vec_env=env, env_info=env.get_env_info(), seed=seed)
-    agent = A2CAgent("sweep", tr["params"])
+        over = {"lr_schedule": "constant", "learning_rate": float(lr)}
+    task, env, agent = make_stage("BlockAssemblyGraspSim", n, seed, task_kwargs={"piles_per_type": 16}, minibatch_size=mb, config_overrides=over)
+    task.sim.set_tvalue_weights(open_gate_weights())
     t0 = time.time()
     curve, lrs, kls = [], [], []
     rew_max = -1e9

@@ -9,27 +9,17 @@ import sys
 import tempfile
 
 import torch
-import yaml
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from seqdex_amd.a2c_agent import A2CAgent  # noqa: E402
-from seqdex_amd.config import TASK_CFG, TRAIN_CFG, set_seed  # noqa: E402
-from seqdex_amd.scripts.evaluation import main_rlgames, train_grasp_policy  # noqa: E402
-from seqdex_amd.tasks.block_assembly_insert_sim import BlockAssemblyInsertSim  # noqa: E402
+from seqdex_amd.scripts.chain_training import train_grasp_policy  # noqa: E402
+from seqdex_amd.scripts.evaluation import main_rlgames  # noqa: E402
+from seqdex_amd.stage import make_stage  # noqa: E402
 from seqdex_amd.tvalue_trainer import TValue_Trainer, flat_from_state_dict  # noqa: E402
-from seqdex_amd.vec_task_rlgames import RLgamesVecTaskPython  # noqa: E402
 
 n = int(sys.argv[1])
 grasp_steps = int(sys.argv[2]) if len(sys.argv) > 2 else 4000
-set_seed(22)
-cfg = yaml.safe_load(open(os.path.join(ROOT, "seqdex_amd", TASK_CFG["BlockAssemblyInsertSim"])))
-cfg["env"]["numEnvs"] = n
-tr = yaml.safe_load(open(os.path.join(ROOT, "seqdex_amd", TRAIN_CFG["BlockAssemblyInsertSim"])))
-task = BlockAssemblyInsertSim(cfg, device_type="cuda", device_id=0, headless=True, seed=22)
-env = RLgamesVecTaskPython(task, "cuda:0")
-tr["params"]["config"].update(num_actors=n, vec_env=env, env_info=env.get_env_info(), seed=22)
-agent = A2CAgent("run", tr["params"])
+task, env, agent = make_stage("BlockAssemblyInsertSim", n, 22)
 for _ in range(1500):
     agent.train_epoch()
 torch.cuda.synchronize()
