@@ -573,52 +573,43 @@ __global__ __launch_bounds__(256) void k_stage(StageBatch sb) {
   }
 }
 
-template <int BF, int EPI>
-static void gemm_nt(const NtArgs* gs, int count, int splits, hipStream_t st) {
-  NtBatch nb;
+static constexpr int NT_LDS[3] = {0, 2 * 192 * 128, 2 * 256 * 128}, TT_LDS[3] = {0, 2 * 32 * 192 * 4, 2 * 32 * 256 * 4};   // dynamic LDS per TILE
+// batch and tile grid of a launch; returns TILE: `tile` when forced (1 = 128 x 64, 2 = 128 x 128: timing / diagnosis), else 128 x 128 (least
+// LDS / L2 traffic per flop) when that gives every CU's two workgroup slots something to do and does not pad the columns by much more than
+// 128 x 64 tiles would (a 396-wide weight gradient: 512 vs 448 columns of work), else 128 x 64
+static int nt_batch(const NtArgs* gs, int count, int splits, int tile, NtBatch& nb, int& nx, int& ny) {
   int Mx = 0, Nx = 0;
   for (int q = 0; q < 3; ++q) {
     nb.a[q] = gs[q < count ? q : 0];
     if (q < count) { Mx = gs[q].M > Mx ? gs[q].M : Mx; Nx = gs[q].N > Nx ? gs[q].N : Nx; }
   }
   nb.splits = splits;
-  // 128 x 128 tiles (least LDS / L2 traffic per flop) when they give every CU's two workgroup slots something to do and do not pad the
-  // columns by much more than 128 x 64 tiles would (a 396-wide weight gradient: 512 vs 448 columns of work), else 128 x 64
-  const int ny = (Mx + 127) / 128, nx2 = (Nx + 127) / 128, nx1 = (Nx + 63) / 64;
-  const long b2 = (long)nx2 * ny * splits * count;
-  static const int forced = getenv("SDXP_NT_TILE") ? atoi(getenv("SDXP_NT_TILE")) : 0;   // 1: 128 x 64, 2: 128 x 128 (timing / diagnosis)
-  const bool wide = forced ? forced == 2 : (b2 >= 512 && nx2 * 128 <= nx1 * 64 * 1.10);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_nt<BF, EPI, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 256 * 128);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_nt<BF, EPI, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 192 * 128);
-    attr = true;
-  }
-  const int nz = splits * count;
-  if (wide) hipLaunchKernelGGL((k_gemm_nt<BF, EPI, 2>), dim3(nx2 * ny * nz), dim3(256), 2 * 256 * 128, st, nb, nx2, ny);
-  else hipLaunchKernelGGL((k_gemm_nt<BF, EPI, 1>), dim3(nx1 * ny * nz), dim3(256), 2 * 192 * 128, st, nb, nx1, ny);
+  ny = (Mx + 127) / 128;
+  const int nx2 = (Nx + 127) / 128, nx1 = (Nx + 63) / 64;
+  const bool wide = tile ? tile == 2 : ((long)nx2 * ny * splits * count >= 512 && nx2 * 128 <= nx1 * 64 * 1.10);
+  nx = wide ? nx2 : nx1;
+  return wide ? 2 : 1;
 }
-
-// launcher of k_gemm_tt: tile choice as gemm_nt; `zeros`: 16-byte aligned device memory holding at least 16 zero bytes
-static void gemm_tt(const NtArgs* gs, int count, int splits, const float* zeros, hipStream_t st) {
+// both tile shapes of a product may use their LDS on the current device (before the first launch there; harmless when repeated)
+template <class K>
+static bool nt_allow_lds(K wide, K narrow, const int* lds) {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(wide), hipFuncAttributeMaxDynamicSharedMemorySize, lds[2]) == hipSuccess &&
+         hipFuncSetAttribute(reinterpret_cast<const void*>(narrow), hipFuncAttributeMaxDynamicSharedMemorySize, lds[1]) == hipSuccess;
+}
+template <int BF, int EPI>
+static bool gemm_nt_prepare() { return nt_allow_lds(k_gemm_nt<BF, EPI, 2>, k_gemm_nt<BF, EPI, 1>, NT_LDS); }
+static bool gemm_tt_prepare() { return nt_allow_lds(k_gemm_tt<2>, k_gemm_tt<1>, TT_LDS); }
+template <int BF, int EPI>
+static void gemm_nt(const NtArgs* gs, int count, int splits, hipStream_t st, int tile = 0) {
   NtBatch nb;
-  int Mx = 0, Nx = 0;
-  for (int q = 0; q < 3; ++q) {
-    nb.a[q] = gs[q < count ? q : 0];
-    if (q < count) { Mx = gs[q].M > Mx ? gs[q].M : Mx; Nx = gs[q].N > Nx ? gs[q].N : Nx; }
-  }
-  nb.splits = splits;
-  const int ny = (Mx + 127) / 128, nx2 = (Nx + 127) / 128, nx1 = (Nx + 63) / 64;
-  const long b2 = (long)nx2 * ny * splits * count;
-  static const int forced = getenv("SDXP_NT_TILE") ? atoi(getenv("SDXP_NT_TILE")) : 0;
-  const bool wide = forced ? forced == 2 : (b2 >= 512 && nx2 * 128 <= nx1 * 64 * 1.10);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_tt<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 32 * 256 * 4);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_tt<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 32 * 192 * 4);
-    attr = true;
-  }
-  const int nz = splits * count;
-  if (wide) hipLaunchKernelGGL((k_gemm_tt<2>), dim3(nx2 * ny * nz), dim3(256), 2 * 32 * 256 * 4, st, nb, nx2, ny, zeros);
-  else hipLaunchKernelGGL((k_gemm_tt<1>), dim3(nx1 * ny * nz), dim3(256), 2 * 32 * 192 * 4, st, nb, nx1, ny, zeros);
+  int nx, ny;
+  const int t = nt_batch(gs, count, splits, tile, nb, nx, ny);
+  hipLaunchKernelGGL((t == 2 ? k_gemm_nt<BF, EPI, 2> : k_gemm_nt<BF, EPI, 1>), dim3(nx * ny * splits * count), dim3(256), NT_LDS[t], st, nb, nx, ny);
+}
+// launcher of k_gemm_tt: tile choice as gemm_nt; `zeros`: 16-byte aligned device memory holding at least 16 zero bytes
+static void gemm_tt(const NtArgs* gs, int count, int splits, const float* zeros, hipStream_t st, int tile = 0) {
+  NtBatch nb;
+  int nx, ny;
+  const int t = nt_batch(gs, count, splits, tile, nb, nx, ny);
+  hipLaunchKernelGGL((t == 2 ? k_gemm_tt<2> : k_gemm_tt<1>), dim3(nx * ny * splits * count), dim3(256), TT_LDS[t], st, nb, nx, ny, zeros);
 }

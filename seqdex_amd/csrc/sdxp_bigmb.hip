@@ -493,10 +493,6 @@ __global__ __launch_bounds__(256) void k_big_heads_reduce(SdxpDev D, int nblocks
 }
 static int heads_nrb(int MB) { int n = MB / (HR * 512); return n < 1 ? 1 : n; }
 static int heads_blocks(int MB) { const int nrb = heads_nrb(MB); return (MB + HR * nrb - 1) / (HR * nrb); }
-static bool heads_fused_ok(const SdxpDev& D) {
-  static const int off = getenv("SDXP_BIGMB_FUSED_HEADS") ? atoi(getenv("SDXP_BIGMB_FUSED_HEADS")) == 0 : 0;   // =0: the 13-launch head section (diagnosis)
-  return !off && D.units[2] == HU && D.act_dim <= 23;
-}
 
 // ------------------------------------------------------------------------------------------------ central-value input statistics
 // partial column sums / sums of squares (fp64) of rows [r0 + z * rchunk, ...) of mb_states
@@ -546,6 +542,16 @@ __global__ __launch_bounds__(256) void k_big_normalise(SdxpDev D, size_t r0, siz
 // ------------------------------------------------------------------------------------------------ host side
 static int big_splits(int MB) { int s = (MB + 511) / 512; return s < 1 ? 1 : (s > 16 ? 16 : s); }
 
+// The 13-launch head section's partials in ws->part (floats): [0, hb * BIGP) loss partials of k_big_head (folded by k_big_fin before anything
+// else lands there); [Sh][A * U2 + A] splits of the policy head's weight gradient - a 23-row product whose only parallelism is the reduction
+// over the minibatch rows, so it is split 256 rows at a time (32 .. 128 splits instead of the trunk's 8 .. 16: 94 us -> about 15 at 32 768
+// rows); from vp0 / vp1 the [VS][U2 + 1] 64-row splits of the two value heads
+struct HeadParts { int hb, Sh, VS; size_t vp0, vp1; };
+static HeadParts head_parts(const SdxpDev& D, int MB) {
+  const int S = big_splits(MB), Sh = MB / 256 < S ? S : (MB / 256 > 128 ? 128 : MB / 256), VS = (MB + 63) / 64;
+  const size_t vp0 = (size_t)Sh * ((size_t)D.act_dim * D.units[2] + D.act_dim);
+  return {(MB + 255) / 256, Sh, VS, vp0, vp0 + (size_t)VS * (D.units[2] + 1)};
+}
 extern "C" size_t sdxpk_big_part_floats(const SdxpDev* D, int MB) {
   const int S = big_splits(MB);
   const size_t in0 = D->obs_dim > D->state_dim ? D->obs_dim : D->state_dim;
@@ -553,21 +559,33 @@ extern "C" size_t sdxpk_big_part_floats(const SdxpDev* D, int MB) {
   const size_t l1 = (size_t)D->units[1] * D->units[0] + D->units[1], l2 = (size_t)D->units[2] * D->units[1] + D->units[2];
   if (l1 > mx) mx = l1;
   if (l2 > mx) mx = l2;
-  int Sh = MB / 256;                 // splits of the policy head's weight gradient (sdxpk_big_step)
-  Sh = Sh < S ? S : (Sh > 128 ? 128 : Sh);
-  const size_t hp = (size_t)((MB + 255) / 256) * BIGP + (size_t)2 * ((MB + 63) / 64) * (D->units[2] + 1) + (size_t)Sh * (32 * (D->units[2] + 1));
+  const HeadParts h = head_parts(*D, MB);
+  const size_t hp = (size_t)h.hb * BIGP + (size_t)2 * h.VS * (D->units[2] + 1) + (size_t)h.Sh * (32 * (D->units[2] + 1));   // (act_dim <= 32)
   const size_t need = (size_t)S * mx;
   const size_t hf = ((size_t)heads_blocks(MB) * HPZ + 2) / 3;   // fused heads: their partials span the three regions
   const size_t m1 = need > hp ? need : hp;
   return m1 > hf ? m1 : hf;          // per network; the workspace holds three such regions
 }
 extern "C" int sdxpk_big_nsplit(int MB) { return big_splits(MB); }
-// The NT path (sdx_gemm_nt.h: staged operands, global_load_lds, two LDS stages) serves the trunk products unless SDXP_BIGMB_NT=0 asks for
-// the round-1 kernel (k_gemm of sdx_gemm.h; kept for A/B timing).  It needs 16-byte aligned minibatch windows in the transposed inputs.
-extern "C" int sdxpk_big_nt_enabled(const SdxpDev* D, int MB) {
-  const char* e = getenv("SDXP_BIGMB_NT");
-  if (e && e[0] == '0') return 0;
-  return MB % 8 == 0 && D->units[0] % 128 == 0 && D->units[1] % 128 == 0 && D->units[2] % 128 == 0 && D->obs_dim % 4 == 0 && D->state_dim % 4 == 0;
+// lowers the large-minibatch options to what shapes and device allow, sets the LDS attributes of the kernels that stay (NT path: 16-byte aligned windows)
+extern "C" void sdxpk_big_prepare(const SdxpDev* D, int MB, SdxpOpts* o) {
+  int dev = 0, lds = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) lds = 0;
+  o->bigmb_fused_heads = o->bigmb_fused_heads && D->units[2] == HU && D->act_dim <= 23;
+  if (o->bigmb_fused_heads && (lds < (int)sizeof(HeadsLds) || hipFuncSetAttribute(reinterpret_cast<const void*>(k_big_heads),
+                                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(HeadsLds)) != hipSuccess)) {
+    fprintf(stderr, "libseqdex_hip: k_big_heads cannot have %zu bytes of LDS on device %d: this handle uses the 13-launch head section\n", sizeof(HeadsLds), dev);
+    o->bigmb_fused_heads = 0;
+  }
+  o->bigmb_nt = o->bigmb_nt && MB % 8 == 0 && D->units[0] % 128 == 0 && D->units[1] % 128 == 0 && D->units[2] % 128 == 0 && D->obs_dim % 4 == 0 &&
+                D->state_dim % 4 == 0;
+  o->bigmb_tt = o->bigmb_tt && o->bigmb_nt && !D->bf16;
+  if (o->bigmb_nt && !(D->bf16 ? gemm_nt_prepare<1, EPI_FWD>() && gemm_nt_prepare<1, EPI_NN>() && gemm_nt_prepare<1, EPI_TN>()
+                               : gemm_nt_prepare<0, EPI_FWD>() && gemm_nt_prepare<0, EPI_NN>() && gemm_nt_prepare<0, EPI_TN>() && (!o->bigmb_tt || gemm_tt_prepare()))) {
+    fprintf(stderr, "libseqdex_hip: k_gemm_nt / k_gemm_tt cannot have their LDS on device %d: this handle's trunk products use k_gemm\n", dev);
+    o->bigmb_nt = o->bigmb_tt = 0;
+  }
+  (void)hipGetLastError();
 }
 template <int BF>
 static void stage_launch(const StageArgs* a, int count, hipStream_t st) {
@@ -605,198 +623,205 @@ extern "C" void sdxpk_big_prenorm(const SdxpDev* D, const SdxpBigWs* ws, hipStre
   }
 }
 
-// forward + losses + backward of minibatch `mb` (mini-epoch `me`) for all three networks; leaves the flat gradients in ac_g / cv_g,
-// the KL word in ac_g[g_tail] and the control block advanced.  The caller follows with the explicit clip + Adam.
-extern "C" void sdxpk_big_step(const SdxpDev* Dp, const SdxpBigWs* ws, int mb, int me, hipStream_t st) {
-  const SdxpDev& D = *Dp;
-  const int MB = ws->MB, A = D.act_dim, U2 = D.units[2];
-  const size_t r0 = (size_t)mb * MB;
-  const int S = ws->nsplit, rchunk = (MB + S - 1) / S;
-  const float* P[3] = {D.ac, D.ac, D.cv};
-  float* G[3] = {D.ac_g, D.ac_g, D.cv_g};
-  const int in0[3] = {D.obs_dim, D.obs_dim, D.state_dim};
-  const float* X0[3] = {D.mb_obs + r0 * D.obs_dim, D.mb_obs + r0 * D.obs_dim, (me == 0 ? D.cvx0 : D.cvx1) + r0 * D.state_dim};
-  auto woff = [&](int net, int l) { return net == 0 ? D.off.a_w[l] : (net == 1 ? D.off.c_w[l] : D.coff.w[l]); };
-  auto boff = [&](int net, int l) { return net == 0 ? D.off.a_b[l] : (net == 1 ? D.off.c_b[l] : D.coff.b[l]); };
-  const size_t region = ws->part_region;                                  // floats of split partials per network
-  const size_t ES = D.bf16 ? 2 : 4;
-  const int xsel[3] = {0, 0, me == 0 ? 1 : 2};                            // which staged dataset input a network reads
-  auto Kof = [&](int net, int l) { return l == 0 ? in0[net] : D.units[l - 1]; };
-  // ---- forward: layer l of the three networks in one launch
-  if (ws->nt) {
-    {   // this step's weights in the element type, [out][in padded] and (layers 1, 2) transposed [in][out]
-      StageArgs a[9];
-      for (int net = 0; net < 3; ++net)
-        for (int l = 0; l < 3; ++l)
-          a[net * 3 + l] = {P[net] + woff(net, l), Kof(net, l), D.units[l], Kof(net, l), ws->kp[net][l], ws->wn[net][l], ws->kp[net][l],
-                            ws->wt[net][l], D.units[l]};
-      stage(D, a, 9, st);
-    }
-    for (int l = 0; l < 3; ++l) {
-      NtArgs g[3];
-      for (int net = 0; net < 3; ++net) {
-        const int kp = ws->kp[net][l];
-        const void* A = l == 0 ? (const void*)((const char*)ws->xn[xsel[net]] + r0 * kp * ES) : (const void*)ws->hn[net][l - 1];
-        // bf16 runs keep the outputs of layers 0 and 1 in bf16 only (both orientations): the next layer, the weight gradient and the
-        // ELU' of the backward pass read those; the last trunk layer stays fp32 for the fp32 heads
-        g[net] = {A, l == 0 ? kp : D.units[l - 1], ws->wn[net][l], kp, MB, D.units[l], kp, kp, (D.bf16 && l < 2) ? nullptr : ws->h[net][l], D.units[l], 0,
-                  (D.bf16 && l < 2) ? ws->hn[net][l] : nullptr, D.units[l], (l < 2 && !ws->tt) ? ws->ht[net][l] : nullptr, ws->MBp,
-                  P[net] + boff(net, l), nullptr, 0, nullptr, 0, nullptr};
-      }
-      if (D.bf16) gemm_nt<1, EPI_FWD>(g, 3, 1, st); else gemm_nt<0, EPI_FWD>(g, 3, 1, st);
-    }
-  } else
+struct BigStep {   // what the three parts of one optimiser step share
+  size_t r0, ES;                                // first dataset row of the minibatch; bytes per staged element
+  const float *P[3], *X0[3]; float* G[3];       // per net: parameter / gradient buffer (actor and critic share one), fp32 layer-0 input rows
+  int xsel[3];                                  // which staged dataset input (ws->xn / xt) a network reads
+  size_t woff[3][3], boff[3][3]; int K[3][3];   // [net][l]: W_l, b_l in the flat buffers; input width
+};
+static BigStep big_step_ctx(const SdxpDev& D, const SdxpBigWs* ws, int mb, int me) {
+  const size_t r0 = (size_t)mb * ws->MB;
+  const float* obs = D.mb_obs + r0 * D.obs_dim;
+  BigStep c = {r0, D.bf16 ? (size_t)2 : (size_t)4, {D.ac, D.ac, D.cv}, {obs, obs, (me == 0 ? D.cvx0 : D.cvx1) + r0 * D.state_dim},
+               {D.ac_g, D.ac_g, D.cv_g}, {0, 0, me == 0 ? 1 : 2}, {}, {}, {}};
   for (int l = 0; l < 3; ++l) {
-    GemmArgs g[3];
-    for (int net = 0; net < 3; ++net) {
-      const int in = l == 0 ? in0[net] : D.units[l - 1];
-      const float* X = l == 0 ? X0[net] : ws->h[net][l - 1];
-      g[net] = {X, in, P[net] + woff(net, l), in, ws->h[net][l], D.units[l], 0, MB, D.units[l], in, in, P[net] + boff(net, l), nullptr, 0, nullptr};
-    }
-    gemm<0, 0, 1>(g, 3, 1, st, D.bf16 != 0);
+    c.woff[0][l] = D.off.a_w[l]; c.woff[1][l] = D.off.c_w[l]; c.woff[2][l] = D.coff.w[l];
+    c.boff[0][l] = D.off.a_b[l]; c.boff[1][l] = D.off.c_b[l]; c.boff[2][l] = D.coff.b[l];
+    for (int net = 0; net < 3; ++net) c.K[net][l] = l == 0 ? (net == 2 ? D.state_dim : D.obs_dim) : D.units[l - 1];
   }
-  if (heads_fused_ok(D)) {
-    static bool attr = false;
-    if (!attr) { attr = true; (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_big_heads), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(HeadsLds)); }
+  return c;
+}
+
+// forward: layer l of the three networks in one launch
+static void big_forward(const SdxpDev& D, const SdxpBigWs* ws, const BigStep& c, hipStream_t st) {
+  const int MB = ws->MB;
+  if (!ws->nt) {
+    for (int l = 0; l < 3; ++l) {
+      GemmArgs g[3];
+      for (int net = 0; net < 3; ++net) {
+        const int in = c.K[net][l];
+        const float* X = l == 0 ? c.X0[net] : ws->h[net][l - 1];
+        g[net] = {X, in, c.P[net] + c.woff[net][l], in, ws->h[net][l], D.units[l], 0, MB, D.units[l], in, in, c.P[net] + c.boff[net][l], nullptr, 0, nullptr};
+      }
+      gemm<0, 0, 1>(g, 3, 1, st, D.bf16 != 0);
+    }
+    return;
+  }
+  StageArgs a[9];   // this step's weights in the element type, [out][in padded] and (layers 1, 2) transposed [in][out]
+  for (int net = 0; net < 3; ++net)
+    for (int l = 0; l < 3; ++l)
+      a[net * 3 + l] = {c.P[net] + c.woff[net][l], c.K[net][l], D.units[l], c.K[net][l], ws->kp[net][l], ws->wn[net][l], ws->kp[net][l],
+                        ws->wt[net][l], D.units[l]};
+  stage(D, a, 9, st);
+  for (int l = 0; l < 3; ++l) {
+    NtArgs g[3];
+    for (int net = 0; net < 3; ++net) {
+      const int kp = ws->kp[net][l];
+      const void* A = l == 0 ? (const void*)((const char*)ws->xn[c.xsel[net]] + c.r0 * kp * c.ES) : (const void*)ws->hn[net][l - 1];
+      // bf16 runs keep the outputs of layers 0 and 1 in bf16 only (both orientations): the next layer, the weight gradient and the
+      // ELU' of the backward pass read those; the last trunk layer stays fp32 for the fp32 heads
+      g[net] = {A, l == 0 ? kp : D.units[l - 1], ws->wn[net][l], kp, MB, D.units[l], kp, kp, (D.bf16 && l < 2) ? nullptr : ws->h[net][l], D.units[l], 0,
+                (D.bf16 && l < 2) ? ws->hn[net][l] : nullptr, D.units[l], (l < 2 && !ws->tt) ? ws->ht[net][l] : nullptr, ws->MBp,
+                c.P[net] + c.boff[net][l], nullptr, 0, nullptr, 0, nullptr};
+    }
+    if (D.bf16) gemm_nt<1, EPI_FWD>(g, 3, 1, st, ws->nt_tile); else gemm_nt<0, EPI_FWD>(g, 3, 1, st, ws->nt_tile);
+  }
+}
+
+// heads, losses, head backward: data gradients into dy[net][2], weight gradients into the flat buffers, control block advanced
+static void big_heads(const SdxpDev& D, const SdxpBigWs* ws, const BigStep& c, hipStream_t st) {
+  const int MB = ws->MB, A = D.act_dim, U2 = D.units[2];
+  if (ws->fused_heads) {
     const int nrb = heads_nrb(MB), nb = heads_blocks(MB);
-    hipLaunchKernelGGL(k_big_heads, dim3(nb), dim3(512), sizeof(HeadsLds), st, D, r0, MB, nrb, ws->h[0][2], ws->h[1][2], ws->h[2][2], ws->dy[0][2], ws->dy[1][2],
+    hipLaunchKernelGGL(k_big_heads, dim3(nb), dim3(512), sizeof(HeadsLds), st, D, c.r0, MB, nrb, ws->h[0][2], ws->h[1][2], ws->h[2][2], ws->dy[0][2], ws->dy[1][2],
                        ws->dy[2][2], ws->part);
     hipLaunchKernelGGL(k_big_heads_reduce, dim3((HPZ + 31) / 32), dim3(256), 0, st, D, nb, MB, ws->part);
-  } else {
-  {  // heads
-    GemmArgs g = {ws->h[0][2], U2, D.ac + D.off.mu_w, U2, ws->mu, 24, 0, MB, A, U2, U2, D.ac + D.off.mu_b, nullptr, 0, nullptr};
-    gemm<0, 0, 2>(&g, 1, 1, st);
-    hipLaunchKernelGGL(k_rowdot, dim3((MB + 3) / 4), dim3(256), 0, st, ws->h[1][2], U2, MB, D.ac + D.off.v_w, D.ac + D.off.v_b, ws->v);
-    hipLaunchKernelGGL(k_rowdot, dim3((MB + 3) / 4), dim3(256), 0, st, ws->h[2][2], U2, MB, D.cv + D.coff.v_w, D.cv + D.coff.v_b, ws->v + MB);
+    return;
   }
-  const int hb = (MB + 255) / 256;
-  hipLaunchKernelGGL(k_big_head, dim3(hb), dim3(256), 0, st, D, r0, MB, ws->mu, ws->v, ws->v + MB, ws->dmu, ws->dv, ws->part);
-  hipLaunchKernelGGL(k_big_fin, dim3(1), dim3(64), 0, st, D, hb, MB, ws->part);
-  // ---- head backward: data gradients into dy[net][2], weight gradients into the flat buffers
-  {
-    GemmArgs g = {ws->dmu, 24, D.ac + D.off.mu_w, U2, ws->dy[0][2], U2, 0, MB, U2, A, A, nullptr, ws->h[0][2], U2, nullptr};
-    gemm<0, 1, 3>(&g, 1, 1, st);                                         // dY2 = (dmu Wmu) * ELU'(h3)
-    hipLaunchKernelGGL(k_vhead_back, dim3(512), dim3(256), 0, st, ws->dv, D.ac + D.off.v_w, ws->h[1][2], U2, MB, ws->dy[1][2]);
-    hipLaunchKernelGGL(k_vhead_back, dim3(512), dim3(256), 0, st, ws->dv + MB, D.cv + D.coff.v_w, ws->h[2][2], U2, MB, ws->dy[2][2]);
-    // mu head: G[A][U2] = dmu^T h3, bias = row sums of dmu^T; contiguous [mu_w | mu_b] in the flat layout
-    // (a 23-row product: its only parallelism is the reduction over the minibatch rows, so it is split 256 rows at a time - 32 .. 128
-    // splits instead of the trunk's 8 .. 16: 94 us -> about 15 at 32 768 rows - and the partials are summed by one wave per output)
-    const size_t pz = (size_t)A * U2 + A;
-    int Sh = MB / 256;
-    Sh = Sh < S ? S : (Sh > 128 ? 128 : Sh);
-    GemmArgs gw = {ws->dmu, 24, ws->h[0][2], U2, ws->part, U2, pz, A, U2, MB, (MB + Sh - 1) / Sh, nullptr, nullptr, 0, ws->part + (size_t)A * U2};
-    gemm<1, 1, 4>(&gw, 1, Sh, st);
-    // value heads: [v_w | v_b] contiguous; 64-row splits
-    const int VS = (MB + 63) / 64;
-    float* vp0 = ws->part + (size_t)Sh * pz;
-    float* vp1 = vp0 + (size_t)VS * (U2 + 1);
-    hipLaunchKernelGGL(k_vhead_wgrad, dim3(VS), dim3(256), 0, st, ws->dv, ws->h[1][2], U2, MB, 64, vp0, (size_t)U2 + 1);
-    hipLaunchKernelGGL(k_vhead_wgrad, dim3(VS), dim3(256), 0, st, ws->dv + MB, ws->h[2][2], U2, MB, 64, vp1, (size_t)U2 + 1);
-    hipLaunchKernelGGL(k_wave_reduce, dim3(((int)pz + 3) / 4), dim3(256), 0, st, ws->part, pz, Sh, (int)pz, D.ac_g + D.off.mu_w);
-    hipLaunchKernelGGL(k_vhead_reduce, dim3((2 * (U2 + 1) + 3) / 4), dim3(256), 0, st, vp0, vp1, (size_t)U2 + 1, VS, U2 + 1, D.ac_g + D.off.v_w,
-                       D.cv_g + D.coff.v_w);
-  }
-  }
-  // ---- trunk backward, layer by layer for the three networks at once
-  if (ws->nt) {
-    if (!ws->tt) {   // the head kernels left dLoss/d(pre-activation of trunk layer 2) in fp32: element-type copy + transpose
-      StageArgs a[3];
-      for (int net = 0; net < 3; ++net)
-        a[net] = {ws->dy[net][2], U2, MB, U2, U2, D.bf16 ? ws->dyn[net][2] : nullptr, U2, ws->dyt[net][2], ws->MBp};
-      stage(D, a, 3, st);
-    }
+  const HeadParts hp = head_parts(D, MB);
+  const size_t pz = (size_t)A * U2 + A;                                   // [mu_w | mu_b] contiguous in the flat layout
+  GemmArgs gm = {ws->h[0][2], U2, D.ac + D.off.mu_w, U2, ws->mu, 24, 0, MB, A, U2, U2, D.ac + D.off.mu_b, nullptr, 0, nullptr};
+  gemm<0, 0, 2>(&gm, 1, 1, st);
+  hipLaunchKernelGGL(k_rowdot, dim3((MB + 3) / 4), dim3(256), 0, st, ws->h[1][2], U2, MB, D.ac + D.off.v_w, D.ac + D.off.v_b, ws->v);
+  hipLaunchKernelGGL(k_rowdot, dim3((MB + 3) / 4), dim3(256), 0, st, ws->h[2][2], U2, MB, D.cv + D.coff.v_w, D.cv + D.coff.v_b, ws->v + MB);
+  hipLaunchKernelGGL(k_big_head, dim3(hp.hb), dim3(256), 0, st, D, c.r0, MB, ws->mu, ws->v, ws->v + MB, ws->dmu, ws->dv, ws->part);
+  hipLaunchKernelGGL(k_big_fin, dim3(1), dim3(64), 0, st, D, hp.hb, MB, ws->part);
+  GemmArgs gd = {ws->dmu, 24, D.ac + D.off.mu_w, U2, ws->dy[0][2], U2, 0, MB, U2, A, A, nullptr, ws->h[0][2], U2, nullptr};
+  gemm<0, 1, 3>(&gd, 1, 1, st);                                         // dY2 = (dmu Wmu) * ELU'(h3)
+  hipLaunchKernelGGL(k_vhead_back, dim3(512), dim3(256), 0, st, ws->dv, D.ac + D.off.v_w, ws->h[1][2], U2, MB, ws->dy[1][2]);
+  hipLaunchKernelGGL(k_vhead_back, dim3(512), dim3(256), 0, st, ws->dv + MB, D.cv + D.coff.v_w, ws->h[2][2], U2, MB, ws->dy[2][2]);
+  // mu head: G[A][U2] = dmu^T h3, bias = row sums of dmu^T; the partials are summed by one wave per output
+  GemmArgs gw = {ws->dmu, 24, ws->h[0][2], U2, ws->part, U2, pz, A, U2, MB, (MB + hp.Sh - 1) / hp.Sh, nullptr, nullptr, 0, ws->part + (size_t)A * U2};
+  gemm<1, 1, 4>(&gw, 1, hp.Sh, st);
+  float *vp0 = ws->part + hp.vp0, *vp1 = ws->part + hp.vp1;               // value heads: [v_w | v_b] contiguous; 64-row splits
+  hipLaunchKernelGGL(k_vhead_wgrad, dim3(hp.VS), dim3(256), 0, st, ws->dv, ws->h[1][2], U2, MB, 64, vp0, (size_t)U2 + 1);
+  hipLaunchKernelGGL(k_vhead_wgrad, dim3(hp.VS), dim3(256), 0, st, ws->dv + MB, ws->h[2][2], U2, MB, 64, vp1, (size_t)U2 + 1);
+  hipLaunchKernelGGL(k_wave_reduce, dim3(((int)pz + 3) / 4), dim3(256), 0, st, ws->part, pz, hp.Sh, (int)pz, D.ac_g + D.off.mu_w);
+  hipLaunchKernelGGL(k_vhead_reduce, dim3((2 * (U2 + 1) + 3) / 4), dim3(256), 0, st, vp0, vp1, (size_t)U2 + 1, hp.VS, U2 + 1, D.ac_g + D.off.v_w,
+                     D.cv_g + D.coff.v_w);
+}
+
+// trunk backward, layer by layer for the three networks at once
+static void big_backward(const SdxpDev& D, const SdxpBigWs* ws, const BigStep& c, hipStream_t st) {
+  const int MB = ws->MB, U2 = D.units[2], S = ws->nsplit;
+  const size_t region = ws->part_region;                                  // floats of split partials per network
+  if (!ws->nt) {
+    const int rchunk = (MB + S - 1) / S;
     for (int l = 2; l >= 0; --l) {
       const int Nl = D.units[l];
-      // splits of this layer's weight-gradient product over the minibatch rows: as few as still give the 512 workgroup slots about a
-      // round and a half of 128 x 64-or-wider tiles (every split costs a pass over [W | b] in the partial reduction), at least 4 chunks each
-      int Sl;
-      {
-        int Kmax = 0;
-        for (int net = 0; net < 3; ++net) Kmax = Kof(net, l) > Kmax ? Kof(net, l) : Kmax;
-        const int tiles = 3 * ((Nl + 127) / 128) * ((Kmax + 127) / 128);
-        Sl = (768 + tiles - 1) / tiles;
-        const int smax = ws->MBp / (4 * ws->KC) > 0 ? ws->MBp / (4 * ws->KC) : 1;
-        if (Sl > smax) Sl = smax;
-        if (Sl > S) Sl = S;
-        if (Sl < 1) Sl = 1;
-      }
-      const int kc = (((ws->MBp + Sl - 1) / Sl) + ws->KC - 1) / ws->KC * ws->KC;        // reduction rows per split, a whole number of chunks
-      NtArgs gw[3];
+      GemmArgs gw[3];
       ReduceBatch rb;
-      rb.S = Sl;
+      rb.S = S;
       for (int net = 0; net < 3; ++net) {
-        const int Kl = Kof(net, l);
-        const size_t pz = (size_t)Nl * Kl + Nl;                           // [W_l | b_l] contiguous in the flat layout
+        const int Kl = c.K[net][l];
+        const float* Xl = l == 0 ? c.X0[net] : ws->h[net][l - 1];
+        const size_t pz = (size_t)Nl * Kl + Nl;                             // [W_l | b_l] contiguous in the flat layout
         float* part = ws->part + (size_t)net * region;
-        if (ws->tt) {   // fp32: dY_l [MB][N_l] and the layer input [MB][K_l] as the other products leave them (k_gemm_tt)
-          const int kp = ws->kp[net][0];
-          const void* X = l == 0 ? (const void*)((const char*)ws->xn[xsel[net]] + r0 * kp * ES) : (const void*)ws->h[net][l - 1];
-          gw[net] = {ws->dy[net][l], Nl, X, l == 0 ? kp : D.units[l - 1], Nl, Kl, MB, kc, part, Kl, pz, nullptr, 0, nullptr, 0,
-                     nullptr, nullptr, 0, nullptr, 0, part + (size_t)Nl * Kl};
-        } else {
-          const void* Xt = l == 0 ? (const void*)((const char*)ws->xt[xsel[net]] + r0 * ES) : (const void*)ws->ht[net][l - 1];
-          gw[net] = {ws->dyt[net][l], ws->MBp, Xt, l == 0 ? ws->Rp : ws->MBp, Nl, Kl, ws->MBp, kc, part, Kl, pz, nullptr, 0, nullptr, 0,
-                     nullptr, nullptr, 0, nullptr, 0, part + (size_t)Nl * Kl};
-        }
-        rb.part[net] = part; rb.pz[net] = pz; rb.n[net] = pz; rb.out[net] = G[net] + woff(net, l);
+        gw[net] = {ws->dy[net][l], Nl, Xl, Kl, part, Kl, pz, Nl, Kl, MB, rchunk, nullptr, nullptr, 0, part + (size_t)Nl * Kl};
+        rb.part[net] = part; rb.pz[net] = pz; rb.n[net] = pz; rb.out[net] = c.G[net] + c.woff[net][l];
       }
-      if (ws->tt) gemm_tt(gw, 3, Sl, ws->zeros, st);
-      else if (D.bf16) gemm_nt<1, EPI_TN>(gw, 3, Sl, st); else gemm_nt<0, EPI_TN>(gw, 3, Sl, st);   // G_l = dY_l^T X_l, b_l = row sums of dY_l^T
+      gemm<1, 1, 4>(gw, 3, S, st, D.bf16 != 0);                             // G_l = dY_l^T X_l, b_l = row sums of dY_l^T (fused)
       hipLaunchKernelGGL(k_reduce_parts3, dim3(256, 3), dim3(256), 0, st, rb);
       if (l > 0) {
-        NtArgs gx[3];
+        GemmArgs gx[3];
         const int Kl = D.units[l - 1];
-        for (int net = 0; net < 3; ++net) {
-          if (ws->tt)   // one image: dY_{l-1} [MB][K_l] (layer 0 included: its weight gradient reads it), ELU' from the layer output itself
-            gx[net] = {ws->dy[net][l], Nl, ws->wt[net][l], Nl, MB, Kl, Nl, Nl, nullptr, 0, 0, ws->dy[net][l - 1], Kl,
-                       nullptr, 0, nullptr, ws->h[net][l - 1], Kl, nullptr, 0, nullptr};
-          else
-            gx[net] = {ws->dyn[net][l], Nl, ws->wt[net][l], Nl, MB, Kl, Nl, Nl, nullptr, 0, 0, l - 1 >= 1 ? ws->dyn[net][l - 1] : nullptr, Kl,
-                       ws->dyt[net][l - 1], ws->MBp, nullptr, ws->hn[net][l - 1], Kl, ws->ht[net][l - 1], ws->MBp, nullptr};
-        }
-        if (D.bf16) gemm_nt<1, EPI_NN>(gx, 3, 1, st); else gemm_nt<0, EPI_NN>(gx, 3, 1, st);   // dY_{l-1} = (dY_l W_l) * ELU'(H_{l-1})
+        for (int net = 0; net < 3; ++net)
+          gx[net] = {ws->dy[net][l], Nl, c.P[net] + c.woff[net][l], Kl, ws->dy[net][l - 1], Kl, 0, MB, Kl, Nl, Nl, nullptr, ws->h[net][l - 1], Kl, nullptr};
+        gemm<0, 1, 3>(gx, 3, 1, st, D.bf16 != 0);                           // dY_{l-1} = (dY_l W_l) * ELU'(H_{l-1})
       }
     }
     return;
   }
+  if (!ws->tt) {   // the head kernels left dLoss/d(pre-activation of trunk layer 2) in fp32: element-type copy + transpose
+    StageArgs a[3];
+    for (int net = 0; net < 3; ++net)
+      a[net] = {ws->dy[net][2], U2, MB, U2, U2, D.bf16 ? ws->dyn[net][2] : nullptr, U2, ws->dyt[net][2], ws->MBp};
+    stage(D, a, 3, st);
+  }
   for (int l = 2; l >= 0; --l) {
     const int Nl = D.units[l];
-    GemmArgs gw[3];
-    ReduceBatch rb;
-    rb.S = S;
-    for (int net = 0; net < 3; ++net) {
-      const int Kl = l == 0 ? in0[net] : D.units[l - 1];
-      const float* Xl = l == 0 ? X0[net] : ws->h[net][l - 1];
-      const size_t pz = (size_t)Nl * Kl + Nl;                             // [W_l | b_l] contiguous in the flat layout
-      float* part = ws->part + (size_t)net * region;
-      gw[net] = {ws->dy[net][l], Nl, Xl, Kl, part, Kl, pz, Nl, Kl, MB, rchunk, nullptr, nullptr, 0, part + (size_t)Nl * Kl};
-      rb.part[net] = part; rb.pz[net] = pz; rb.n[net] = pz; rb.out[net] = G[net] + woff(net, l);
+    // splits of this layer's weight-gradient product over the minibatch rows: as few as still give the 512 workgroup slots about a
+    // round and a half of 128 x 64-or-wider tiles (every split costs a pass over [W | b] in the partial reduction), at least 4 chunks each
+    int Sl;
+    {
+      int Kmax = 0;
+      for (int net = 0; net < 3; ++net) Kmax = c.K[net][l] > Kmax ? c.K[net][l] : Kmax;
+      const int tiles = 3 * ((Nl + 127) / 128) * ((Kmax + 127) / 128);
+      Sl = (768 + tiles - 1) / tiles;
+      const int smax = ws->MBp / (4 * ws->KC) > 0 ? ws->MBp / (4 * ws->KC) : 1;
+      if (Sl > smax) Sl = smax;
+      if (Sl > S) Sl = S;
+      if (Sl < 1) Sl = 1;
     }
-    gemm<1, 1, 4>(gw, 3, S, st, D.bf16 != 0);                             // G_l = dY_l^T X_l, b_l = row sums of dY_l^T (fused)
+    const int kc = (((ws->MBp + Sl - 1) / Sl) + ws->KC - 1) / ws->KC * ws->KC;        // reduction rows per split, a whole number of chunks
+    NtArgs gw[3];
+    ReduceBatch rb;
+    rb.S = Sl;
+    for (int net = 0; net < 3; ++net) {
+      const int Kl = c.K[net][l];
+      const size_t pz = (size_t)Nl * Kl + Nl;                           // [W_l | b_l] contiguous in the flat layout
+      float* part = ws->part + (size_t)net * region;
+      if (ws->tt) {   // fp32: dY_l [MB][N_l] and the layer input [MB][K_l] as the other products leave them (k_gemm_tt)
+        const int kp = ws->kp[net][0];
+        const void* X = l == 0 ? (const void*)((const char*)ws->xn[c.xsel[net]] + c.r0 * kp * c.ES) : (const void*)ws->h[net][l - 1];
+        gw[net] = {ws->dy[net][l], Nl, X, l == 0 ? kp : D.units[l - 1], Nl, Kl, MB, kc, part, Kl, pz, nullptr, 0, nullptr, 0,
+                   nullptr, nullptr, 0, nullptr, 0, part + (size_t)Nl * Kl};
+      } else {
+        const void* Xt = l == 0 ? (const void*)((const char*)ws->xt[c.xsel[net]] + c.r0 * c.ES) : (const void*)ws->ht[net][l - 1];
+        gw[net] = {ws->dyt[net][l], ws->MBp, Xt, l == 0 ? ws->Rp : ws->MBp, Nl, Kl, ws->MBp, kc, part, Kl, pz, nullptr, 0, nullptr, 0,
+                   nullptr, nullptr, 0, nullptr, 0, part + (size_t)Nl * Kl};
+      }
+      rb.part[net] = part; rb.pz[net] = pz; rb.n[net] = pz; rb.out[net] = c.G[net] + c.woff[net][l];
+    }
+    if (ws->tt) gemm_tt(gw, 3, Sl, ws->zeros, st, ws->nt_tile);
+    else if (D.bf16) gemm_nt<1, EPI_TN>(gw, 3, Sl, st, ws->nt_tile); else gemm_nt<0, EPI_TN>(gw, 3, Sl, st, ws->nt_tile);   // G_l = dY_l^T X_l, b_l = row sums of dY_l^T
     hipLaunchKernelGGL(k_reduce_parts3, dim3(256, 3), dim3(256), 0, st, rb);
     if (l > 0) {
-      GemmArgs gx[3];
+      NtArgs gx[3];
       const int Kl = D.units[l - 1];
-      for (int net = 0; net < 3; ++net)
-        gx[net] = {ws->dy[net][l], Nl, P[net] + woff(net, l), Kl, ws->dy[net][l - 1], Kl, 0, MB, Kl, Nl, Nl, nullptr, ws->h[net][l - 1], Kl, nullptr};
-      gemm<0, 1, 3>(gx, 3, 1, st, D.bf16 != 0);                           // dY_{l-1} = (dY_l W_l) * ELU'(H_{l-1})
+      for (int net = 0; net < 3; ++net) {
+        if (ws->tt)   // one image: dY_{l-1} [MB][K_l] (layer 0 included: its weight gradient reads it), ELU' from the layer output itself
+          gx[net] = {ws->dy[net][l], Nl, ws->wt[net][l], Nl, MB, Kl, Nl, Nl, nullptr, 0, 0, ws->dy[net][l - 1], Kl,
+                     nullptr, 0, nullptr, ws->h[net][l - 1], Kl, nullptr, 0, nullptr};
+        else
+          gx[net] = {ws->dyn[net][l], Nl, ws->wt[net][l], Nl, MB, Kl, Nl, Nl, nullptr, 0, 0, l - 1 >= 1 ? ws->dyn[net][l - 1] : nullptr, Kl,
+                     ws->dyt[net][l - 1], ws->MBp, nullptr, ws->hn[net][l - 1], Kl, ws->ht[net][l - 1], ws->MBp, nullptr};
+      }
+      if (D.bf16) gemm_nt<1, EPI_NN>(gx, 3, 1, st, ws->nt_tile); else gemm_nt<0, EPI_NN>(gx, 3, 1, st, ws->nt_tile);   // dY_{l-1} = (dY_l W_l) * ELU'(H_{l-1})
     }
   }
 }
 
-// ---- timing / test hook (not part of include/seqdex.h): launch one batched NT product on caller-owned operands (tools/time_gemm_nt.py)
-extern "C" int sdxpk_gemm_nt_launch(int bf, int epi, const NtArgs* gs, int count, int splits, hipStream_t st) {
+// forward + losses + backward of minibatch `mb` (mini-epoch `me`) for all three networks; leaves the flat gradients in ac_g / cv_g,
+// the KL word in ac_g[g_tail] and the control block advanced.  The caller follows with the explicit clip + Adam.
+extern "C" void sdxpk_big_step(const SdxpDev* D, const SdxpBigWs* ws, int mb, int me, hipStream_t st) {
+  const BigStep c = big_step_ctx(*D, ws, mb, me);
+  big_forward(*D, ws, c, st);
+  big_heads(*D, ws, c, st);
+  big_backward(*D, ws, c, st);
+}
+
+// ---- timing / test hook (not part of include/seqdex.h): one batched NT product on caller-owned operands (tools/time_gemm_nt.py); tile as SdxpOpts::nt_tile
+template <int BF, int EPI>
+static bool nt_prepare_and_launch(const NtArgs* gs, int count, int splits, int tile, hipStream_t st) {
+  const bool ok = gemm_nt_prepare<BF, EPI>();
+  if (ok) gemm_nt<BF, EPI>(gs, count, splits, st, tile);
+  return hipGetLastError() == hipSuccess && ok;   // (also clears what a refused attribute left behind)
+}
+extern "C" int sdxpk_gemm_nt_launch(int bf, int epi, const NtArgs* gs, int count, int splits, int tile, hipStream_t st) {
   if (count < 1 || count > 3 || splits < 1) return -1;
-  if (bf) {
-    if (epi == EPI_FWD) gemm_nt<1, EPI_FWD>(gs, count, splits, st);
-    else if (epi == EPI_NN) gemm_nt<1, EPI_NN>(gs, count, splits, st);
-    else if (epi == EPI_TN) gemm_nt<1, EPI_TN>(gs, count, splits, st);
-    else return -1;
-  } else {
-    if (epi == EPI_FWD) gemm_nt<0, EPI_FWD>(gs, count, splits, st);
-    else if (epi == EPI_NN) gemm_nt<0, EPI_NN>(gs, count, splits, st);
-    else if (epi == EPI_TN) gemm_nt<0, EPI_TN>(gs, count, splits, st);
-    else return -1;
-  }
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  if (epi == EPI_FWD) return (bf ? nt_prepare_and_launch<1, EPI_FWD> : nt_prepare_and_launch<0, EPI_FWD>)(gs, count, splits, tile, st) ? 0 : -1;
+  if (epi == EPI_NN) return (bf ? nt_prepare_and_launch<1, EPI_NN> : nt_prepare_and_launch<0, EPI_NN>)(gs, count, splits, tile, st) ? 0 : -1;
+  if (epi == EPI_TN) return (bf ? nt_prepare_and_launch<1, EPI_TN> : nt_prepare_and_launch<0, EPI_TN>)(gs, count, splits, tile, st) ? 0 : -1;
+  return -1;
 }

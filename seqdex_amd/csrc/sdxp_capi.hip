@@ -13,9 +13,9 @@
 #include "sdxp_types.h"
 
 extern "C" {
-void sdxpk_linear(const float*, const float*, const float*, float*, int, int, int, int, const double*, const double*, hipStream_t);
-void sdxpk_linear2(const float*, const float*, const float*, float*, int, int, const double*, const double*,
-                   const float*, const float*, const float*, float*, int, int, const double*, const double*, int, int, hipStream_t);
+void sdxpk_linear_as(const float*, const float*, const float*, float*, int, int, int, int, const double*, const double*, int, hipStream_t);
+void sdxpk_linear2_as(const float*, const float*, const float*, float*, int, int, const double*, const double*,
+                      const float*, const float*, const float*, float*, int, int, const double*, const double*, int, int, int, hipStream_t);
 void sdxpk_act_heads(const SdxpDev*, int, const float*, const float*, const int64_t*, const float*, float*, uint64_t, hipStream_t);
 void sdxpk_store_rewards(const SdxpDev*, int, const float*, const int64_t*, hipStream_t);
 void sdxpk_value_head(const SdxpDev*, float*, hipStream_t);
@@ -29,8 +29,10 @@ void sdxpk_pad_obs(const SdxpDev*, const float*, hipStream_t);
 int sdxpk_backward_factors(const SdxpDev*, int, hipStream_t);
 int sdxpk_grads_from_factors(const SdxpDev*, int, hipStream_t);
 int sdxpk_apply_factors(const SdxpDev*, int, hipStream_t);
-int sdxpk_apply_factors_fused(const SdxpDev*, int, unsigned*, hipStream_t);
-int sdxpk_update_persistent(const SdxpDev*, int, unsigned*, hipStream_t);
+int sdxpk_apply_fused_prepare(const SdxpDev*, int);
+void sdxpk_apply_factors_fused(const SdxpDev*, int, unsigned*, hipStream_t);
+int sdxpk_persist_prepare(int);
+int sdxpk_update_persistent(const SdxpDev*, int, unsigned*, int, int, hipStream_t);
 int sdxpk_fwd_bwd_persistent(const SdxpDev*, unsigned*, hipStream_t);
 int sdxpk_prenorm(const SdxpDev*, int, hipStream_t);
 void sdxpk_apply_explicit(const SdxpDev*, int, float, int, hipStream_t);
@@ -38,7 +40,7 @@ void sdxpk_apply_explicit(const SdxpDev*, int, float, int, hipStream_t);
 
 extern "C" size_t sdxpk_big_part_floats(const SdxpDev* D, int MB);
 extern "C" int sdxpk_big_nsplit(int MB);
-extern "C" int sdxpk_big_nt_enabled(const SdxpDev* D, int MB);
+extern "C" void sdxpk_big_prepare(const SdxpDev* D, int MB, SdxpOpts* o);
 extern "C" void sdxpk_big_prenorm(const SdxpDev* D, const SdxpBigWs* ws, hipStream_t st);
 extern "C" void sdxpk_big_step(const SdxpDev* D, const SdxpBigWs* ws, int mb, int me, hipStream_t st);
 extern "C" void sdxpk_apply_flat(const SdxpDev* D, hipStream_t st);
@@ -55,10 +57,11 @@ struct sdxp_agent {
   hipGraphExec_t graph_exec = nullptr;
   int graph_chunk = 0;
   bool use_persist = false;      // persistent register-resident update kernel (sdxp_persist.hip)
-  unsigned* bar_dev = nullptr;   // [64] grid-barrier counter (+ fail flags at [32] persistent kernels, [34] one-launch apply; [36] its launch counter = tag of its exchange words)
+  SdxpOpts opts;                 // the SDXP_* switches as sdxp_create found them, lowered to what this device can run (prepare_device)
+  unsigned* bar_dev = nullptr;   // [SDXP_BAR_WORDS] grid-barrier counter, fail flags and launch counter (sdxp_types.h)
   bool last_was_step = false;    // the most recent persistent launch was a single forward/backward (no restore possible on failure)
   bool use_persist_step = false; // multi-rank path: forward/backward of one minibatch as one persistent-style launch
-  bool use_fused_apply = false;  // multi-rank path: gradient rebuild + norm + clip + Adam + control block as one launch (SDXP_APPLY_IMPL=fused; default: three launches)
+  bool use_fused_apply = false;  // multi-rank path: gradient rebuild + norm + clip + Adam + control block as one launch (opts.apply_fused; default: three launches)
   unsigned* fail_host = nullptr; // pinned mirror of the fail flag, refreshed after every persistent update
   // what a persistent update touches before it can fail (old mu/sigma rows, running mean/std, control block): saved at the start
   // of the call so that sdxp_update_status can put it back and the caller can repeat the epoch on the hipGraph path
@@ -68,7 +71,6 @@ struct sdxp_agent {
   bool big = false;              // minibatch_size > 8: GEMM-shaped update path (sdxp_bigmb.hip)
   SdxpBigWs bigws;
   int big_me = 0, big_next = 0;  // multi-rank big path: mini-epoch / expected minibatch of the next sdxp_backward call
-  long max_steps = 0;            // SDXP_MAX_STEPS read ONCE at sdxp_create (0: no limit): debug limit of optimiser steps per sdxp_update
   std::string err;
 };
 
@@ -115,6 +117,37 @@ static void init_linear(std::vector<float>& p, size_t woff, int out, int in, std
   for (size_t i = 0; i < (size_t)out * in; ++i) p[woff + i] = U(rng);
 }
 
+// The one place where SDXP_* switches are read: at sdxp_create, into the handle (INTEGRATION.md has the table)
+static SdxpOpts read_opts() {
+  SdxpOpts o;
+  auto is = [](const char* name, const char* value) { const char* e = getenv(name); return e && strcmp(e, value) == 0; };
+  auto num = [](const char* name) { const char* e = getenv(name); return e ? atol(e) : 0; };
+  auto off = [](const char* name) { const char* e = getenv(name); return e && e[0] == '0'; };
+  o.update_graph = is("SDXP_UPDATE_IMPL", "graph"); o.step_kernels = is("SDXP_STEP_IMPL", "kernels"); o.apply_fused = is("SDXP_APPLY_IMPL", "fused");
+  o.max_steps = num("SDXP_MAX_STEPS");   // announced: a stray variable cannot silently truncate the epochs of a production run
+  if (o.max_steps > 0) fprintf(stderr, "libseqdex_hip: SDXP_MAX_STEPS=%ld - DEBUG LIMIT: every sdxp_update of this handle stops after %ld optimiser steps\n", o.max_steps, o.max_steps);
+  o.bigmb_nt = !off("SDXP_BIGMB_NT"); o.bigmb_tt = !off("SDXP_BIGMB_TT");
+  o.bigmb_fused_heads = !(getenv("SDXP_BIGMB_FUSED_HEADS") && num("SDXP_BIGMB_FUSED_HEADS") == 0);
+  o.nt_tile = (int)num("SDXP_NT_TILE"); o.linear_tile = (int)num("SDXP_LINEAR_TILE");
+  if (const char* e = getenv("SDXP_PERSIST_STAMPS")) if (e[0] == '1') o.persist_stamps = 1 | (((int)num("SDXP_PERSIST_STAMP_CU") & 255) << 8);
+  return o;
+}
+// read per sdxp_update call (the failure-path test sets and clears it around one): one CU of the persistent update goes silent
+static int persist_fault() { const char* e = getenv("SDXP_PERSIST_FAULT"); return e && e[0] == '1'; }
+
+// the kernels the handle's options select get their dynamic-LDS attribute on its device; a path whose kernel cannot run there takes its multi-kernel form
+static int prepare_device(sdxp_agent* h) {
+  hipDeviceProp_t prop;
+  PCHK(h, hipGetDeviceProperties(&prop, h->device));
+  const bool persist = !(h->opts.update_graph && h->opts.step_kernels) && sdxpk_persist_supported(&h->D, h->cfg.minibatch, prop.multiProcessorCount) &&
+                       sdxpk_persist_prepare(h->device);
+  h->use_persist = persist && !h->opts.update_graph;
+  h->use_persist_step = persist && !h->opts.step_kernels;
+  h->use_fused_apply = h->opts.apply_fused && sdxpk_apply_fused_prepare(&h->D, h->cfg.minibatch);
+  if (h->big) sdxpk_big_prepare(&h->D, h->cfg.minibatch, &h->opts);
+  return SDX_OK;
+}
+
 extern "C" int sdxp_create(const sdxp_config* cfg, int32_t device, uint64_t seed, sdxp_handle* out) {
   if (!cfg || !out) { gp_create_err = "sdxp_create: bad argument"; return SDX_ERR_INVALID; }
   int ndev = 0;
@@ -137,10 +170,7 @@ extern "C" int sdxp_create(const sdxp_config* cfg, int32_t device, uint64_t seed
     gp_create_err = "sdxp_create: obs_dim / state_dim above 1024 are not supported by the rollout's first-layer kernel"; return SDX_ERR_INVALID;
   }
   sdxp_agent* h = new sdxp_agent();
-  if (const char* ms = getenv("SDXP_MAX_STEPS")) {
-    h->max_steps = atol(ms);
-    if (h->max_steps > 0) fprintf(stderr, "libseqdex_hip: SDXP_MAX_STEPS=%ld - DEBUG LIMIT: every sdxp_update of this handle stops after %ld optimiser steps\n", h->max_steps, h->max_steps);
-  }
+  h->opts = read_opts();
   h->device = device;
   h->cfg = *cfg;
   PCHK(h, hipSetDevice(device));
@@ -175,6 +205,8 @@ extern "C" int sdxp_create(const sdxp_config* cfg, int32_t device, uint64_t seed
     D.coff.total = o;
   }
   int rc;
+  h->big = cfg->minibatch > 8;
+  if ((rc = prepare_device(h)) != SDX_OK) { gp_create_err = h->err; sdxp_destroy(h); return rc; }
 #define PAL(ptr, count) if ((rc = palloc(h, &(ptr), (size_t)(count))) != SDX_OK) { gp_create_err = h->err; sdxp_destroy(h); return rc; }
   PAL(D.ac, D.off.total); PAL(D.ac_m, D.off.total); PAL(D.ac_v, D.off.total);
   // both flat gradients and the KL word live in ONE allocation so that the multi-rank path needs a single all-reduce per step
@@ -189,7 +221,6 @@ extern "C" int sdxp_create(const sdxp_config* cfg, int32_t device, uint64_t seed
   PAL(D.mb_rewards, R); PAL(D.mb_dones, R); PAL(D.returns, R); PAL(D.adv, R); PAL(D.last_values, N);
   PAL(D.cur_rew, N); PAL(D.cur_len, N);
   PAL(D.rms_mean, cfg->state_dim); PAL(D.rms_var, cfg->state_dim);
-  h->big = cfg->minibatch > 8;
   const int MB = h->big ? 1 : cfg->minibatch;   // the rank-MB factor buffers below belong to the small-minibatch paths
   for (int net = 0; net < 3; ++net) {
     for (int l = 0; l < 3; ++l) {
@@ -200,7 +231,7 @@ extern "C" int sdxp_create(const sdxp_config* cfg, int32_t device, uint64_t seed
   }
   PAL(D.cvx0, R * cfg->state_dim); PAL(D.cvx1, R * cfg->state_dim);
   PAL(D.dbg, 64); PAL(D.dhead, (size_t)2 * MB * 34); PAL(D.dlogstd, 64); PAL(D.ctrl, 1); PAL(h->stats_dev, 16);
-  PAL(h->bar_dev, 64); PAL(D.ll, SDXP_LL_WORDS);
+  PAL(h->bar_dev, SDXP_BAR_WORDS); PAL(D.ll, SDXP_LL_WORDS);
   D.obs_cols = cfg->obs_cols > 0 ? cfg->obs_cols : cfg->obs_dim;
   PAL(D.obs_pad, (size_t)N * cfg->obs_dim);
   PAL(h->mus_bak, R * cfg->act_dim); PAL(h->sig_bak, R * cfg->act_dim); PAL(h->rms_bak, (size_t)2 * cfg->state_dim); PAL(h->ctrl_bak, 1);
@@ -227,12 +258,8 @@ extern "C" int sdxp_create(const sdxp_config* cfg, int32_t device, uint64_t seed
     w.part_region = sdxpk_big_part_floats(&D, cfg->minibatch);
     PAL(w.part, 3 * w.part_region);
     PAL(w.dpart, (size_t)w.nsplit * cfg->state_dim * 2);
-    w.nt = sdxpk_big_nt_enabled(&D, cfg->minibatch);
-    w.tt = 0; w.zeros = nullptr;
-    {
-      const char* e = getenv("SDXP_BIGMB_TT");
-      if (w.nt && !D.bf16 && !(e && e[0] == '0')) { w.tt = 1; PAL(w.zeros, 64); }
-    }
+    w.nt = h->opts.bigmb_nt; w.tt = h->opts.bigmb_tt; w.nt_tile = h->opts.nt_tile; w.fused_heads = h->opts.bigmb_fused_heads;
+    w.zeros = nullptr; if (w.tt) PAL(w.zeros, 64);
     if (w.nt) {   // staged operands of the NT products (sdx_gemm_nt.h); hipMemset by palloc: the padding the kernels never write stays zero
       const size_t ES = D.bf16 ? 2 : 4;
       char* q;
@@ -292,19 +319,8 @@ extern "C" int sdxp_create(const sdxp_config* cfg, int32_t device, uint64_t seed
     ctl.world = cfg->world_size > 0 ? cfg->world_size : 1;
     PCHK(h, hipMemcpy(D.ctrl, &ctl, sizeof(ctl), hipMemcpyHostToDevice));
   }
-  {
-    hipDeviceProp_t prop;
-    PCHK(h, hipGetDeviceProperties(&prop, device));
-    const char* impl = getenv("SDXP_UPDATE_IMPL");   // "persist" (default when supported) | "graph"
-    const bool supported = sdxpk_persist_supported(&D, cfg->minibatch, prop.multiProcessorCount);
-    h->use_persist = supported && !(impl && std::string(impl) == "graph");
-    const char* simpl = getenv("SDXP_STEP_IMPL");   // multi-rank path: "kernels" forces the multi-kernel forward/backward
-    h->use_persist_step = supported && !(simpl && std::string(simpl) == "kernels");
-    const char* aimpl = getenv("SDXP_APPLY_IMPL");  // multi-rank path: "fused" = the one-launch apply (opt-in: its grid-wide meeting needs every workgroup resident, i.e. the GPU to itself)
-    h->use_fused_apply = aimpl && std::string(aimpl) == "fused";
-    PCHK(h, hipHostMalloc((void**)&h->fail_host, sizeof(unsigned), hipHostMallocDefault));
-    *h->fail_host = 0;
-  }
+  PCHK(h, hipHostMalloc((void**)&h->fail_host, sizeof(unsigned), hipHostMallocDefault));
+  *h->fail_host = 0;
   pset(h, SDXP_T_AC_PARAMS, D.ac, SDX_F32, {(int64_t)D.off.total});
   pset(h, SDXP_T_AC_GRADS, D.ac_g, SDX_F32, {(int64_t)D.off.total});
   pset(h, SDXP_T_CV_PARAMS, D.cv, SDX_F32, {(int64_t)D.coff.total});
@@ -387,7 +403,7 @@ static void trunk_forward(sdxp_agent* h, int net, const float* x, int M, hipStre
   for (int l = 0; l < 3; ++l) {
     const size_t wo = net == 0 ? D.off.a_w[l] : D.coff.w[l], bo = net == 0 ? D.off.a_b[l] : D.coff.b[l];
     const bool norm = (net == 2 && l == 0 && D.cv_normalize_input);
-    sdxpk_linear(cur, P + wo, P + bo, hb[l], M, D.units[l], in, 1, norm ? D.rms_mean : nullptr, norm ? D.rms_var : nullptr, st);
+    sdxpk_linear_as(cur, P + wo, P + bo, hb[l], M, D.units[l], in, 1, norm ? D.rms_mean : nullptr, norm ? D.rms_var : nullptr, h->opts.linear_tile, st);
     cur = hb[l];
     in = D.units[l];
   }
@@ -400,9 +416,9 @@ static void trunk_forward2(sdxp_agent* h, const float* obs, const float* states,
   int ina = D.obs_dim, inv = D.state_dim;
   for (int l = 0; l < 3; ++l) {
     const bool norm = (l == 0 && D.cv_normalize_input);
-    sdxpk_linear2(xa, D.ac + D.off.a_w[l], D.ac + D.off.a_b[l], D.h_a[l], D.units[l], ina, nullptr, nullptr,
-                  xv, D.cv + D.coff.w[l], D.cv + D.coff.b[l], D.h_v[l], D.units[l], inv, norm ? D.rms_mean : nullptr, norm ? D.rms_var : nullptr,
-                  M, 1, st);
+    sdxpk_linear2_as(xa, D.ac + D.off.a_w[l], D.ac + D.off.a_b[l], D.h_a[l], D.units[l], ina, nullptr, nullptr,
+                     xv, D.cv + D.coff.w[l], D.cv + D.coff.b[l], D.h_v[l], D.units[l], inv, norm ? D.rms_mean : nullptr, norm ? D.rms_var : nullptr,
+                     M, 1, h->opts.linear_tile, st);
     xa = D.h_a[l]; xv = D.h_v[l];
     ina = inv = D.units[l];
   }
@@ -477,8 +493,7 @@ extern "C" int sdxp_update(sdxp_handle h, void* stream) {
   long total = (long)h->cfg.mini_epochs * h->D.num_minibatches;
   // debug step limit (tests/test_gpu_fullsize_properties.py pins the N = 1024 persistent update to the oracle step for step): the
   // update phase stops after SDXP_MAX_STEPS optimiser steps, in minibatch order, on whichever path the handle uses
-  // (read once, at sdxp_create, and announced on stderr there: a stray variable cannot silently truncate the epochs of a production run)
-  if (h->max_steps > 0 && h->max_steps < total) total = h->max_steps;
+  if (h->opts.max_steps > 0 && h->opts.max_steps < total) total = h->opts.max_steps;
   if (h->fail_host && *h->fail_host) {
     h->use_persist = false;   // a grid barrier of the persistent kernel timed out earlier: fall back for good
     *h->fail_host = 0;
@@ -499,8 +514,9 @@ extern "C" int sdxp_update(sdxp_handle h, void* stream) {
   if (h->use_persist) {
     sdxpk_prenorm(&h->D, MB, st);
     h->last_was_step = false;
-    if (sdxpk_update_persistent(&h->D, (int)total, h->bar_dev + 32, st) != 0) { h->err = "persistent update launch failed"; return SDX_ERR_HIP; }
-    PCHK(h, hipMemcpyAsync(h->fail_host, h->bar_dev + 32, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    unsigned* fail = h->bar_dev + SDXP_BAR_PERSIST_FAIL;
+    if (sdxpk_update_persistent(&h->D, (int)total, fail, h->opts.persist_stamps, persist_fault(), st) != 0) { h->err = "persistent update launch failed"; return SDX_ERR_HIP; }
+    PCHK(h, hipMemcpyAsync(h->fail_host, fail, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     return plaunch_ok(h, "sdxp_update(persistent)");
   }
   sdxpk_update_begin(&h->D, MB, st);
@@ -571,7 +587,7 @@ extern "C" int sdxp_backward_factors(sdxp_handle h, int32_t mb, void* stream) {
   if (mb >= h->D.num_minibatches) { h->err = "sdxp_backward_factors: minibatch index out of range"; return SDX_ERR_INVALID; }
   if (h->use_persist_step) {   // one launch: forward + backward on 256 CUs with tagged-word exchange, factors straight into D.fact
     h->last_was_step = true;
-    if (sdxpk_fwd_bwd_persistent(&h->D, h->bar_dev + 32, st) != 0) { h->err = "persistent forward/backward launch failed"; return SDX_ERR_HIP; }
+    if (sdxpk_fwd_bwd_persistent(&h->D, h->bar_dev + SDXP_BAR_PERSIST_FAIL, st) != 0) { h->err = "persistent forward/backward launch failed"; return SDX_ERR_HIP; }
     return plaunch_ok(h, "sdxp_backward_factors(persistent)");
   }
   sdxpk_backward_factors(&h->D, MB, st);
@@ -585,9 +601,9 @@ extern "C" int sdxp_grads_from_factors(sdxp_handle h, void* stream) {
 // sdxp_grads_from_factors + sdxp_apply(0, -INFINITY) + sdxp_apply(1) in four launches (the multi-rank step is launch-latency bound)
 extern "C" int sdxp_apply_factors(sdxp_handle h, void* stream) {
   if (!h) return SDX_ERR_INVALID;
-  if (h->use_fused_apply) {   // one launch with a grid-wide ticket; -1: shape or occupancy does not allow it on this device
-    if (sdxpk_apply_factors_fused(&h->D, h->cfg.minibatch, h->bar_dev, (hipStream_t)stream) == 0) return plaunch_ok(h, "sdxp_apply_factors(fused)");
-    h->use_fused_apply = false;
+  if (h->use_fused_apply) {   // one launch with a grid-wide ticket
+    sdxpk_apply_factors_fused(&h->D, h->cfg.minibatch, h->bar_dev, (hipStream_t)stream);
+    return plaunch_ok(h, "sdxp_apply_factors(fused)");
   }
   sdxpk_apply_factors(&h->D, h->cfg.minibatch, (hipStream_t)stream);
   return plaunch_ok(h, "sdxp_apply_factors");
@@ -610,22 +626,22 @@ extern "C" int sdxp_update_status(sdxp_handle h, void* stream) {
   PCHK(h, hipStreamSynchronize(st));
   if (!h->fail_host) return SDX_OK;
   if (h->use_fused_apply) {   // the one-launch apply gave up at its ticket: from that step on nothing was applied
-    PCHK(h, hipMemcpy(h->fail_host, h->bar_dev + 34, sizeof(unsigned), hipMemcpyDeviceToHost));
+    PCHK(h, hipMemcpy(h->fail_host, h->bar_dev + SDXP_BAR_APPLY_FAIL, sizeof(unsigned), hipMemcpyDeviceToHost));
     if (*h->fail_host) {
       *h->fail_host = 0;
       h->use_fused_apply = false;
-      PCHK(h, hipMemset(h->bar_dev + 34, 0, sizeof(unsigned)));
+      PCHK(h, hipMemset(h->bar_dev + SDXP_BAR_APPLY_FAIL, 0, sizeof(unsigned)));
       h->err = "sdxp_apply_factors: the one-launch apply timed out at its grid-wide meeting (not all workgroups resident?); optimiser steps of "
                "this epoch were skipped from that launch on; this handle now uses the three-launch apply - restore a checkpoint";
       return SDX_ERR_STATE;
     }
   }
-  PCHK(h, hipMemcpy(h->fail_host, h->bar_dev + 32, sizeof(unsigned), hipMemcpyDeviceToHost));
+  PCHK(h, hipMemcpy(h->fail_host, h->bar_dev + SDXP_BAR_PERSIST_FAIL, sizeof(unsigned), hipMemcpyDeviceToHost));
   if (!*h->fail_host) return SDX_OK;
   if (h->last_was_step) {   // multi-rank path: a forward/backward launch gave up; its factors were garbage and may have been applied
     *h->fail_host = 0;
     h->use_persist_step = false;
-    PCHK(h, hipMemset(h->bar_dev, 0, 36 * sizeof(unsigned)));
+    PCHK(h, hipMemset(h->bar_dev, 0, SDXP_BAR_CLEAR * sizeof(unsigned)));
     {   // tags of the failed launch must never be handed out again
       SdxpCtrl c;
       PCHK(h, hipMemcpy(&c, h->D.ctrl, sizeof(c), hipMemcpyDeviceToHost));
@@ -640,7 +656,7 @@ extern "C" int sdxp_update_status(sdxp_handle h, void* stream) {
   *h->fail_host = 0;
   h->use_persist = false;
   const size_t ra = (size_t)h->D.N * h->D.horizon * h->D.act_dim * sizeof(float), sd = (size_t)h->D.state_dim * sizeof(double);
-  PCHK(h, hipMemsetAsync(h->bar_dev, 0, 36 * sizeof(unsigned), st));
+  PCHK(h, hipMemsetAsync(h->bar_dev, 0, SDXP_BAR_CLEAR * sizeof(unsigned), st));
   PCHK(h, hipMemcpyAsync(h->D.mb_mus, h->mus_bak, ra, hipMemcpyDeviceToDevice, st));
   PCHK(h, hipMemcpyAsync(h->D.mb_sigmas, h->sig_bak, ra, hipMemcpyDeviceToDevice, st));
   PCHK(h, hipMemcpyAsync(h->D.rms_mean, h->rms_bak, sd, hipMemcpyDeviceToDevice, st));

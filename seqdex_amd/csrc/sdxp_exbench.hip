@@ -187,12 +187,8 @@ __global__ __launch_bounds__(64) void k_pingpong(u64* ll, long long* out, int pe
 // host side: `ll` >= 2 buffers x words x 8 bytes of device memory, `out` 4 x int64 on the device (zeroed by the caller).  Returns 0 / -1.
 extern "C" int sdxpk_exchange_bench(void* ll, long long* out, int words, int rounds, int fmt, int src, int pattern, unsigned tag0, hipStream_t st) {
   if (words % (XNWG * 12) != 0 || rounds < 1 || fmt < 0 || fmt > 1 || src < 0 || src > 2 || pattern < 0 || pattern > 1) return -1;
-  static bool attr = false;
   const int lds = 148 * 1024;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_exchange_bench), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -1;
-    attr = true;
-  }
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_exchange_bench), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -1;
   ExArgs a;
   a.ll = (u64*)ll; a.out = out; a.words = words; a.rounds = rounds; a.fmt = fmt; a.src = src; a.pattern = pattern; a.tag0 = tag0;
   hipLaunchKernelGGL(k_exchange_bench, dim3(XNWG), dim3(XNTH), lds, st, a);
@@ -200,12 +196,8 @@ extern "C" int sdxpk_exchange_bench(void* ll, long long* out, int words, int rou
 }
 extern "C" int sdxpk_pingpong_bench(void* ll, long long* out, int peer, int rounds, unsigned tag0, hipStream_t st) {
   if (peer < 1 || peer >= XNWG || rounds < 1) return -1;
-  static bool attr = false;
   const int lds = 148 * 1024;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_pingpong), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -1;
-    attr = true;
-  }
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_pingpong), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return -1;
   hipLaunchKernelGGL(k_pingpong, dim3(XNWG), dim3(64), lds, st, (u64*)ll, out, peer, rounds, tag0);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

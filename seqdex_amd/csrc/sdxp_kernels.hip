@@ -354,19 +354,18 @@ template <int WTM, int KS, int GKc>
 static void launch_linear_as(const LinBatch& lb, int count, int M, int Nx, hipStream_t st) {
   hipLaunchKernelGGL((k_linear_mfma<WTM, KS, GKc>), dim3((Nx + GT - 1) / GT, (M + WTM * GT - 1) / (WTM * GT), count), dim3(256 * KS), 0, st, lb);
 }
-static int g_linear_shape = 0;           // sdxpk_linear_force_shape (tests / timing tools); 0 = automatic
-#define SDXP_LINEAR_SMALL_M_SHAPE 3     // the shape below M = 2048 when SDXP_LINEAR_TILE is unset
-static void launch_linear(const LinBatch& lb, int count, int M, int Nx, hipStream_t st) {
-  // Up to 2048 rows: 64 x 64 tiles, every chunk split over two groups of four waves; beyond: 128 x 64.  SDXP_LINEAR_TILE forces one shape
-  // (timing aid): 1 = 64 x 64, 2 = 128 x 64, 3 = 64 x 64 with 2 k groups, 4 = the same with chunks of 64, 5 = 4 k groups and chunks of
+static int g_linear_shape = 0;           // sdxpk_linear_force_shape (tests / timing tools): wins over the caller's shape; 0 = none
+#define SDXP_LINEAR_SMALL_M_SHAPE 3     // the automatic shape below M = 2048
+static void launch_linear(const LinBatch& lb, int count, int M, int Nx, int shape, hipStream_t st) {
+  // shape 0 (automatic): up to 2048 rows 64 x 64 tiles, every chunk split over two groups of four waves; beyond: 128 x 64.  Otherwise one shape
+  // (SdxpOpts::linear_tile, timing aid): 1 = 64 x 64, 2 = 128 x 64, 3 = 64 x 64 with 2 k groups, 4 = the same with chunks of 64, 5 = 4 k groups and chunks of
   // 64, 6 = 64 x 64 with chunks of 64.  sdxp_act at M = 1024 (tools/time_act.py, profiles/r3_act_shapes.txt): 87 us with shape 3 or 4, 95 with
   // 1, 96 with 6, 95 with 5, 141 with 2 (round 3 started at 143 with shape 1: exec-masked loads made every wait vmcnt(0), and the LDS operands were
   // read two at a time).  The matrix pipe is about half busy in the middle layer; the rest is the per-chunk barrier and LDS read latency
   for (int i = 0; i < count; ++i)
     if (lb.a[i].nmean && lb.a[i].K > SDXP_NORM_K) { fprintf(stderr, "seqdex: k_linear_mfma normalises at most %d input columns (got %d)\n", SDXP_NORM_K, lb.a[i].K); abort(); }
-  static const int env_forced = getenv("SDXP_LINEAR_TILE") ? atoi(getenv("SDXP_LINEAR_TILE")) : 0;
-  const int forced = g_linear_shape ? g_linear_shape : env_forced;
-  const int shape = forced ? forced : (M > 2048 ? 2 : SDXP_LINEAR_SMALL_M_SHAPE);
+  if (g_linear_shape) shape = g_linear_shape;
+  if (!shape) shape = M > 2048 ? 2 : SDXP_LINEAR_SMALL_M_SHAPE;
   switch (shape) {
     case 2: launch_linear_as<2, 1, 32>(lb, count, M, Nx, st); break;
     case 3: launch_linear_as<1, 2, 32>(lb, count, M, Nx, st); break;
@@ -1474,23 +1473,34 @@ __global__ void k_apply_fin(SdxpDev D, int which, float kl_host) {
 }
 
 // ------------------------------------------------------------------------------------------------ launch helpers
-extern "C" void sdxpk_linear(const float* X, const float* W, const float* b, float* Y, int M, int N, int K, int elu_flag,
-                             const double* nmean, const double* nvar, hipStream_t st) {
+// shape: SdxpOpts::linear_tile of the handle, 0 = automatic (launch_linear)
+extern "C" void sdxpk_linear_as(const float* X, const float* W, const float* b, float* Y, int M, int N, int K, int elu_flag,
+                                const double* nmean, const double* nvar, int shape, hipStream_t st) {
   LinBatch lb;
   lb.a[0] = LinArgs{X, W, b, Y, M, N, K, elu_flag, nmean, nvar};
   lb.a[1] = lb.a[0];
-  launch_linear(lb, 1, M, N, st);
+  launch_linear(lb, 1, M, N, shape, st);
+}
+// handle-less callers (Search's T-value, kernel tests, timing tools)
+extern "C" void sdxpk_linear(const float* X, const float* W, const float* b, float* Y, int M, int N, int K, int elu_flag,
+                             const double* nmean, const double* nvar, hipStream_t st) {
+  sdxpk_linear_as(X, W, b, Y, M, N, K, elu_flag, nmean, nvar, 0, st);
 }
 extern "C" void sdxpk_linear_force_shape(int shape) { g_linear_shape = shape; }   // not part of include/*.h: kernel tests and timing tools only
 // two independent products in one launch (the same layer of the actor and of the central-value trunk)
-extern "C" void sdxpk_linear2(const float* X0, const float* W0, const float* b0, float* Y0, int N0, int K0, const double* nmean0, const double* nvar0,
-                              const float* X1, const float* W1, const float* b1, float* Y1, int N1, int K1, const double* nmean1, const double* nvar1,
-                              int M, int elu_flag, hipStream_t st) {
+extern "C" void sdxpk_linear2_as(const float* X0, const float* W0, const float* b0, float* Y0, int N0, int K0, const double* nmean0, const double* nvar0,
+                                 const float* X1, const float* W1, const float* b1, float* Y1, int N1, int K1, const double* nmean1, const double* nvar1,
+                                 int M, int elu_flag, int shape, hipStream_t st) {
   LinBatch lb;
   lb.a[0] = LinArgs{X0, W0, b0, Y0, M, N0, K0, elu_flag, nmean0, nvar0};
   lb.a[1] = LinArgs{X1, W1, b1, Y1, M, N1, K1, elu_flag, nmean1, nvar1};
   const int Nx = N0 > N1 ? N0 : N1;
-  launch_linear(lb, 2, M, Nx, st);
+  launch_linear(lb, 2, M, Nx, shape, st);
+}
+extern "C" void sdxpk_linear2(const float* X0, const float* W0, const float* b0, float* Y0, int N0, int K0, const double* nmean0, const double* nvar0,
+                              const float* X1, const float* W1, const float* b1, float* Y1, int N1, int K1, const double* nmean1, const double* nvar1,
+                              int M, int elu_flag, hipStream_t st) {
+  sdxpk_linear2_as(X0, W0, b0, Y0, N0, K0, nmean0, nvar0, X1, W1, b1, Y1, N1, K1, nmean1, nvar1, M, elu_flag, 0, st);
 }
 extern "C" void sdxpk_act_heads(const SdxpDev* D, int t, const float* obs, const float* states, const int64_t* dones,
                                 const float* eps, float* actions_out, uint64_t counter, hipStream_t st) {
@@ -1713,14 +1723,18 @@ __global__ void k_apply_fin2(SdxpDev D) {
     if (kl < 0.5f * D.kl_threshold) ctl->ac_lr = fminf(ctl->ac_lr * 1.5f, 1e-2f);
   }
 }
+// grid of k_grad_all_w / k_apply_factors_fused: four trunk-layer rows of one network per workgroup, then nhb head blocks (one output per thread, + one for the tails)
+struct ApplyGrid { int nb, Kmax; };
+static ApplyGrid apply_grid(const SdxpDev* D) {
+  const int nhb = ((D->act_dim + 2) * D->units[2] + 255) / 256 + 1;
+  return {3 * ((D->units[0] + 3) / 4) + 3 * ((D->units[1] + 3) / 4) + 3 * ((D->units[2] + 3) / 4) + nhb, D->units[0] > D->state_dim ? D->units[0] : D->state_dim};
+}
 template <int MB>
 static void launch_apply_factors(const SdxpDev* D, hipStream_t st) {
-  const int nhb = ((D->act_dim + 2) * D->units[2] + 255) / 256 + 1;   // head blocks: one output per thread, + one block for the tails
-  const int nb = 3 * ((D->units[0] + 3) / 4) + 3 * ((D->units[1] + 3) / 4) + 3 * ((D->units[2] + 3) / 4) + nhb;
-  const int Kmax = D->units[0] > D->state_dim ? D->units[0] : D->state_dim;
+  const ApplyGrid g = apply_grid(D);
   // the squared norms ride along with the gradient rebuild (one launch and one 13.4 MB read less than a separate norm pass)
-  hipLaunchKernelGGL(k_grad_all_w<MB>, dim3(nb), dim3(256), (size_t)MB * Kmax * sizeof(float), st, *D, 1);
-  hipLaunchKernelGGL(k_adam3, dim3(512, 2), dim3(256), 0, st, *D, nb);
+  hipLaunchKernelGGL(k_grad_all_w<MB>, dim3(g.nb), dim3(256), (size_t)MB * g.Kmax * sizeof(float), st, *D, 1);
+  hipLaunchKernelGGL(k_adam3, dim3(512, 2), dim3(256), 0, st, *D, g.nb);
   hipLaunchKernelGGL(k_apply_fin2, dim3(1), dim3(1), 0, st, *D);
 }
 // ---- the apply phase of the multi-rank step as ONE launch (round 6).  The three-launch form above rebuilds the summed
@@ -1732,7 +1746,7 @@ static void launch_apply_factors(const SdxpDev* D, hipStream_t st) {
 // is); workgroup 0 advances the control block behind the ticket (every workgroup read what it needs of it BEFORE it arrived).
 // Exchange discipline (MI355X guide, cross-XCD hand-off): shares and KL word leave as write-through (sc1) stores, the producer drains its
 // stores (vmcnt(0)) before the relaxed agent-scope ticket increment, consumers read them with agent-scope loads after the ticket completes.
-// A workgroup that waits too long raises the fail flag (bar[34]) and every later launch returns at once: sdxp_update_status reports it
+// A workgroup that waits too long raises the fail flag (bar[SDXP_BAR_APPLY_FAIL]) and every later launch returns at once: sdxp_update_status reports it
 // and the handle goes back to the three-launch form.
 template <int MB>
 __global__ __launch_bounds__(256, 6) void k_apply_factors_fused(SdxpDev D, unsigned* __restrict__ gen, unsigned* __restrict__ failflag) {
@@ -1968,29 +1982,19 @@ __global__ __launch_bounds__(256, 6) void k_apply_factors_fused(SdxpDev D, unsig
     }
   }
 }
-// 1 when every workgroup of the one-launch apply can be resident at once on this device (its grid-wide ticket needs that); decided once per MB
-template <int MB>
-static int apply_fused_fits(const SdxpDev* D, int nb, size_t lds) {
-  static int fits = -1;
-  if (fits < 0) {
-    int per_cu = 0, dev = 0;
-    hipDeviceProp_t prop;
-    fits = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_apply_factors_fused<MB>, 256, lds) == hipSuccess)
-      fits = (long long)per_cu * prop.multiProcessorCount >= nb ? 1 : 0;
-  }
-  return fits;
+// 1 when the shapes fit the one-launch apply's tables and every workgroup can be resident at once on the current device (its grid-wide ticket)
+extern "C" int sdxpk_apply_fused_prepare(const SdxpDev* D, int mb_size) {
+  const ApplyGrid g = apply_grid(D);
+  if (g.nb > SDXP_SQN_STRIDE || g.Kmax > 1024 || D->obs_dim > 1024 || (mb_size != 2 && mb_size != 4)) return 0;
+  int per_cu = 0, dev = 0, cus = 0;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mb_size == 2 ? k_apply_factors_fused<2> : k_apply_factors_fused<4>, 256,
+                                                      (size_t)mb_size * g.Kmax * sizeof(float)) == hipSuccess &&
+         hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && (long long)per_cu * cus >= g.nb;
 }
-extern "C" int sdxpk_apply_factors_fused(const SdxpDev* D, int mb_size, unsigned* bar, hipStream_t st) {
-  const int nhb = ((D->act_dim + 2) * D->units[2] + 255) / 256 + 1;
-  const int nb = 3 * ((D->units[0] + 3) / 4) + 3 * ((D->units[1] + 3) / 4) + 3 * ((D->units[2] + 3) / 4) + nhb;
-  const int Kmax = D->units[0] > D->state_dim ? D->units[0] : D->state_dim;
-  if (nb > SDXP_SQN_STRIDE || Kmax > 1024 || D->obs_dim > 1024) return -1;
-#define C_(M) { const size_t lds = (size_t)M * Kmax * sizeof(float); if (!apply_fused_fits<M>(D, nb, lds)) return -1; \
-                hipLaunchKernelGGL(k_apply_factors_fused<M>, dim3(nb), dim3(256), lds, st, *D, bar + 36, bar + 34); }
-  switch (mb_size) { case 2: C_(2) return 0; case 4: C_(4) return 0; default: return -1; }
-#undef C_
+extern "C" void sdxpk_apply_factors_fused(const SdxpDev* D, int mb_size, unsigned* bar, hipStream_t st) {
+  const ApplyGrid g = apply_grid(D);
+  hipLaunchKernelGGL((mb_size == 2 ? k_apply_factors_fused<2> : k_apply_factors_fused<4>), dim3(g.nb), dim3(256), (size_t)mb_size * g.Kmax * sizeof(float), st, *D,
+                     bar + SDXP_BAR_APPLY_GEN, bar + SDXP_BAR_APPLY_FAIL);
 }
 // clip_grad_norm_ + Adam + LR schedule on the flat gradients already sitting in ac_g / cv_g (KL word in ac_g[g_tail])
 extern "C" void sdxpk_apply_flat(const SdxpDev* D, hipStream_t st) {

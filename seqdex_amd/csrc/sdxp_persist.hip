@@ -1446,30 +1446,22 @@ extern "C" int sdxpk_persist_supported(const SdxpDev* D, int minibatch, int n_cu
   return minibatch == MB && D->obs_dim <= OBS && D->obs_dim % 4 == 0 && D->state_dim == ST && D->units[0] == U0 && D->units[1] == U1 &&
          D->units[2] == U2 && D->act_dim == ACT && n_cus >= NWG;
 }
-extern "C" int sdxpk_update_persistent(const SdxpDev* D, int total_steps, unsigned* failflag, hipStream_t st) {
-  static bool attr = false;
-  // SDXP_PERSIST_STAMPS=1: phase clock of CU 0; SDXP_PERSIST_STAMP_CU=<g> picks another CU (bits 8.. of the kernel's flag)
-  static const int stamps = (getenv("SDXP_PERSIST_STAMPS") && getenv("SDXP_PERSIST_STAMPS")[0] == '1')
-                                ? (1 | ((getenv("SDXP_PERSIST_STAMP_CU") ? (atoi(getenv("SDXP_PERSIST_STAMP_CU")) & 255) : 0) << 8)) : 0;
-  const char* fe = getenv("SDXP_PERSIST_FAULT");   // read per call: the failure-path test sets and clears it
-  const int fault = (fe && fe[0] == '1') ? 1 : 0;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_update_persistent<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)sizeof(PLds)) != hipSuccess) return -1;
-    attr = true;
-  }
+// both instances may use their LDS on the current device `dev` (sdxp_create); 0: they cannot, the handle takes the multi-kernel paths
+extern "C" int sdxpk_persist_prepare(int dev) {
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_update_persistent<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PLds)) == hipSuccess &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(k_update_persistent<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PLds)) == hipSuccess) return 1;
+  (void)hipGetLastError();
+  fprintf(stderr, "libseqdex_hip: k_update_persistent cannot have %zu bytes of LDS on device %d: this handle uses the hipGraph update and the multi-kernel step\n", sizeof(PLds), dev);
+  return 0;
+}
+// stamps: SdxpOpts::persist_stamps (phase clock of one CU); fault: SDXP_PERSIST_FAULT=1 (one CU goes silent: the failure-path test)
+extern "C" int sdxpk_update_persistent(const SdxpDev* D, int total_steps, unsigned* failflag, int stamps, int fault, hipStream_t st) {
   if (hipMemsetAsync(failflag, 0, sizeof(unsigned), st) != hipSuccess) return -1;
   hipLaunchKernelGGL(k_update_persistent<false>, dim3(NWG), dim3(NTH), sizeof(PLds), st, *D, total_steps, nullptr, failflag, stamps, fault);
   return 0;
 }
 // forward + backward of the minibatch under the device cursor -> D.fact (multi-rank path); the fail flag is sticky (not cleared here)
 extern "C" int sdxpk_fwd_bwd_persistent(const SdxpDev* D, unsigned* failflag, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_update_persistent<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)sizeof(PLds)) != hipSuccess) return -1;
-    attr = true;
-  }
   hipLaunchKernelGGL(k_update_persistent<true>, dim3(NWG), dim3(NTH), sizeof(PLds), st, *D, 1, nullptr, failflag, 0, 0);
   return 0;
 }

@@ -37,6 +37,19 @@ struct SdxpCtrl {
 
 #define SDXP_LL_WORDS 65536
 
+// words of a handle's barrier block (unsigned[SDXP_BAR_WORDS] in HBM): fail flag of the persistent kernels, fail flag of the one-launch apply,
+// its launch counter (= tag of its exchange words); a failed persistent launch zeroes the words below the launch counter
+enum { SDXP_BAR_PERSIST_FAIL = 32, SDXP_BAR_APPLY_FAIL = 34, SDXP_BAR_APPLY_GEN = 36, SDXP_BAR_CLEAR = SDXP_BAR_APPLY_GEN, SDXP_BAR_WORDS = 64 };
+
+// launch options of a handle: the SDXP_* switches as sdxp_create found them (read_opts), lowered where the device cannot run a kernel; defaults = empty environment
+struct SdxpOpts {
+  int update_graph = 0, step_kernels = 0, apply_fused = 0;   // SDXP_UPDATE_IMPL=graph, SDXP_STEP_IMPL=kernels, SDXP_APPLY_IMPL=fused
+  long max_steps = 0;          // SDXP_MAX_STEPS: debug limit of optimiser steps per sdxp_update (0: none)
+  int bigmb_nt = 1, bigmb_tt = 1, bigmb_fused_heads = 1;     // SDXP_BIGMB_NT / _TT / _FUSED_HEADS=0: k_gemm, transposed copies, 13-launch heads
+  int nt_tile = 0, linear_tile = 0;   // SDXP_NT_TILE (1 = 128 x 64, 2 = 128 x 128), SDXP_LINEAR_TILE (1 .. 7, launch_linear); 0 automatic
+  int persist_stamps = 0;      // SDXP_PERSIST_STAMPS=1: bit 0; SDXP_PERSIST_STAMP_CU=<g>: bits 8.. (the CU whose phase clock is recorded)
+};
+
 // rank-MB factors of one minibatch packed for the multi-rank exchange (floats): per net the inputs X_l [MB][K_l] and the
 // pre-activation gradients dY_l [MB][N_l] of the three trunk layers, the head inputs [MB][units[2]], the head gradients
 // [MB][34], dlogstd [32] and the minibatch KL
@@ -91,6 +104,7 @@ struct SdxpBigWs {
   size_t part_region;         // floats of split partials per network inside `part`
   // ---- NT path (sdx_gemm_nt.h): every operand staged k-contiguous in the element type of the run (fp32, or bf16 with mixed_precision)
   int nt;                     // 1: the trunk products run on k_gemm_nt
+  int nt_tile, fused_heads;   // SdxpOpts::nt_tile; 1: heads, losses and head gradients in k_big_heads, 0: the 13-launch head section
   int KC, MBp, Rp;            // chunk elements (32 fp32 / 64 bf16); MB rounded up to KC; dataset rows + 64 (row stride of the transposed inputs)
   int kp[3][3];               // padded reduction length of forward layer l of net
   void* xn[3];                // dataset inputs [R][kp0]: [0] observations (actor + critic), [1] cvx0, [2] cvx1
@@ -102,7 +116,7 @@ struct SdxpBigWs {
   void* dyn[3][3];            // gradients [MB][units[l]], l = 1, 2 (fp32 runs, l = 2: dy[net][2] itself)
   void* dyt[3][3];            // ... transposed [units[l]][MBp], l = 0, 1, 2
   // ---- fp32 runs: weight gradients read the [row][feature] arrays themselves (k_gemm_tt): no transposed copy of an activation or a
-  // gradient is written or read (ht / dyt / xt stay unused); SDXP_BIGMB_TT=0 keeps the transposed-copy form
+  // gradient is written or read (ht / dyt / xt stay unused); tt = 0 keeps the transposed-copy form
   int tt;
   float* zeros;               // 64 zero floats: the rows a ragged last chunk lacks
 };

@@ -1,6 +1,8 @@
 """-m gpu: the HIP PPO kernels (through the sdxp_* C ABI) against oracle/ppo_oracle.py, a plain-PyTorch autograd
 restatement of the rl_games arithmetic (PARITY UNPINNED vs rl_games itself - see the oracle header).
 SURVEY.md §8(a) rows R1-R9."""
+import os
+
 import numpy as np
 import pytest
 
@@ -125,14 +127,20 @@ def test_update_matches_autograd_adam(adaptive):
         agent.close()
 
 
-@pytest.mark.parametrize("mbsize,critic_coef", [(64, 4.0), (96, 1.0), (48, 1.0)])
-def test_large_minibatch_update_matches_autograd_adam(mbsize, critic_coef):
-    """minibatch_size > 8 (the insert policy's schedule, cfg/lego/ppo_continuous_insert.yaml: 4096, critic_coef 4) takes the GEMM-shaped
-    step of sdxp_bigmb.hip (fp32 MFMA forward / data-gradient / weight-gradient GEMMs, explicit flat gradients, clip + Adam): the
-    whole update phase against torch.autograd + Adam.  96 does not divide the 64-wide tiles: edge handling; 48 leaves the fused head kernel
-    (k_big_heads: 32 rows per block) a half-empty second block."""
+def _large_minibatch_update_against_oracle(mbsize, critic_coef, env=None):
+    """one update phase of a large-minibatch agent checked against the oracle; `env`: variables set around sdxp_create only.  Returns the
+    parameters after the update."""
     n = 48
-    agent, orc = make_pair(n, minibatch=mbsize, cv_minibatch=mbsize, critic_coef=critic_coef)
+    old = {k: os.environ.get(k) for k in (env or {})}
+    os.environ.update(env or {})
+    try:
+        agent, orc = make_pair(n, minibatch=mbsize, cv_minibatch=mbsize, critic_coef=critic_coef)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
     try:
         assert agent.update_impl() == "gemm"
         g = torch.Generator().manual_seed(7)
@@ -158,8 +166,28 @@ def test_large_minibatch_update_matches_autograd_adam(mbsize, critic_coef):
         np.testing.assert_allclose(agent.t["CV_RMS_VAR"].cpu().numpy(), orc.rms.var.numpy(), rtol=1e-5, atol=1e-7)
         assert abs(c.rms_count - float(orc.rms.count)) < 1e-9
         np.testing.assert_allclose(agent.t["MB_MUS"].cpu().numpy().reshape(-1, 23), ds["mus"].numpy(), rtol=1e-3, atol=1e-3)
+        return ac, cv
     finally:
         agent.close()
+
+
+@pytest.mark.parametrize("mbsize,critic_coef", [(64, 4.0), (96, 1.0), (48, 1.0)])
+def test_large_minibatch_update_matches_autograd_adam(mbsize, critic_coef):
+    """minibatch_size > 8 (the insert policy's schedule, cfg/lego/ppo_continuous_insert.yaml: 4096, critic_coef 4) takes the GEMM-shaped
+    step of sdxp_bigmb.hip (fp32 MFMA forward / data-gradient / weight-gradient GEMMs, explicit flat gradients, clip + Adam): the
+    whole update phase against torch.autograd + Adam.  96 does not divide the 64-wide tiles: edge handling; 48 leaves the fused head kernel
+    (k_big_heads: 32 rows per block) a half-empty second block."""
+    _large_minibatch_update_against_oracle(mbsize, critic_coef)
+
+
+def test_large_minibatch_switches_are_per_handle():
+    """the SDXP_* switches are read by sdxp_create into the handle: within one process a second agent created under
+    SDXP_BIGMB_FUSED_HEADS=0 takes the 13-launch head section although the first one has already run the fused head kernel.  Both meet the
+    bounds of test_large_minibatch_update_matches_autograd_adam; the two head sections sum in different orders, so parameters that were equal
+    bit for bit would mean that the second handle did not see its switch."""
+    ac0, cv0 = _large_minibatch_update_against_oracle(64, 4.0)
+    ac1, cv1 = _large_minibatch_update_against_oracle(64, 4.0, env={"SDXP_BIGMB_FUSED_HEADS": "0"})
+    assert not (np.array_equal(ac0, ac1) and np.array_equal(cv0, cv1))
 
 
 @pytest.mark.parametrize("mbsize", [64, 96, 384])

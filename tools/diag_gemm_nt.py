@@ -1,5 +1,5 @@
 """Where does k_gemm_nt differ from torch?  One product per (dtype, epilogue, tile shape); G and row-sum errors separately, the worst
-element's position and the error summed per 32 x 32 output block (SDXP_NT_TILE must be set by the caller: the launcher reads it once)."""
+element's position and the error summed per 32 x 32 output block (usage: python tools/diag_gemm_nt.py [tile]; tile 1 = 128 x 64, 2 = 128 x 128, default: the launcher's choice)."""
 import ctypes as C
 import sys
 
@@ -12,7 +12,8 @@ from time_gemm_nt import EPI_FWD, EPI_NN, EPI_TN, NtArgs  # noqa: E402
 
 lib = _abi.load_library()
 lib.sdxpk_gemm_nt_launch.restype = C.c_int
-lib.sdxpk_gemm_nt_launch.argtypes = [C.c_int, C.c_int, C.POINTER(NtArgs), C.c_int, C.c_int, C.c_void_p]
+lib.sdxpk_gemm_nt_launch.argtypes = [C.c_int, C.c_int, C.POINTER(NtArgs), C.c_int, C.c_int, C.c_int, C.c_void_p]
+TILE = int(sys.argv[1]) if len(sys.argv) > 1 else 0
 dev = torch.device("cuda:0")
 g = torch.Generator().manual_seed(1)
 rnd = lambda *s: (torch.randn(*s, generator=g) * 0.5).to(dev)
@@ -34,7 +35,7 @@ for bf in (0, 1):
         part = torch.full((S, pz), float("nan"), device=dev)
         a = NtArgs(A.data_ptr(), K, B.data_ptr(), K, M, N, K, kc, part.data_ptr(), N, pz, None, 0, None, 0, None, None, 0, None, 0, part.data_ptr() + 4 * M * N)
         arr = (NtArgs * 3)(a, a, a)
-        assert lib.sdxpk_gemm_nt_launch(bf, EPI_TN, arr, 1, S, None) == 0
+        assert lib.sdxpk_gemm_nt_launch(bf, EPI_TN, arr, 1, S, TILE, None) == 0
         torch.cuda.synchronize()
         tot = part.double().sum(0)
         G, rs = tot[:M * N].reshape(M, N), tot[M * N:]
@@ -52,7 +53,7 @@ for bf in (0, 1):
         Cf = torch.full((M, N), float("nan"), device=dev); Ct = torch.zeros(N, (M + 63) // 64 * 64, device=dev, dtype=dt)
         a = NtArgs(A.data_ptr(), K, B.data_ptr(), K, M, N, K, K, Cf.data_ptr(), N, 0, None, 0, Ct.data_ptr(), Ct.shape[1], bias.data_ptr(), None, 0, None, 0, None)
         arr = (NtArgs * 3)(a, a, a)
-        assert lib.sdxpk_gemm_nt_launch(bf, EPI_FWD, arr, 1, 1, None) == 0
+        assert lib.sdxpk_gemm_nt_launch(bf, EPI_FWD, arr, 1, 1, TILE, None) == 0
         torch.cuda.synchronize()
         ref = torch.nn.functional.elu(A.double() @ B.double().t() + bias.double())
         e = (Cf.double() - ref).abs()

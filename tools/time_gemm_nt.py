@@ -1,7 +1,7 @@
 """The three trunk products of the large-minibatch PPO step (csrc/sdx_gemm_nt.h) timed alone, per layer, as the step launches them (the
 same layer of the three networks per launch), against torch matmul for the result and against the MFMA peak for the rate.
 
-    python tools/time_gemm_nt.py [--mb 32768] [--bf16] [--out profiles/r4_bigmb_products_<dtype>_mb<MB>.txt]
+    python tools/time_gemm_nt.py [--mb 32768] [--bf16] [--tile 1|2] [--out profiles/r4_bigmb_products_<dtype>_mb<MB>.txt]
 """
 import argparse
 import ctypes as C
@@ -27,12 +27,13 @@ def main():
     ap.add_argument("--mb", type=int, default=32768)
     ap.add_argument("--bf16", action="store_true")
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--tile", type=int, default=0, help="force one tile shape: 1 = 128 x 64, 2 = 128 x 128 (what SDXP_NT_TILE does for a handle); 0: the launcher's choice")
     ap.add_argument("--out", default="")
     ap.add_argument("--ablate", action="store_true", help="also time the L1 forward / data-gradient products with some or all of their output copies switched off (what the epilogue costs)")
     a = ap.parse_args()
     lib = _abi.load_library()
     lib.sdxpk_gemm_nt_launch.restype = C.c_int
-    lib.sdxpk_gemm_nt_launch.argtypes = [C.c_int, C.c_int, C.POINTER(NtArgs), C.c_int, C.c_int, C.c_void_p]
+    lib.sdxpk_gemm_nt_launch.argtypes = [C.c_int, C.c_int, C.POINTER(NtArgs), C.c_int, C.c_int, C.c_int, C.c_void_p]
     dev = torch.device("cuda:0")
     dt = torch.bfloat16 if a.bf16 else torch.float32
     KC = 64 if a.bf16 else 32
@@ -47,12 +48,12 @@ def main():
     def run(name, epi, args3, flops, splits=1, check=None):
         arr = (NtArgs * 3)(*args3)
         for _ in range(3):
-            assert lib.sdxpk_gemm_nt_launch(int(a.bf16), epi, arr, 3, splits, st) == 0
+            assert lib.sdxpk_gemm_nt_launch(int(a.bf16), epi, arr, 3, splits, a.tile, st) == 0
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(a.reps):
-            lib.sdxpk_gemm_nt_launch(int(a.bf16), epi, arr, 3, splits, st)
+            lib.sdxpk_gemm_nt_launch(int(a.bf16), epi, arr, 3, splits, a.tile, st)
         e1.record()
         torch.cuda.synchronize()
         us = e0.elapsed_time(e1) * 1e3 / a.reps
