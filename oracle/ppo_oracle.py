@@ -121,7 +121,7 @@ class PPOOracle:
         sigma = torch.exp(self.logstd).expand_as(mu)
         a = mu + sigma * eps
         nlp = self.neglogp(a, mu, sigma, self.logstd)
-        v = self.cv(self.rms(states)).squeeze(-1)
+        v = self.cv(self._cv_in(states)).squeeze(-1)
         return dict(actions=a, mus=mu, sigmas=sigma, neglogp=nlp, values=v)
 
     @staticmethod
@@ -141,7 +141,32 @@ class PPOOracle:
 
     @torch.no_grad()
     def values(self, states):
-        return self.cv(self.rms(states)).squeeze(-1)
+        return self.cv(self._cv_in(states)).squeeze(-1)
+
+    def _cv_in(self, states):
+        """central-value input: running mean/std normalisation unless cv_normalize_input is off (then the bare states)"""
+        return self.rms(states) if self.cfg.get("cv_normalize_input", True) else states
+
+    @staticmethod
+    def entropy(logstd):
+        """entropy of the diagonal Gaussian: sum_a (0.5 + 0.5 log 2 pi + logstd_a); the same for every row (fixed sigma)"""
+        return (0.5 + 0.5 * math.log(2 * math.pi) + logstd).sum(-1)
+
+    def _clip_grads(self, params):
+        """clip_grad_norm_ (RC:1859-1877); truncate_grads off: the norm is still reported, the gradient is not scaled"""
+        c = self.cfg
+        return nn.utils.clip_grad_norm_(params, c["grad_norm"] if c.get("truncate_grads", True) else float("inf"))
+
+    def _value_clip_census(self, old_v, v, ret):
+        """side of the value clip per row: 0 inside (|v - v_old| <= e_clip), 1 outside with c1 > c2 (gradient through v), 2 outside
+        with c2 >= c1 (zero gradient); margin: distance of |v - v_old| from e_clip"""
+        e = self.cfg["e_clip"]
+        d = (v - old_v).detach()
+        vc = old_v + torch.clamp(d, -e, e)
+        c1, c2 = (v.detach() - ret) ** 2, (vc - ret) ** 2
+        inside = d.abs() <= e
+        side = torch.where(inside, torch.zeros_like(d), torch.where(c1 > c2, torch.ones_like(d), 2 * torch.ones_like(d))).long()
+        return side, (d.abs() - e).abs()
 
     # ---- R5: discount_values.  All arrays [H, N]
     def gae(self, rewards, values, dones, last_values, last_dones):
@@ -160,10 +185,13 @@ class PPOOracle:
         return adv, adv + values
 
     # ---- R6-R8 + central value: one train_epoch's update phase on an env-major dataset dict
-    def update(self, ds, max_steps=None):
+    def update(self, ds, max_steps=None, only=None):
         """ds: dict of env-major flattened tensors (rows r = env*H + t): obs, states, actions, mus, sigmas, neglogp,
-        values, returns.  Mutates ds['mus'/'sigmas'] like dataset.update_mu_sigma.  Returns statistics.
-        max_steps: stop each of the two loops after that many minibatches (the library's SDXP_MAX_STEPS debug limit)."""
+        values, returns.  Mutates ds['mus'/'sigmas'] like dataset.update_mu_sigma.  Returns statistics; stats["census"] records, per
+        optimiser step and row, which branch of every loss term was taken and how far from its boundary (census_summary()).
+        max_steps: stop each of the two loops after that many minibatches (the library's SDXP_MAX_STEPS debug limit).
+        only: list of (mini_epoch, minibatch) to run instead of the whole schedule (the two networks share no parameters, so calling
+        update once per minibatch in schedule order is the whole update; tests/helpers/ppo_branch_data.py builds its data that way)."""
         c = self.cfg
         mbs = c["minibatch"]
         nmb = ds["obs"].shape[0] // mbs
@@ -171,9 +199,13 @@ class PPOOracle:
         if c.get("normalize_advantage", True):
             adv = self.normalize_advantages(ds["returns"], ds["values"])
         ds["advantages"] = adv
-        stats = dict(a=[], c=[], b=[], kl=[], cv=[], lr=[], gnorm=[], cv_gnorm=[])
+        stats = dict(a=[], c=[], b=[], kl=[], cv=[], lr=[], gnorm=[], cv_gnorm=[], entropy=[])
+        census = dict(cv=[], ac=[])   # one record per optimiser step of either loop: see census_summary()
+        stats["census"] = census
         # central value first (RC:1323-1324)
         todo = [(ep, i) for ep in range(c["mini_epochs"]) for i in range(nmb)]
+        if only is not None:
+            todo = list(only)
         if max_steps is not None:
             todo = todo[:max_steps]
         for ep, i in todo:
@@ -186,10 +218,12 @@ class PPOOracle:
                 loss = self._critic_loss(ds["values"][sl], v, ds["returns"][sl]).mean()
                 self.cv_opt.zero_grad()
                 loss.backward()
-                gn = nn.utils.clip_grad_norm_(self.cv.parameters(), c["grad_norm"])
+                gn = self._clip_grads(self.cv.parameters())
                 self.cv_opt.step()
-                stats["cv"].append(float(loss))
+                stats["cv"].append(float(loss.detach()))
                 stats["cv_gnorm"].append(float(gn))
+                side, margin = self._value_clip_census(ds["values"][sl], v, ds["returns"][sl])
+                census["cv"].append(dict(vclip_side=side, vclip_margin=margin, gnorm_above=bool(float(gn) > c["grad_norm"])))
         for ep, i in todo:
             if True:
                 sl = slice(i * mbs, (i + 1) * mbs)
@@ -203,11 +237,13 @@ class PPOOracle:
                 a_loss = torch.max(-A * ratio, -A * torch.clamp(ratio, 1 - c["e_clip"], 1 + c["e_clip"]))
                 c_loss = self._critic_loss(ds["values"][sl], v, ds["returns"][sl])
                 b_loss = (torch.clamp_min(mu - 1.1, 0.0) ** 2 + torch.clamp_max(mu + 1.1, 0.0) ** 2).sum(-1)
-                loss = self.ac_loss(a_loss.mean(), c_loss.mean(), c["critic_coef"], torch.zeros(()), 0.0, b_loss.mean(), c["bounds_loss_coef"])
+                entropy = self.entropy(self.logstd)
+                loss = self.ac_loss(a_loss.mean(), c_loss.mean(), c["critic_coef"], entropy, c.get("entropy_coef", 0.0), b_loss.mean(),
+                                    c["bounds_loss_coef"])
                 for p in self.ac_params:
                     p.grad = None
                 loss.backward()
-                gn = nn.utils.clip_grad_norm_(self.ac_params, c["grad_norm"])
+                gn = self._clip_grads(self.ac_params)
                 for g in self.opt.param_groups:
                     g["lr"] = self.lr
                 self.opt.step()
@@ -219,7 +255,20 @@ class PPOOracle:
                     ds["sigmas"][sl] = sg_d
                 stats["a"].append(float(a_loss.mean())); stats["c"].append(float(c_loss.mean()))
                 stats["b"].append(float(b_loss.mean())); stats["kl"].append(float(kl)); stats["lr"].append(self.lr)
-                stats["gnorm"].append(float(gn))
+                stats["gnorm"].append(float(gn)); stats["entropy"].append(float(entropy))
+                with torch.no_grad():
+                    r = ratio.detach()
+                    lo, hi = 1 - c["e_clip"], 1 + c["e_clip"]
+                    vside, vmargin = self._value_clip_census(ds["values"][sl], v, ds["returns"][sl])
+                    klf, thr = float(kl), c["kl_threshold"]
+                    rec = dict(ratio_side=(r > hi).long() - (r < lo).long(), adv_sign=torch.sign(A).long(),
+                               ratio_margin=torch.minimum((r - lo).abs(), (r - hi).abs()),
+                               vclip_side=vside, vclip_margin=vmargin,
+                               mu_above=int((mu_d > 1.1).sum()), mu_below=int((mu_d < -1.1).sum()),
+                               mu_margin=float((mu_d.abs() - 1.1).abs().min()), gnorm_above=bool(float(gn) > c["grad_norm"]),
+                               lr_decision=(-1 if klf > 2.0 * thr else 1 if klf < 0.5 * thr else 0),
+                               kl_margin=min(abs(klf - 2.0 * thr) / (2.0 * thr), abs(klf - 0.5 * thr) / (0.5 * thr)))
+                    census["ac"].append(rec)
                 if c.get("adaptive_lr", True):   # legacy schedule: after every minibatch
                     if float(kl) > 2.0 * c["kl_threshold"]:
                         self.lr = max(self.lr / 1.5, 1e-6)
@@ -235,7 +284,32 @@ class PPOOracle:
         return (ret - v) ** 2
 
 
+def census_summary(census):
+    """counts of the row decisions (and step decisions) recorded by PPOOracle.update, and the smallest distance of any of them from
+    its boundary: ratio (from 1 -+ e_clip), value clip (|v - v_old| from e_clip; critic and central value), |mu| from 1.1, KL
+    (relative, from 2 kl_threshold and 0.5 kl_threshold)."""
+    cat = lambda recs, k: torch.cat([r[k].reshape(-1) for r in recs])
+    ac, cv = census["ac"], census["cv"]
+    side, sign = cat(ac, "ratio_side"), cat(ac, "adv_sign")
+    vs_c, vs_v = cat(ac, "vclip_side"), cat(cv, "vclip_side")
+    n = lambda m: int(m.sum())
+    counts = dict(ratio_below_adv_neg=n((side < 0) & (sign < 0)), ratio_below_adv_pos=n((side < 0) & (sign > 0)),
+                  ratio_above_adv_neg=n((side > 0) & (sign < 0)), ratio_above_adv_pos=n((side > 0) & (sign > 0)),
+                  ratio_inside=n(side == 0),
+                  critic_clip_inside=n(vs_c == 0), critic_clip_outside_c1=n(vs_c == 1), critic_clip_outside_c2=n(vs_c == 2),
+                  cv_clip_inside=n(vs_v == 0), cv_clip_outside_c1=n(vs_v == 1), cv_clip_outside_c2=n(vs_v == 2),
+                  mu_above=sum(r["mu_above"] for r in ac), mu_below=sum(r["mu_below"] for r in ac))
+    steps = dict(ac_norm_above=sum(r["gnorm_above"] for r in ac), ac_norm_below=sum(not r["gnorm_above"] for r in ac),
+                 cv_norm_above=sum(r["gnorm_above"] for r in cv), cv_norm_below=sum(not r["gnorm_above"] for r in cv),
+                 lr_raised=sum(r["lr_decision"] > 0 for r in ac), lr_lowered=sum(r["lr_decision"] < 0 for r in ac),
+                 lr_kept=sum(r["lr_decision"] == 0 for r in ac))
+    margins = dict(ratio=float(cat(ac, "ratio_margin").min()), critic_clip=float(cat(ac, "vclip_margin").min()),
+                   cv_clip=float(cat(cv, "vclip_margin").min()), mu=min(r["mu_margin"] for r in ac),
+                   kl=min(r["kl_margin"] for r in ac))
+    return dict(rows=counts, steps=steps, margins=margins)
+
+
 DEFAULT_CFG = dict(obs_dim=396, state_dim=564, act_dim=23, units=[1024, 512, 256], horizon=8, minibatch=4, mini_epochs=5,
                    gamma=0.99, tau=0.95, lr=3e-4, cv_lr=1e-3, e_clip=0.1, grad_norm=1.0, critic_coef=1.0,
                    bounds_loss_coef=1e-3, kl_threshold=0.02, clip_value=True, normalize_advantage=True,
-                   cv_normalize_input=True, adaptive_lr=True)
+                   cv_normalize_input=True, adaptive_lr=True, truncate_grads=True, entropy_coef=0.0)

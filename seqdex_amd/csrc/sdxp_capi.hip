@@ -139,8 +139,12 @@ static int persist_fault() { const char* e = getenv("SDXP_PERSIST_FAULT"); retur
 static int prepare_device(sdxp_agent* h) {
   hipDeviceProp_t prop;
   PCHK(h, hipGetDeviceProperties(&prop, h->device));
-  const bool persist = !(h->opts.update_graph && h->opts.step_kernels) && sdxpk_persist_supported(&h->D, h->cfg.minibatch, prop.multiProcessorCount) &&
-                       sdxpk_persist_prepare(h->device);
+  // k_update_persistent forms the logstd gradient without the entropy term: a handle with entropy_coef != 0 takes the multi-kernel step (k_head has it)
+  const bool no_entropy = h->D.entropy_coef == 0.0f;
+  const bool persist_fits = sdxpk_persist_supported(&h->D, h->cfg.minibatch, prop.multiProcessorCount) != 0;
+  if (persist_fits && !no_entropy && !(h->opts.update_graph && h->opts.step_kernels))
+    fprintf(stderr, "libseqdex_hip: k_update_persistent has no entropy term and entropy_coef is %g: this handle uses the hipGraph update and the multi-kernel step\n", (double)h->D.entropy_coef);
+  const bool persist = !(h->opts.update_graph && h->opts.step_kernels) && no_entropy && persist_fits && sdxpk_persist_prepare(h->device);
   h->use_persist = persist && !h->opts.update_graph;
   h->use_persist_step = persist && !h->opts.step_kernels;
   h->use_fused_apply = h->opts.apply_fused && sdxpk_apply_fused_prepare(&h->D, h->cfg.minibatch);

@@ -920,6 +920,7 @@ __global__ __launch_bounds__(1024) void k_head(SdxpDev D, int flush) {
     const int a = tid - 512;
     float dls = 0.0f;
     for (int s = 0; s < MB; ++s) dls += s_gnlp[s] * (1.0f - s_z[s][a] * s_z[s][a]) * invM;
+    dls -= D.entropy_coef;   // d(-coef * mean entropy)/d logstd = -coef (k_big_fin does the same); the norm below sees this value
     D.dlogstd[(size_t)par * 32 + a] = dls;
     s_dls[a] = dls;
   }

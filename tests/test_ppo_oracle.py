@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
-from oracle.ppo_oracle import DEFAULT_CFG, PPOOracle, RunningMeanStd  # noqa: E402
+from oracle.ppo_oracle import DEFAULT_CFG, PPOOracle, RunningMeanStd, census_summary  # noqa: E402
 
 
 def small_cfg(**kw):
@@ -83,3 +83,119 @@ def test_adaptive_lr_rule():
         if kl < 0.5 * c["kl_threshold"]:
             lr = min(lr * 1.5, 1e-2)
         assert math.isclose(lr, want)
+
+
+def _small_dataset(o, n=8, seed=1):
+    g = torch.Generator().manual_seed(seed)
+    obs, st = torch.randn(n, 12, generator=g), torch.randn(n, 8, generator=g)
+    r = o.act(obs, st, torch.randn(n, 3, generator=g))
+    return dict(obs=obs, states=st, actions=r["actions"], mus=r["mus"].clone(), sigmas=r["sigmas"].clone(), neglogp=r["neglogp"],
+                values=r["values"], returns=r["values"] + torch.randn(n, generator=g))
+
+
+def test_entropy_term_gradient_is_minus_coef_on_logstd_only():
+    """ac_loss with the entropy of the policy, sum_a(0.5 + 0.5 log 2 pi + logstd_a): against the same loss without it the gradient
+    differs by exactly -entropy_coef on every logstd component and by nothing anywhere else."""
+    o = PPOOracle(small_cfg())
+    with torch.no_grad():
+        o.logstd.copy_(torch.tensor([0.3, -0.2, 0.1]))
+    ent = PPOOracle.entropy(o.logstd)
+    np.testing.assert_allclose(float(ent), sum(0.5 + 0.5 * math.log(2 * math.pi) + x for x in (0.3, -0.2, 0.1)), rtol=1e-6)
+    np.testing.assert_allclose(float(ent), float(torch.distributions.Normal(torch.zeros(3), o.logstd.exp()).entropy().sum()), rtol=1e-6)
+    obs = torch.randn(4, 12)
+    grads = []
+    for coef in (0.0, 0.02):
+        for p in o.ac_params:
+            p.grad = None
+        mu, v = o.actor(obs), o.critic(obs).squeeze(-1)
+        a = ((mu * o.logstd.exp()) ** 2).sum(-1).mean()                  # any loss that touches every parameter
+        PPOOracle.ac_loss(a, (v ** 2).mean(), 1.0, PPOOracle.entropy(o.logstd), coef, mu.abs().sum(-1).mean(), 1e-3).backward()
+        grads.append([p.grad.clone() for p in o.ac_params])
+    for p, g0, g1 in zip(o.ac_params, *grads):
+        want = torch.full_like(g0, -0.02) if p is o.logstd else torch.zeros_like(g0)
+        np.testing.assert_allclose((g1 - g0).numpy(), want.numpy(), rtol=0, atol=1e-8)
+
+
+def test_update_carries_the_entropy_coefficient():
+    """update() with entropy_coef: the first step's logstd moves the way -entropy_coef says when nothing else acts on it (advantage 0)"""
+    c = small_cfg(adaptive_lr=False, mini_epochs=1, minibatch=8, entropy_coef=0.02, normalize_advantage=False)
+    o = PPOOracle(c)
+    ds = _small_dataset(o)
+    ds["returns"] = ds["values"].clone()                               # advantage 0: the policy loss has no gradient
+    st = o.update(ds)
+    np.testing.assert_allclose(o.logstd.detach().numpy(), c["lr"], rtol=1e-4)       # Adam's first step: -lr * sign(g), g = -0.02
+    np.testing.assert_allclose(st["entropy"][0], 3 * (0.5 + 0.5 * math.log(2 * math.pi)), rtol=1e-6)
+
+
+def test_truncate_grads_off_is_plain_adam_on_the_unscaled_gradient():
+    c = small_cfg(adaptive_lr=False, mini_epochs=1, minibatch=8, truncate_grads=False, grad_norm=1e-3)
+    o, twin = PPOOracle(c), PPOOracle(c)
+    ds = _small_dataset(o)
+    ds2 = {k: v.clone() for k, v in ds.items()}
+    # the same step by hand on the twin: the oracle's loss, torch.optim.Adam, no clipping anywhere
+    adv = PPOOracle.normalize_advantages(ds2["returns"], ds2["values"])
+    mu = twin.actor(ds2["obs"]); sigma = torch.exp(twin.logstd).expand_as(mu)
+    ratio = torch.exp(ds2["neglogp"] - PPOOracle.neglogp(ds2["actions"], mu, sigma, twin.logstd))
+    a_loss = torch.max(-adv * ratio, -adv * torch.clamp(ratio, 0.9, 1.1)).mean()
+    c_loss = twin._critic_loss(ds2["values"], twin.critic(ds2["obs"]).squeeze(-1), ds2["returns"]).mean()
+    b_loss = (torch.clamp_min(mu - 1.1, 0.0) ** 2 + torch.clamp_max(mu + 1.1, 0.0) ** 2).sum(-1).mean()
+    (a_loss + 0.5 * c_loss + 1e-3 * b_loss).backward()
+    norm = torch.sqrt(sum((p.grad ** 2).sum() for p in twin.ac_params))
+    torch.optim.Adam(twin.ac_params, lr=c["lr"], eps=1e-8).step()
+    st = o.update(ds)
+    assert float(norm) > 100 * c["grad_norm"]                          # clipping would have scaled the gradient by < 0.01
+    np.testing.assert_allclose(st["gnorm"][0], float(norm), rtol=1e-5)  # the norm is still reported
+    np.testing.assert_allclose(o.ac_flat().numpy(), twin.ac_flat().numpy(), rtol=0, atol=1e-7)
+    # and with truncation on the same step differs: Adam's epsilon makes the scale visible
+    on = PPOOracle(small_cfg(adaptive_lr=False, mini_epochs=1, minibatch=8, grad_norm=1e-3))
+    on.update({k: v.clone() for k, v in ds2.items()})
+    assert np.abs(on.ac_flat().numpy() - twin.ac_flat().numpy()).max() > 1e-6
+
+
+def test_cv_normalize_input_off_is_the_bare_network():
+    o = PPOOracle(small_cfg(cv_normalize_input=False))
+    st = torch.randn(6, 8) * 3
+    with torch.no_grad():
+        bare = o.cv(st).squeeze(-1)
+    np.testing.assert_array_equal(o.values(st).numpy(), bare.numpy())
+    np.testing.assert_array_equal(o.act(torch.randn(6, 12), st, torch.zeros(6, 3))["values"].numpy(), bare.numpy())
+    on = PPOOracle(small_cfg())                                        # default: mean 0, var 1 is still x / sqrt(1 + 1e-5) clamped to +-5
+    with torch.no_grad():
+        want = on.cv(torch.clamp(st / math.sqrt(1 + 1e-5), -5, 5)).squeeze(-1)
+    np.testing.assert_allclose(on.values(st).numpy(), want.numpy(), rtol=1e-6, atol=1e-7)
+    assert np.abs(on.values(st).numpy() - on.cv(st).squeeze(-1).detach().numpy()).max() > 1e-4
+
+
+def test_census_counts_hand_made_rows():
+    """one minibatch whose decisions are known by construction"""
+    c = small_cfg(adaptive_lr=True, mini_epochs=1, minibatch=8, normalize_advantage=False)
+    o = PPOOracle(c)
+    ds = _small_dataset(o)
+    with torch.no_grad():
+        v = o.critic(ds["obs"]).squeeze(-1)
+    ds["neglogp"] = ds["neglogp"] + torch.tensor([0.25, 0.25, -0.25, -0.25, 0.0, 0.0, 0.0, 0.0])      # ratio = exp(shift)
+    dr = torch.tensor([1.0, -1.0, 1.0, -1.0, 1.0, -1.0, 1.0, -1.0])                                 # = advantage
+    ds["values"] = v + torch.tensor([0.0, 0.05, -0.05, 0.0, 0.3, 0.3, -0.3, -0.3])                   # critic: 4 inside, 4 outside
+    ds["returns"] = ds["values"] + dr
+    s = census_summary(o.update(ds)["census"])
+    r = s["rows"]
+    assert (r["ratio_above_adv_pos"], r["ratio_above_adv_neg"], r["ratio_below_adv_pos"], r["ratio_below_adv_neg"], r["ratio_inside"]) == (1, 1, 1, 1, 4)
+    # v below the stored value by 0.3: clipped value = stored - 0.1; return above (dr > 0): the unclipped error is larger (c1), below: c2
+    assert (r["critic_clip_inside"], r["critic_clip_outside_c1"], r["critic_clip_outside_c2"]) == (4, 2, 2)
+    assert r["mu_above"] == 0 and r["mu_below"] == 0
+    assert s["steps"]["lr_raised"] == 1 and s["steps"]["lr_lowered"] == 0           # KL of the policy with itself
+    np.testing.assert_allclose(s["margins"]["ratio"], 0.1, atol=1e-4)               # the ratio-1 rows are 0.1 from both ends
+    np.testing.assert_allclose(s["margins"]["critic_clip"], 0.05, atol=1e-5)
+
+
+@pytest.mark.parametrize("n,minibatch,case", [(16, 4, "defaults"), (16, 2, "defaults"), (16, 8, "defaults"), (48, 48, "defaults"),
+                                               (16, 4, "clip_value_0"), (48, 48, "clip_value_0")])
+def test_branch_rich_data_census_on_the_oracle_alone(n, minibatch, case):
+    """the data of tests/test_gpu_ppo_branches.py (tests/helpers/ppo_branch_data.py) is decided on the CPU: its census has every class of
+    decision often enough and none close to its boundary.  (The GPU tests assert the same for every case before they compare.)"""
+    from helpers import ppo_branch_data as BD
+    over = dict(clip_value=0) if case == "clip_value_0" else {}
+    orc, ds = BD.branch_dataset(n, minibatch, **over)
+    s = census_summary(orc.update(ds)["census"])
+    bad = BD.census_violations(s, clip_value=not over, minibatch=minibatch)
+    assert not bad, bad
