@@ -373,6 +373,27 @@ int sdx_set_indexed(sdx_handle h, int32_t id, const float* src_dev, const int32_
  * sigma >= 0 (gaussian) are checked (SDX_ERR_INVALID). */
 int sdx_set_randomization(sdx_handle h, const sdx_dr_desc* desc, void* stream);
 
+/* View camera: depth, label and colour images of the listed envs from the current SDX_T_ROOT / SDX_T_RB, for
+ * looking at the engine; no task's step launches it.  k_seg_camera's pinhole model: f = normalize(target - pos), r = normalize(f x up),
+ * u = r x f, ray through pixel centre (row, col) d = f + r px + u py, row 0 on top; since d . f = 1 the depth of a hit is its distance
+ * along the optical axis (metres, +inf where nothing is hit).  What is drawn: SDX_VIEW_BOUNDS = the boxes of the segmentation camera
+ * (132 brick bounding boxes, the static bounding boxes, the robot boxes); SDX_VIEW_COLLISION = what k_physics collides (slab compounds,
+ * the hollow target brick when seg_hollow, fixed bricks as bounding boxes, every static slot's boxes with slot static_var_slot showing
+ * row static_var_row[env % 3], the robot boxes).  A box that strictly contains the ray origin is skipped.  Labels (i16): brick index + 1,
+ * robot link l -> -1 - l, static slot s -> -100 - s, background 0.  rgb: class colour x (0.35 + 0.65 |n . d| / |d|), n the entering face.
+ * env_ids_dev: device i32 [n], any subset / order / repeats (ids outside [0, N) leave their image untouched).  Outputs are caller-owned
+ * device buffers [n, height, width] (rgb: [n, height, width, 3]); any may be NULL.  Stream-ordered, no host synchronisation, no state. */
+typedef enum { SDX_VIEW_BOUNDS = 0, SDX_VIEW_COLLISION = 1 } sdx_view_geometry;
+typedef struct {
+  float pos[3], target[3], up[3];  /* env frame, or the frame of rigid body attach_body when attach_body >= 0 */
+  int32_t attach_body;             /* -1, or a row of SDX_T_RB in [0, SDX_NLINK): the camera rides on that link */
+  float hfov_deg;                  /* horizontal field of view; square pixels: vertical half extent = tan(hfov/2) * height / width */
+  int32_t width, height;           /* 1..2048 each; need not be multiples of anything */
+  int32_t geometry;                /* sdx_view_geometry */
+} sdx_view_desc;
+int sdx_render_view(sdx_handle h, const sdx_view_desc* view, const int32_t* env_ids_dev, int32_t n,
+                    float* depth_out_dev, int16_t* label_out_dev, uint8_t* rgb_out_dev, void* stream);
+
 int sdx_num_envs(sdx_handle h);
 const char* sdx_last_error(sdx_handle h);   /* never NULL; h may be NULL for create-time errors */
 

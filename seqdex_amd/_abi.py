@@ -71,6 +71,15 @@ class PPOConfig(C.Structure):
     ]
 
 
+class ViewDesc(C.Structure):
+    """sdx_view_desc"""
+    _fields_ = [("pos", f32 * 3), ("target", f32 * 3), ("up", f32 * 3), ("attach_body", i32), ("hfov_deg", f32),
+                ("width", i32), ("height", i32), ("geometry", i32)]
+
+
+VIEW_BOUNDS, VIEW_COLLISION = 0, 1    # sdx_view_geometry
+
+
 class OptState(C.Structure):
     """sdxp_opt_state"""
     _fields_ = [("rms_count", C.c_double), ("ac_t", i32), ("cv_t", i32), ("ac_lr", f32), ("cv_lr", f32)]
@@ -92,7 +101,7 @@ TP = dict(AC_PARAMS=0, AC_GRADS=1, CV_PARAMS=2, CV_GRADS=3, MB_OBS=4, MB_STATES=
 SDX_EXPORTS = ["sdx_create", "sdx_destroy", "sdx_tensor", "sdx_load_initial_states", "sdx_set_tvalue_weights", "sdx_set_retri_tvalue_weights",
                "sdx_step", "sdx_pre_physics", "sdx_simulate", "sdx_post_physics", "sdx_compute_observations",
                "sdx_reset_idx", "sdx_set_indexed", "sdx_refresh_kinematics", "sdx_render_segmentation", "sdx_num_envs", "sdx_last_error",
-               "sdx_set_randomization",
+               "sdx_set_randomization", "sdx_render_view",
                "sdxp_create", "sdxp_destroy", "sdxp_tensor", "sdxp_param_count", "sdxp_act", "sdxp_store_rewards",
                "sdxp_finish_rollout", "sdxp_get_values", "sdxp_discount_values", "sdxp_prepare_dataset", "sdxp_update", "sdxp_update_impl", "sdxp_update_status", "sdxp_backward", "sdxp_apply", "sdxp_backward_factors",
                "sdxp_grads_from_factors", "sdxp_apply_factors", "sdxp_get_state", "sdxp_set_state", "sdxp_last_error",
@@ -125,6 +134,7 @@ def load_library():
     lib.sdx_reset_idx.argtypes = [vp, vp, vp, vp]
     lib.sdx_set_indexed.argtypes = [vp, i32, vp, vp, i32, vp]
     lib.sdx_set_randomization.argtypes = [vp, vp, vp]
+    lib.sdx_render_view.argtypes = [vp, C.POINTER(ViewDesc), vp, i32, vp, vp, vp, vp]
     lib.sdx_num_envs.argtypes = [vp]
     lib.sdx_last_error.argtypes = [vp]
     lib.sdx_last_error.restype = C.c_char_p

@@ -55,7 +55,23 @@ def get_args(argv=None):
     p.add_argument("--num_threads", type=int, default=0)
     p.add_argument("--subscenes", type=int, default=0)
     p.add_argument("--slices", type=int, default=0)
+    # frames of chosen envs to disk while playing or training (view.Recorder): numbered PNGs + frames.jsonl under DIR
+    p.add_argument("--record", type=str, default="", metavar="DIR")
+    p.add_argument("--record_envs", type=str, default="0")
+    p.add_argument("--record_every", type=int, default=1)
+    p.add_argument("--record_camera", type=str, default="overview")
+    p.add_argument("--record_size", type=str, default="256x256")
     args = p.parse_args(argv)
+    try:
+        args.record_envs = [int(x) for x in str(args.record_envs).split(",") if x.strip() != ""]
+        w, h = args.record_size.lower().split("x")
+        args.record_size = (int(w), int(h))
+    except ValueError:
+        raise SystemExit("--record_envs wants a list like 0,1 and --record_size a size like 256x256")
+    if not args.record_envs or min(args.record_envs) < 0 or args.record_every < 1 or not all(1 <= v <= 2048 for v in args.record_size):
+        raise SystemExit("--record_envs >= 0, --record_every >= 1, --record_size within 1..2048")
+    if args.record_camera not in ("scene", "overview", "wrist"):
+        raise SystemExit("--record_camera: one of scene, overview, wrist")
     if args.pipeline.lower() != "gpu":
         raise SystemExit("seqdex_amd has no CPU pipeline (the product path is HIP only); use --pipeline gpu")
     args.device_id = int(args.sim_device.split(":")[1]) if ":" in args.sim_device else 0

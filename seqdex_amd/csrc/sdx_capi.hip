@@ -17,6 +17,7 @@ void sdxk_post_physics(const SdxConst*, const SdxBuf*, int, hipStream_t);
 void sdxk_physics(const SdxConst*, const SdxBuf*, hipStream_t);
 void sdxk_kinematics(const SdxConst*, const SdxBuf*, hipStream_t);
 extern "C" void sdxk_seg_camera(const SdxConst*, const SdxBuf*, hipStream_t);
+void sdxk_render_view(const SdxConst*, const SdxBuf*, const sdx_view_desc*, const int32_t*, int, float*, int16_t*, uint8_t*, hipStream_t);
 void sdxk_orient_pregrasp(const SdxConst*, const SdxBuf*, const uint8_t*, int, int, hipStream_t);
 void sdxk_orient_post_reset(const SdxConst*, const SdxBuf*, const uint8_t*, hipStream_t);
 }
@@ -675,6 +676,31 @@ extern "C" int sdx_render_segmentation(sdx_handle h, void* stream) {
   if (h->h_const.sc.task_kind != 3) { h->err = "sdx_render_segmentation: the segmentation camera belongs to BlockAssemblySearch (task_kind 3)"; return SDX_ERR_STATE; }
   sdxk_seg_camera(h->d_const, &h->buf, (hipStream_t)stream);
   return check_launch(h, "sdx_render_segmentation");
+}
+extern "C" int sdx_render_view(sdx_handle h, const sdx_view_desc* v, const int32_t* env_ids_dev, int32_t n, float* depth_out_dev,
+                               int16_t* label_out_dev, uint8_t* rgb_out_dev, void* stream) {
+  if (!h) return SDX_ERR_INVALID;
+  if (!v || n < 0 || (n > 0 && !env_ids_dev)) { h->err = "sdx_render_view: view / env_ids NULL or n < 0"; return SDX_ERR_INVALID; }
+  if (v->width < 1 || v->width > 2048 || v->height < 1 || v->height > 2048) { h->err = "sdx_render_view: width and height must lie in 1..2048"; return SDX_ERR_INVALID; }
+  if (v->attach_body < -1 || v->attach_body >= SDX_NLINK) { h->err = "sdx_render_view: attach_body must be -1 or a link in [0, SDX_NLINK)"; return SDX_ERR_INVALID; }
+  if (v->geometry != SDX_VIEW_BOUNDS && v->geometry != SDX_VIEW_COLLISION) { h->err = "sdx_render_view: geometry must be SDX_VIEW_BOUNDS or SDX_VIEW_COLLISION"; return SDX_ERR_INVALID; }
+  if (!(v->hfov_deg > 0.0f && v->hfov_deg < 180.0f)) { h->err = "sdx_render_view: hfov_deg must lie in (0, 180)"; return SDX_ERR_INVALID; }
+  double f[3], c[3], f2 = 0.0, c2 = 0.0, u2 = 0.0;
+  bool finite = true;
+  for (int a = 0; a < 3; ++a) {
+    finite = finite && std::isfinite(v->pos[a]) && std::isfinite(v->target[a]) && std::isfinite(v->up[a]);
+    f[a] = (double)v->target[a] - (double)v->pos[a];
+  }
+  if (!finite) { h->err = "sdx_render_view: pos / target / up must be finite"; return SDX_ERR_INVALID; }
+  c[0] = f[1] * v->up[2] - f[2] * v->up[1]; c[1] = f[2] * v->up[0] - f[0] * v->up[2]; c[2] = f[0] * v->up[1] - f[1] * v->up[0];
+  for (int a = 0; a < 3; ++a) { f2 += f[a] * f[a]; c2 += c[a] * c[a]; u2 += (double)v->up[a] * v->up[a]; }
+  if (!(f2 > 0.0)) { h->err = "sdx_render_view: pos == target (no view direction)"; return SDX_ERR_INVALID; }
+  if (!(c2 > 1e-12 * f2 * u2)) { h->err = "sdx_render_view: up is zero or parallel to the view direction"; return SDX_ERR_INVALID; }
+  const long long tiles = (long long)((v->width + 15) / 16) * ((v->height + 15) / 16);
+  if (tiles * n > 0x7fffffffLL) { h->err = "sdx_render_view: too many tiles for one launch (n x ceil(width / 16) x ceil(height / 16) >= 2^31)"; return SDX_ERR_INVALID; }
+  if (n == 0 || (!depth_out_dev && !label_out_dev && !rgb_out_dev)) return SDX_OK;
+  sdxk_render_view(h->d_const, &h->buf, v, env_ids_dev, n, depth_out_dev, label_out_dev, rgb_out_dev, (hipStream_t)stream);
+  return check_launch(h, "sdx_render_view");
 }
 extern "C" int sdx_refresh_kinematics(sdx_handle h, void* stream) {
   if (!h) return SDX_ERR_INVALID;

@@ -160,6 +160,36 @@ class SdxSim:
         """BlockAssemblySearch: gym.render_all_camera_sensors + pixel statistics -> SEG_IMAGE, SEG_PIXELS, EMERGENCE"""
         self._check(self.lib.sdx_render_segmentation(self.h, _stream_ptr(self.device)))
 
+    def render_view(self, env_ids, camera, width, height, geometry="collision", depth=True, label=True, rgb=True, out=None):
+        """view camera (include/seqdex.h sdx_render_view): images of the listed envs from the current ROOT / RB.
+        env_ids: a sequence or an int32 tensor on the device (any subset, order, repeats); camera: a view.ViewCamera or one of
+        "scene" / "overview" / "wrist"; geometry "collision" (what the physics collides) or "bounds" (the segmentation camera's boxes).
+        Returns {"depth": f32 [n, H, W] (+inf: nothing hit), "label": i16 [n, H, W], "rgb": u8 [n, H, W, 3]} for the outputs asked for,
+        device tensors; `out`: a dict returned earlier for the same shape, reused.  Stream-ordered, no synchronisation."""
+        from .view import named_camera
+        cam = named_camera(camera, self.scene, self._desc)
+        if torch.is_tensor(env_ids):
+            ids = env_ids
+            assert ids.dtype == torch.int32 and ids.is_contiguous() and ids.device.type == self.device.type, (ids.dtype, ids.device)
+        else:
+            ids = torch.as_tensor(list(env_ids), dtype=torch.int32).to(self.device)
+        n, w, h = int(ids.numel()), int(width), int(height)
+        spec = {"depth": (depth, (n, h, w), torch.float32), "label": (label, (n, h, w), torch.int16), "rgb": (rgb, (n, h, w, 3), torch.uint8)}
+        res, ptr = {}, {}
+        for k, (on, shape, dt) in spec.items():
+            ptr[k] = None
+            if not on:
+                continue
+            t = out.get(k) if out else None
+            if t is None or tuple(t.shape) != shape or t.dtype != dt or t.device.type != self.device.type or not t.is_contiguous():
+                t = torch.empty(shape, dtype=dt, device=self.device)
+            res[k], ptr[k] = t, C.c_void_p(t.data_ptr())
+        desc = cam.to_desc(w, h, geometry)
+        stream = _stream_ptr(self.device) if self.device.type == "cuda" else None
+        self._check(self.lib.sdx_render_view(self.h, C.byref(desc), C.c_void_p(ids.data_ptr()), n, ptr["depth"], ptr["label"], ptr["rgb"], stream))
+        res["_ids"] = ids                     # (keeps the id tensor alive until the caller drops the result)
+        return res
+
     def refresh_kinematics(self):
         self._check(self.lib.sdx_refresh_kinematics(self.h, _stream_ptr(self.device)))
 

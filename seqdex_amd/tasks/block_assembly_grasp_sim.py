@@ -137,5 +137,13 @@ class BlockAssemblyGraspSim:
     def get_states(self):                         # BT:152-153
         return self.states_buf
 
-    def render(self, sync_frame_time=False):      # headless: BT:155-177 are viewer calls
-        return None
+    def render(self, sync_frame_time=False, mode=None, env=0, camera="overview", width=256, height=256):
+        """BT:155-177 are viewer calls: without `mode` nothing happens (None).  mode "rgb_array" / "depth_array" / "label_array": one
+        image of env `env` from the view camera (view.py) as a numpy array [H, W, 3] u8 / [H, W] f32 / [H, W] i16"""
+        if mode is None:
+            return None
+        key = {"rgb_array": "rgb", "depth_array": "depth", "label_array": "label"}.get(mode)
+        if key is None:
+            raise ValueError("render mode %r: one of rgb_array, depth_array, label_array" % (mode,))
+        out = self.sim.render_view([int(env)], camera, width, height, depth=key == "depth", label=key == "label", rgb=key == "rgb")
+        return out[key][0].cpu().numpy()

@@ -33,6 +33,10 @@ def build(args, task_kwargs=None, minibatch_size=0, config_overrides=None):
     cfg_train["params"]["config"]["env_config"]["seed"] = seed
     env, agent = wrap_and_build_agent(task, cfg_train, seed, args.rl_device, minibatch_size,
                                       {**(config_overrides or {}), "name": args.task, "multi_gpu": world > 1})
+    if getattr(args, "record", ""):                # frames of the chosen envs after every env step (view.Recorder), rank 0 only
+        from .view import Recorder
+        if rank == 0:
+            env.recorder = Recorder(task, args.record, args.record_envs, args.record_every, args.record_camera, args.record_size)
     if cfg_train["params"].get("load_path"):       # (resumes the checkpoint's epoch counter, as rl_games does)
         agent.restore(cfg_train["params"]["load_path"])
     return task, env, agent, logdir, rank

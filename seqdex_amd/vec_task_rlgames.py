@@ -82,6 +82,8 @@ class VecTask:
 
 
 class RLgamesVecTaskPython(VecTask):
+    recorder = None      # a view.Recorder when --record is given (train_rlgames.build): frames are captured after every env step
+
     def get_state(self):
         return self.task.sim.STATES_CLAMPED
 
@@ -90,6 +92,8 @@ class RLgamesVecTaskPython(VecTask):
 
     def step(self, actions):
         self.task.step(actions)                      # clamp to +-1 happens in k_pre_physics (VR:166)
+        if self.recorder is not None:
+            self.recorder.capture()
         return self._obs_dict(), self.task.rew_buf, self.task.reset_buf, self.task.extras
 
     def reset(self):
