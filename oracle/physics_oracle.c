@@ -1004,4 +1004,17 @@ int sdxo_contact_keys(const sdx_scene_desc* sc, const float* root_env, const flo
   return n;
 }
 
+/* debug: what the first collision pass of the same state finds (inclusion threshold = the contact offset), listed or not, before the
+ * capacity rule: more than SDXO_MAXC means that collide() rebuilds the list without its speculative part */
+int sdxo_contacts_first_pass(const sdx_scene_desc* sc, const float* root_env, const float* dof_env) {
+  env_t* e = (env_t*)calloc(1, sizeof(env_t));
+  float tg[ND] = {0};
+  load_env(sc, e, 0, root_env, dof_env, tg);
+  fk(sc, e);
+  collide_pass(sc, e, sc->contact_offset);
+  int total = e->nc + e->overflow;
+  free(e);
+  return total;
+}
+
 int sdxo_max_contacts(void) { return SDXO_MAXC; }

@@ -23,6 +23,8 @@ def lib():
             build()
         _lib = C.CDLL(_SO)
         _lib.sdxo_contacts.restype = C.c_int
+        _lib.sdxo_contact_keys.restype = C.c_int
+        _lib.sdxo_contacts_first_pass.restype = C.c_int
         _lib.sdxo_max_contacts.restype = C.c_int
     return _lib
 
@@ -88,3 +90,22 @@ def contacts(desc, root_env, dof_env):
     d = np.ascontiguousarray(dof_env, np.float32)
     total = lib().sdxo_contacts(C.byref(desc), _p(r), _p(d), _p(out), C.c_int(cap))
     return out[:min(total, cap)], total
+
+
+def contact_keys(desc, root_env, dof_env):
+    """identity keys (uint32: enumeration index of the body pair << 15 | box pair << 6 | direction << 5 | sample) of the list contacts()
+    returns for the same state, in the same order: zip(contact_keys(...), contacts(...)[0][:, 8]) is the separation per identity"""
+    cap = lib().sdxo_max_contacts()
+    out = np.zeros(cap, np.uint32)
+    r = np.ascontiguousarray(root_env, np.float32)
+    d = np.ascontiguousarray(dof_env, np.float32)
+    n = lib().sdxo_contact_keys(C.byref(desc), _p(r), _p(d), _p(out), C.c_int(cap))
+    return out[:n]
+
+
+def first_pass_contacts(desc, root_env, dof_env):
+    """number of contacts the first collision pass finds for the state (inclusion threshold = the contact offset), before the capacity
+    rule: more than lib().sdxo_max_contacts() means that the list contacts() returns is the rebuilt one (samples with sep < 0 only)"""
+    r = np.ascontiguousarray(root_env, np.float32)
+    d = np.ascontiguousarray(dof_env, np.float32)
+    return lib().sdxo_contacts_first_pass(C.byref(desc), _p(r), _p(d))

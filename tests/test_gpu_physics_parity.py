@@ -52,11 +52,14 @@ def _one_step(s, root, dof, targets):
 
 @pytest.mark.parametrize("warm_start", [0.0, 0.8])
 def test_one_step_teacher_forcing(state, scene, warm_start):
-    """same start state, one simulate() on each side.  Contact-rich piles amplify fp32 rounding through the
-    discrete contact set (and, since the face manifold of DESIGN.md section 3.D, through its separating-axis choice), so the bar is: identical
-    contact counts, robot pose to 1e-4 (velocities 5e-4 / 1e-3), brick poses to 2e-5 m for >= 99% and brick velocities to 2e-3 m/s for
+    """same start state, one simulate() (two substeps) on each side.  Contact-rich piles amplify fp32 rounding through the
+    discrete contact set (and, since the face manifold of DESIGN.md section 3.D, through its separating-axis choice), so the bar is: contact
+    counts within 2 of the oracle's and equal in at least 75 % of the envs (they are the SECOND substep's, which starts from states that
+    already differ by rounding), robot pose to 1e-4 (velocities 2e-3), brick poses to 2e-5 m for >= 99% and brick velocities to 2e-3 m/s for
     >= 98% of the bricks, at most 2 bricks further than 1e-4 m off and none further than 1 mm (measured over 16 steps: 99.6 - 100 % within
-    2e-5 m, identical contact sets, one step in which a sample on the contact offset fell on the other side: 1 brick 0.12 mm off)."""
+    2e-5 m, one step in which a sample on the contact offset fell on the other side: 1 brick 0.12 mm off).  That the contact SETS are
+    the oracle's is not asserted here but in tests/test_gpu_physics_contact_parity.py::test_contact_sets_are_the_oracles_on_device, with
+    one substep per step, where the compared list is the one built from the shared start state."""
     from seqdex_amd.sim import SdxSim
     n = state["root"].shape[0]
     s = SdxSim(n, warm_start=warm_start)      # default: cold solver; 0.8: the optional warm start of DESIGN.md section 3.E

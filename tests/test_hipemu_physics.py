@@ -179,34 +179,116 @@ def test_emulated_compound_shapes_match_oracle(scene):
         root, dof = o_root, o_dof
 
 
-def _contact_sets(g_warm, o_warm, ns, e):
-    from tests.helpers.contact_keys import decode_kernel, decode_oracle
-    G = {decode_kernel(g_warm.key[e, c]): g_warm.lam[e, :, c] for c in range(g_warm.count[e])}
-    O = {decode_oracle(o_warm.key[e, c], ns): o_warm.lam[e, :, c] for c in range(o_warm.count[e])}
-    return G, O
-
-
 def test_emulated_contact_sets_are_the_oracles(state, scene):
     """contact by contact: after a warm-started step from an empty cache both caches hold the identities (body pair, box pair, direction,
-    sample) and impulses of the contacts of the step's last solve.  The two sides number body pairs differently
-    (tests/helpers/contact_keys.py decodes both); decoded, the SETS are identical for all 8 golden piles (about 1 000 contacts each) and the
-    impulses agree.  This is the comparison that found the device's one differing contact (a tie between two samples of one box edge,
-    DESIGN.md section 5) - tests/helpers/parity_keys.py runs it against the GPU."""
+    sample), ages and impulses of the contacts of the step's last solve.  The two sides number body pairs differently
+    (tests/helpers/contact_keys.py decodes both, tests/helpers/contact_sets.py compares them); decoded, the SETS are identical for all 8
+    golden piles (about 1 000 contacts each), the age nibbles (bits 28..31 of a key, which scale the warm start) are equal and the impulses
+    agree, over three steps.  This is the comparison that found the device's one differing contact (a tie between two samples of one
+    box edge) - tests/test_gpu_physics_contact_parity.py makes it against the GPU."""
+    from tests.helpers.contact_sets import contact_caches
     desc = scene.to_desc(warm_start=0.8)
     root, dof, tg = state["root"].copy(), state["dof"].copy(), state["targets"].copy()
     n = root.shape[0]
     g_warm, o_warm = po.WarmState(n), po.WarmState(n)
-    for it in range(2):
+    for it in range(3):
         g_root, g_dof, o_root, o_dof = root.copy(), dof.copy(), root.copy(), dof.copy()
         hipemu.simulate(desc, g_root, g_dof, tg, g_warm)
         po.simulate(desc, o_root, o_dof, tg, o_warm)
         for e in range(n):
-            G, O = _contact_sets(g_warm, o_warm, int(desc.n_static), e)
+            G, O = contact_caches(g_warm, o_warm, int(desc.n_static), e)
             assert len(G) == g_warm.count[e] and len(O) == o_warm.count[e]          # identities are unique within a solve
             assert set(G) == set(O), (e, sorted(set(G) ^ set(O))[:6])
             kinds = {(k[0][0], k[1][0]) for k in G}
             assert {("brick", "static"), ("brick", "brick"), ("rbox", "brick")} <= kinds, kinds   # all enumeration ranges occur
-            lam_g = np.array([G[k] for k in sorted(G)])
-            lam_o = np.array([O[k] for k in sorted(G)])
+            ks = sorted(G)
+            age_g, age_o = np.array([G[k][0] for k in ks]), np.array([O[k][0] for k in ks])
+            np.testing.assert_array_equal(age_g, age_o)
+            # two solves per step, the cache is the second one's: a contact that has persisted since the empty cache is 2 it + 1 solves old
+            assert age_o.max() == 2 * it + 1 and (age_o == 2 * it + 1).mean() > 0.7, np.bincount(age_o)
+            lam_g = np.array([G[k][1] for k in ks])
+            lam_o = np.array([O[k][1] for k in ks])
             np.testing.assert_allclose(lam_g, lam_o, rtol=2e-2, atol=2e-5)           # (summation order inside a body differs, 16 iterations)
         root, dof = o_root, o_dof
+
+
+def test_emulated_contact_sets_one_substep(state, scene):
+    """the comparison tests/test_gpu_physics_contact_parity.py makes on the device, with the emulated source in the device's place: one
+    substep per step, so that the cache - written by the step's last solve - holds the list built from the start state both sides share
+    bit for bit.  The emulator rounds like the oracle (no fma contraction): the sets are EQUAL, no boundary excuse.  Also proves what the
+    GPU test relies on: the oracle's contact_keys() list is the cache's identity set, boundary_pairs() names a handful of box pairs per
+    env (0 - 3 samples within 2 um of the 2 mm contact offset among 884 - 1 053 contacts), and a contact that persists ages by one per step."""
+    from tests.helpers.contact_sets import DELTA, boundary_pairs, boundary_samples, box_pair, contact_caches, oracle_list
+    desc = scene.to_desc(warm_start=0.8, substeps=1)
+    root, dof, tg = state["root"].copy(), state["dof"].copy(), state["targets"].copy()
+    n, ns = root.shape[0], int(desc.n_static)
+    g_warm, o_warm = po.WarmState(n), po.WarmState(n)
+    for it in range(3):
+        g_root, g_dof, o_root, o_dof = root.copy(), dof.copy(), root.copy(), dof.copy()
+        _, _, _, g_nc = hipemu.simulate(desc, g_root, g_dof, tg, g_warm)
+        _, _, _, o_nc = po.simulate(desc, o_root, o_dof, tg, o_warm)
+        np.testing.assert_array_equal(g_warm.count, g_nc)
+        np.testing.assert_array_equal(o_warm.count, o_nc)
+        for e in range(n):
+            G, O = contact_caches(g_warm, o_warm, ns, e)
+            assert len(G) == g_warm.count[e] and len(O) == o_warm.count[e]
+            assert set(G) == set(O), (it, e, sorted(set(G) ^ set(O))[:6])
+            lst, total = oracle_list(desc, root[e], dof[e])
+            assert total == len(lst) and [i for i, _ in lst] == [k for k in O] and len(O) == total   # same identities, same order
+            bs = boundary_samples(desc, root[e], dof[e], desc.contact_offset, DELTA)
+            bp = boundary_pairs(desc, root[e], dof[e], desc.contact_offset, DELTA)
+            assert bp == {box_pair(i) for i, _ in bs} and len(bs) <= 6, (it, e, bs)
+            assert sum(1 for k in O if box_pair(k) in bp) <= 0.05 * len(O)
+            ks = sorted(G)
+            age_g, age_o = np.array([G[k][0] for k in ks]), np.array([O[k][0] for k in ks])
+            np.testing.assert_array_equal(age_g, age_o)
+            assert age_o.max() == it and (age_o == it).mean() > 0.7, np.bincount(age_o)
+            np.testing.assert_allclose(np.array([G[k][1] for k in ks]), np.array([O[k][1] for k in ks]), rtol=2e-2, atol=2e-5)
+        dp = np.abs(g_root[:, 9:81, :7] - o_root[:, 9:81, :7])
+        assert dp.max() < 2e-5, dp.max()
+        root, dof = o_root, o_dof
+
+
+def test_emulated_capacity_rule_one_substep(state, scene):
+    """the capacity case of tests/test_gpu_physics_contact_parity.py with the emulated source in the device's place (contact offset 1.4 cm,
+    golden envs 0, 1, 3, 4, 6, one substep, warm start 0.8).  From the oracle alone: env 0 stays below the capacity (1 515 contacts), the
+    first pass of the other four exceeds it and their rebuilt lists hold 708 - 844 contacts, all touching or penetrating, none within 1 um
+    of the rebuild threshold 0 and at most 9 samples within 2 um of it.  Then: EQUAL sets (no boundary excuse: the emulator rounds like the
+    oracle), equal ages and impulses, the same step, four rebuilt env-substeps."""
+    from tests.helpers.contact_sets import DELTA, boundary_samples, contact_caches, oracle_list
+    envs = [0, 1, 3, 4, 6]
+    desc = scene.to_desc(contact_offset=0.014, warm_start=0.8, substeps=1)
+    root, dof, tg = state["root"][envs].copy(), state["dof"][envs].copy(), state["targets"][envs].copy()
+    n, ns, cap = len(envs), int(desc.n_static), po.lib().sdxo_max_contacts()
+    first = np.array([po.first_pass_contacts(desc, root[e], dof[e]) for e in range(n)])
+    assert first[0] == 1515 and (first[1:] > cap).all(), first
+    for e in range(n):
+        lst, total = oracle_list(desc, root[e], dof[e])
+        sep = np.array([s for _, s in lst])
+        assert total == len(lst)
+        if e == 0:
+            assert total == 1515 and (sep > 0).sum() > 900
+            assert len(boundary_samples(desc, root[e], dof[e], desc.contact_offset, DELTA)) <= 9
+        else:
+            assert 708 <= total <= 844 and (sep <= 0).all() and (sep < -1e-6).all(), (e, total, sep.max())
+            assert len(boundary_samples(desc, root[e], dof[e], 0.0, DELTA)) <= 9
+    hipemu.contact_stats()                                    # (reset)
+    g_warm, o_warm = po.WarmState(n), po.WarmState(n)
+    g_root, g_dof, o_root, o_dof = root.copy(), dof.copy(), root.copy(), dof.copy()
+    _, _, _, g_nc = hipemu.simulate(desc, g_root, g_dof, tg, g_warm)
+    _, _, _, o_nc = po.simulate(desc, o_root, o_dof, tg, o_warm)
+    np.testing.assert_array_equal(g_nc, o_nc)
+    np.testing.assert_array_equal(g_warm.count, g_nc)
+    for e in range(n):
+        G, O = contact_caches(g_warm, o_warm, ns, e)
+        assert len(G) == g_nc[e] and len(O) == o_nc[e]
+        assert set(G) == set(O), (e, sorted(set(G) ^ set(O))[:6])
+        assert [k for k in O] == [i for i, _ in oracle_list(desc, root[e], dof[e])[0]]
+        ks = sorted(G)
+        assert all(G[k][0] == 0 and O[k][0] == 0 for k in ks)
+        np.testing.assert_allclose(np.array([G[k][1] for k in ks]), np.array([O[k][1] for k in ks]), rtol=2e-2, atol=2e-5)
+    dp = np.abs(g_root[:, 9:81, :7] - o_root[:, 9:81, :7])
+    assert dp[1:].max() < 2e-5 and dp[0].max() < 1e-3, (dp[1:].max(), dp[0].max())
+    st = hipemu.contact_stats()
+    # [0] is the largest list a solve was given (after the rebuild): env 0's; nothing lost, four envs rebuilt, no pair list overflowed
+    assert st[0] == o_nc.max() == 1515 and st[1] == 0 and st[2] == 4 and st[3] == 0, st
