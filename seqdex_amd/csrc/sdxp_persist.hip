@@ -15,7 +15,7 @@
 //   W1 rows      : wave w owns quarter (w&3) of row 2g+(w>>2) of the three nets     (forward)
 //   W1 columns   : CU g owns columns 4g..4g+3 of the three nets, thread = row       (backward; duplicate copy, same Adam)
 //   W2 rows      : wave w owns eighth w of row g of the three nets                  (forward)
-//   W2 columns   : CU g owns columns 2g, 2g+1: thread = (column, row)               (backward; duplicate copy)
+//   W2 columns   : CU g owns columns 2g, 2g+1: lanes l / l ^ 32 of wave w = row 32w + (l & 31) of the two columns (backward; duplicate copy)
 //   heads        : CU g runs Adam for 25 of the 6 400 head weights and publishes them; every CU reads the matrix back in phase D
 // Row and column copies receive the same gradient g[n][k] = sum_s dY_s[n] X_s[k] (same operands, same order), so they
 // stay bit-identical without communication.  The multi-kernel path (sdxp_kernels.hip) remains the fallback for other shapes
@@ -48,6 +48,13 @@ __device__ __forceinline__ float wave_sum(float v) {
   v = dpp_add<0xB1, 0xF>(v); v = dpp_add<0x4E, 0xF>(v); v = dpp_add<0x141, 0xF>(v); v = dpp_add<0x140, 0xF>(v);
   v = dpp_add<0x142, 0xA>(v); v = dpp_add<0x143, 0xC>(v);
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+// v + (the value of lane ^ 32), in both lanes: v_permlane32_swap_b32 of v with itself leaves the lower half's values in one result and the
+// upper half's in the other
+__device__ __forceinline__ float pair_sum(float v) {
+  const unsigned u = __builtin_bit_cast(unsigned, v);
+  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+  return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
 }
 // Opaque copy of an index.  volatile asm statements keep their program order relative to each other and to sched_barrier,
 // and an LDS load whose address depends on the result cannot be floated above it: this is what keeps the operand loads of
@@ -327,7 +334,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     tid = t; lane = t & 63; wave = __builtin_amdgcn_readfirstlane(t >> 6); g = b;
     r0w = wave >> 1; h0 = wave & 1; n0 = 4 * g + r0w;
     r1w = wave >> 2; q1 = wave & 3; r1 = 2 * g + r1w;
-    c2c = t >> 8; c2n = t & 255;
+    c2c = (t >> 5) & 1; c2n = 32 * (t >> 6) + (t & 31);   // column c2n: lanes l and l ^ 32 of one wave hold its two row halves
     he = HPC * g + t; hrow = he >> 8; hk = he & (U2 - 1);
   };
   refresh();
@@ -348,7 +355,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
   float c1[3][4], cm1[3][4], cv1[3][4];
   // layer 2 rows: row g, eighth = wave: k = wave*64 + lane
   float w2[3], m2[3], v2[3];
-  // layer 2 columns: col 2g + (tid>>8), row n = tid & 255
+  // layer 2 columns: col 2g + c2c, row n = c2n (c2c = lane >> 5, c2n = 32 wave + (lane & 31): refresh())
   float c2[3], cm2[3], cv2[3];
   // heads ((A+2) x U2 = 6400 weights): CU g runs Adam for the HPC flat elements [HPC g, HPC g + HPC) on its first HPC threads and
   // publishes the new weight in the parameter array; phase D of every CU reads the whole head matrix back through L2.
@@ -772,20 +779,23 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       pf_osg = __hip_atomic_load(&D.mb_sigmas[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     {
-      float v0[4], v1[4], v2[4];
-      if (!(px2_issued && lq_take<4>(px2, tag, v0, v1, v2)) && !lq_gather<4>(LQ, LQ_X2 + tid, NTH, tag, v0, v1, v2, failflag)) S.fail = 1;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { (&S.x2[0][0][0])[tid + NTH * j] = v0[j]; (&S.x2[1][0][0])[tid + NTH * j] = v1[j]; (&S.x2[2][0][0])[tid + NTH * j] = v2[j]; }
-    }
-    TS(7)
-    __syncthreads();
-    {
+      // Word tid + NTH j is (sample j, unit tid) - and unit tid = wave 64 + lane is the element of row g this lane owns: the products of
+      // forward L2 are formed from the gathered registers; the S.x2 image (Gram of x2, backward L2's elu', the next step's Adam of layer 2)
+      // is stored behind them, under the DPP sums.
+      static_assert(NTH == U1 && MB == 4, "word tid + NTH j of the x2 edge is (sample j, unit tid)");
       float q[3][MB];
-      const int k = wave * 64 + lane;
+      {
+        float v0[4], v1[4], v2[4];
+        if (!(px2_issued && lq_take<4>(px2, tag, v0, v1, v2)) && !lq_gather<4>(LQ, LQ_X2 + tid, NTH, tag, v0, v1, v2, failflag)) S.fail = 1;
+        TS(7)
 #pragma unroll
-      for (int net = 0; net < 3; ++net)
+        for (int s = 0; s < MB; ++s) { q[0][s] = w2[0] * v0[s]; q[1][s] = w2[1] * v1[s]; q[2][s] = w2[2] * v2[s]; }
 #pragma unroll
-        for (int s = 0; s < MB; ++s) q[net][s] = w2[net] * S.x2[net][s][k];
+        for (int j = 0; j < 4; ++j) { (&S.x2[0][0][0])[tid + NTH * j] = v0[j]; (&S.x2[1][0][0])[tid + NTH * j] = v1[j]; (&S.x2[2][0][0])[tid + NTH * j] = v2[j]; }
+      }
+      // (no barrier here: the one that stood between the S.x2 stores and their read-back also kept the S.fpart stores below behind forward L1's
+      // readers of S.fpart - the barrier in front of phase C does that - and the S.x2 stores in front of their readers, which all sit behind
+      // the barrier that follows the S.fpart stores)
 #pragma unroll
       for (int net = 0; net < 3; ++net)
 #pragma unroll
@@ -1054,50 +1064,69 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     }
     SDX_LDS_BARRIER();   // LDS traffic only: the column view's loads stay in flight (a __syncthreads() would wait for them)
     TS(12)
-    // backward through the heads: lane (column k, row half) forms its part of dX3[.][k], the halves meet in LDS; elu' applied here
+    refresh();   // (c2n / c2c and the addresses formed from them are derived HERE: formed in front of the head forward they were spilled across it)
+    // backward through the heads: lane (column k = c2n, row half c2c) forms its part of dX3[.][k]; the two halves of a column are lanes l and
+    // l ^ 32 of ONE wave and meet through v_permlane32_swap, elu' is applied in both lanes, and backward L2's products are fed from these
+    // registers.  One code path for both halves: rows 13 c2c + j, j < 13 - the upper half's j = 10, 11 are the two value heads (a1, a2) and
+    // S.dmu[.][23..25] are zeros (written with the rest of the row), so its a0 takes three exact zeros instead of a branch that every wave
+    // would run both sides of.
+    // (no barriers here: the two that let the halves meet in S.dy2 ordered nothing else - S.dmu / S.dv / S.x3 were published by the barriers
+    // of the loss phase, and the last readers of S.red / S.part, in the x3 shadow, are behind the barriers of the head forward.  The S.dy2
+    // stores below sit in front of block_sum's barriers, their readers - the Gram of dY2, dyown[.][.][6], the next step's Adam of layer 2 -
+    // behind them.)
+    float d2[3][MB];
     {
-      const int k = c2n;
+      const int k = c2n, jr = 13 * c2c;
       float a0[MB], a1[MB], a2[MB];
 #pragma unroll
-      for (int s = 0; s < MB; ++s) { a0[s] = 0.0f; a1[s] = 0.0f; a2[s] = 0.0f; }
-      if (c2c == 0) {
+      for (int s = 0; s < MB; ++s) a0[s] = 0.0f;
 #pragma unroll
-        for (int j = 0; j < 13; ++j)
+      for (int j = 0; j < 13; ++j)
 #pragma unroll
-          for (int s = 0; s < MB; ++s) a0[s] += S.dmu[s][j] * wc[j];
-      } else {
+        for (int s = 0; s < MB; ++s) a0[s] += S.dmu[s][jr + j] * wc[j];
 #pragma unroll
-        for (int j = 0; j < A - 13; ++j)
-#pragma unroll
-          for (int s = 0; s < MB; ++s) a0[s] += S.dmu[s][13 + j] * wc[j];
-#pragma unroll
-        for (int s = 0; s < MB; ++s) {
-          a1[s] = S.dv[0][s] * wc[A - 13]; a2[s] = S.dv[1][s] * wc[A - 12];
-          S.dy2[0][s][k] = a0[s];
-          S.dy2[1][s][k] = a1[s] * elu_g(S.x3[1][s][k]);
-          S.dy2[2][s][k] = a2[s] * elu_g(S.x3[2][s][k]);
-        }
+      for (int s = 0; s < MB; ++s) {
+        a1[s] = c2c ? S.dv[0][s] * wc[A - 13] : 0.0f; a2[s] = c2c ? S.dv[1][s] * wc[A - 12] : 0.0f;
+        d2[0][s] = pair_sum(a0[s]) * elu_g(S.x3[0][s][k]);
+        d2[1][s] = pair_sum(a1[s]) * elu_g(S.x3[1][s][k]);
+        d2[2][s] = pair_sum(a2[s]) * elu_g(S.x3[2][s][k]);
       }
-      __syncthreads();
-      if (c2c == 0) {
-#pragma unroll
-        for (int s = 0; s < MB; ++s) S.dy2[0][s][k] = (S.dy2[0][s][k] + a0[s]) * elu_g(S.x3[0][s][k]);
-      }
-      __syncthreads();
     }
     TS(13)
     // backward L2 with the column copy: dY1[net][s][2g+c] = (sum_n dY2[net][s][n] W2[n][2g+c]) * elu'(x2[net][s][2g+c])
     {
-      float p[24];
+      // Lane half c2c holds column 2g + c2c only, so the butterfly runs over 12 values per lane, not 24 of which half are zeros: a 16-lane
+      // DPP row lies inside one half, and rows 2 c2c, 2 c2c + 1 of every wave are summed for column c.  A DPP row still holds sixteen
+      // consecutive rows n of the column in lane order, and the sixteen row sums are still added in ascending n: the sums of the
+      // 24-wide reduction over (column = tid >> 8, row = tid & 255), bit for bit.
+      float p[12];
 #pragma unroll
       for (int net = 0; net < 3; ++net)
 #pragma unroll
-        for (int s = 0; s < MB; ++s) {
-          const float v = S.dy2[net][s][c2n] * c2[net];
-          p[(net * MB + s) * 2 + 0] = c2c == 0 ? v : 0.0f;
-          p[(net * MB + s) * 2 + 1] = c2c == 1 ? v : 0.0f;
+        for (int s = 0; s < MB; ++s) p[net * MB + s] = d2[net][s] * c2[net];
+      // each column's dY2 is stored once, behind the products: lane half c2c stores samples 2 c2c, 2 c2c + 1
+#pragma unroll
+      for (int net = 0; net < 3; ++net)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          float lo = d2[net][i], hi = d2[net][2 + i];
+          asm volatile("" : "+v"(lo), "+v"(hi));   // (a select of two elements of d2 becomes d2[2 c2c + i]: the array would live in scratch)
+          S.dy2[net][2 * c2c + i][c2n] = c2c ? hi : lo;
         }
-      block_sum<24>(S, p, S.part, tid, wave, lane);
+      {
+        float u2[3];
+        row_butterfly<12>(p, u2, lane);
+        rows_store<3>(S, u2, 0, wave, lane);
+      }
+      SDX_LDS_BARRIER();
+      if (tid < 24) {   // (net MB + s, c)
+        const int i = tid >> 1, c = tid & 1;
+        float t = 0.0f;
+#pragma unroll
+        for (int w = 0; w < NWV; ++w) { t += S.red[4 * w + 2 * c][i]; t += S.red[4 * w + 2 * c + 1][i]; }   // rows 16 j .. 16 j + 15 of the column, j ascending
+        S.part[tid] = t;
+      }
+      SDX_LDS_BARRIER();
       if (tid < MB * 2) {   // S.part: [(net MB + s) 2 + c]
         const int s = tid / 2, c = tid % 2;
         float v[3];
@@ -1198,23 +1227,26 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     refresh();
     // ================================================================== phase E: gather dY1, backward L1
     {
-      float v0[4], v1[4], v2[4];
-      if (!(pdy1_issued && lq_take<4>(pdy1, tag, v0, v1, v2)) && !lq_gather<4>(LQ, LQ_DY1 + tid, NTH, tag, v0, v1, v2, failflag)) S.fail = 1;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { (&S.dy1[0][0][0])[tid + NTH * j] = v0[j]; (&S.dy1[1][0][0])[tid + NTH * j] = v1[j]; (&S.dy1[2][0][0])[tid + NTH * j] = v2[j]; }
-    }
-    TS(16)
-    __syncthreads();
-    {
+      // Word tid + NTH j is (sample j, unit tid), and row tid of the column copy is this lane's: the products of backward L1 are formed from
+      // the gathered registers; the S.dy1 image (Gram of dY1, the next step's Adam of layer 1) is stored behind them.
       float p[48];
+      {
+        float v0[4], v1[4], v2[4];
+        if (!(pdy1_issued && lq_take<4>(pdy1, tag, v0, v1, v2)) && !lq_gather<4>(LQ, LQ_DY1 + tid, NTH, tag, v0, v1, v2, failflag)) S.fail = 1;
+        TS(16)
 #pragma unroll
-      for (int net = 0; net < 3; ++net)
+        for (int s = 0; s < MB; ++s)
 #pragma unroll
-        for (int s = 0; s < MB; ++s) {
-          const float d = S.dy1[net][s][tid];
+          for (int c = 0; c < 4; ++c) {
+            p[(0 * MB + s) * 4 + c] = v0[s] * c1[0][c]; p[(1 * MB + s) * 4 + c] = v1[s] * c1[1][c]; p[(2 * MB + s) * 4 + c] = v2[s] * c1[2][c];
+          }
 #pragma unroll
-          for (int c = 0; c < 4; ++c) p[(net * MB + s) * 4 + c] = d * c1[net][c];
-        }
+        for (int j = 0; j < 4; ++j) { (&S.dy1[0][0][0])[tid + NTH * j] = v0[j]; (&S.dy1[1][0][0])[tid + NTH * j] = v1[j]; (&S.dy1[2][0][0])[tid + NTH * j] = v2[j]; }
+      }
+      // (no barrier here on the epoch's chain: the one that stood between the S.dy1 stores and their read-back also kept block_sum's stores to
+      // S.red / S.part behind the dY1 shadow's readers of both - the LDS barrier that closes that shadow does that - and the S.dy1 stores in
+      // front of the Gram of dY1, which sits behind block_sum's barriers.  The one-minibatch instantiation has no such shadow: it keeps it.)
+      if constexpr (SINGLE) __syncthreads();
       block_sum<48>(S, p, S.part, tid, wave, lane);
       if (tid < MB * 4) {   // S.part: [(net MB + s) 4 + c]
         const int s = tid / 4, c = tid % 4;
