@@ -44,6 +44,7 @@ extern "C" {
 #define SDX_BODIES 165      /* 24 hand links + one body per other actor                                      */
 #define SDX_ACTOR_BRICK0 9  /* first brick actor inside an env                                               */
 #define SDX_BODY_BRICK0 32  /* first brick rigid body inside an env                                          */
+#define SDX_ACTOR_PLATE (SDX_ACTORS - 1) /* the base plate, the last actor of an env                            */
 #define SDX_NUM_OBS 396     /* 132 x 3 stacked frames (GS:207-209)                                           */
 #define SDX_NUM_STATES 564  /* 188 x 3 (GS:204-210)                                                          */
 #define SDX_NUM_ACTIONS 23  /* GS:211                                                                        */
@@ -68,6 +69,9 @@ typedef enum {
 } sdx_status;
 
 typedef enum { SDX_F32 = 0, SDX_I64 = 1, SDX_I32 = 2, SDX_U8 = 3, SDX_F64 = 4, SDX_I16 = 5 } sdx_dtype;
+
+/* values of sdx_scene_desc.task_kind (documented at the field) */
+typedef enum { SDX_TASK_GRASP = 0, SDX_TASK_ORIENT = 1, SDX_TASK_INSERT = 2, SDX_TASK_SEARCH = 3 } sdx_task_kind;
 
 /* Tensor ids for sdx_tensor().  Shapes use N = num_envs. */
 typedef enum {
@@ -244,11 +248,11 @@ typedef struct {
   float grasp_tvalue_gate;             /* BlockAssemblyGraspSim harvests a terminal state only when its transition value exceeds this: 0.8 (GS:1406) */
   float orient_tvalue_gate;            /* BlockAssemblyOrient binarises its transition value at this threshold before anything reads it: 0.99
                                         * (OR:1203); a chain run with an early, not yet confident T-value may lower it (say so when you do) */
-  /* which task's per-step tensor code the pre/post-physics kernels run: 0 = BlockAssemblyGraspSim (GS),
-   * 1 = BlockAssemblyOrient (OR = tasks/block_assembly/allegro_hand_block_assembly_orient.py; targets/IK OR:1720-1778),
-   * 2 = BlockAssemblyInsertSim (IS; position action + fixed wrist orientation IS:1526-1572, 75-number observation IS:1280-1298,
+  /* which task's per-step tensor code the pre/post-physics kernels run (sdx_task_kind): SDX_TASK_GRASP = 0 = BlockAssemblyGraspSim (GS),
+   * SDX_TASK_ORIENT = 1 = BlockAssemblyOrient (OR = tasks/block_assembly/allegro_hand_block_assembly_orient.py; targets/IK OR:1720-1778),
+   * SDX_TASK_INSERT = 2 = BlockAssemblyInsertSim (IS; position action + fixed wrist orientation IS:1526-1572, 75-number observation IS:1280-1298,
    *     insertion reward IS:1640-1695, reset from harvested grasp states IS:1416-1494),
-   * 3 = BlockAssemblySearch (SE; tracking IK 0.24 above the target SE:1565-1575, 62-number observation SE:1220-1230, its own asymmetric
+   * SDX_TASK_SEARCH = 3 = BlockAssemblySearch (SE; tracking IK 0.24 above the target SE:1565-1575, 62-number observation SE:1220-1230, its own asymmetric
    *     state SE:1168-1218, reward SE:1660-1711, reset with 60 settling steps and a segmentation render SE:1274-1538) */
   int32_t task_kind;
   float target_euler[3];               /* Orient: fixed wrist orientation of the tracking IK, OR:477 */

@@ -11,6 +11,8 @@ SDX_ABI_VERSION = 8
 NLINK, NDOF, MAX_RBOX, NBRICK, NFREE, NBRICK_TYPES, MAX_STATIC = 24, 23, 40, 132, 72, 8, 8
 MAX_STATIC_TAB, MAX_STATIC_SUB, MAX_SUB, MAX_SUB_HOLLOW = 10, 112, 2, 8
 ACTORS, BODIES, ACTOR_BRICK0, BODY_BRICK0 = 142, 165, 9, 32
+ACTOR_PLATE = ACTORS - 1      # SDX_ACTOR_PLATE
+TASK_GRASP, TASK_ORIENT, TASK_INSERT, TASK_SEARCH = 0, 1, 2, 3    # sdx_task_kind (sdx_scene_desc.task_kind)
 NUM_OBS, NUM_STATES, NUM_ACTIONS, OBS_FRAME, STATE_FRAME = 396, 564, 23, 132, 188
 HARVEST_SLOTS = 5001      # SDX_HARVEST_SLOTS
 TV_PARAMS = 42562

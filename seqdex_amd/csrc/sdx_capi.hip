@@ -37,6 +37,22 @@ struct sdx_sim {
 
 static thread_local std::string g_create_err = "";
 
+// what the task kind decides about the buffers: the row width of obs / obs_c, and the length of the pile ring per brick-type group
+static int task_obs_width(int task_kind) {
+  switch (task_kind) {
+    case SDX_TASK_ORIENT: case SDX_TASK_SEARCH: return 186;   // 62 x 3, only the first 62 are ever written (OR:191-207)
+    case SDX_TASK_INSERT: return 75;                          // one frame (IS:172)
+    default: return SDX_NUM_OBS;
+  }
+}
+static int task_pile_slots(int task_kind) {   // Orient and Search harvest piles
+  if (task_kind != SDX_TASK_ORIENT && task_kind != SDX_TASK_SEARCH) return 1;
+  // SDX_PILE_SLOTS=10000: the reference's ring length (OR:1485; 549 MB of the 288 GB); default SDX_PILE_HARVEST_SLOTS
+  const char* ps = getenv("SDX_PILE_SLOTS");
+  const long v = ps ? atol(ps) : 0;
+  return v >= 16 && v <= 10000 ? (int)v : SDX_PILE_HARVEST_SLOTS;
+}
+
 #define HIPCHK(h, call)                                                                              \
   do {                                                                                               \
     hipError_t _e = (call);                                                                          \
@@ -252,7 +268,7 @@ extern "C" int sdx_create(const sdx_scene_desc* scene, int32_t num_envs, int32_t
   B.N = N;
   B.task_kind = scene->task_kind;
   B.orient_gate = scene->orient_tvalue_gate;
-  B.obs_w = (scene->task_kind == 1 || scene->task_kind == 3) ? 186 : (scene->task_kind == 2 ? 75 : SDX_NUM_OBS);
+  B.obs_w = task_obs_width(scene->task_kind);
   B.K = 1;
   B.seed = seed;
 #define ALLOC(field, count) if ((rc = dalloc(h, &B.field, (size_t)(count))) != SDX_OK) { g_create_err = h->err; sdx_destroy(h); return rc; }
@@ -302,17 +318,12 @@ extern "C" int sdx_create(const sdx_scene_desc* scene, int32_t num_envs, int32_t
   ALLOC(tv_count, 2);
   ALLOC(tv_key, (size_t)2 * SDX_TV_LOG_SLOTS);
   ALLOC(harvest_key, (size_t)8 * SDX_HARVEST_SLOTS);
-  B.pile_slots = (scene->task_kind == 1 || scene->task_kind == 3) ? SDX_PILE_HARVEST_SLOTS : 1;   // Orient and Search harvest piles
-  if (B.pile_slots > 1) {   // SDX_PILE_SLOTS=10000: the reference's ring length (OR:1485; 549 MB of the 288 GB); default SDX_PILE_HARVEST_SLOTS
-    const char* ps = getenv("SDX_PILE_SLOTS");
-    const long v = ps ? atol(ps) : 0;
-    if (v >= 16 && v <= 10000) B.pile_slots = (int32_t)v;
-  }
+  B.pile_slots = task_pile_slots(scene->task_kind);
   ALLOC(pile_harvest, (size_t)8 * B.pile_slots * SDX_NBRICK * 13);
   ALLOC(pile_harvest_count, 8);
   ALLOC(pile_key, (size_t)8 * B.pile_slots);
   ALLOC(seg_stats, (size_t)N * 4);
-  ALLOC(seg_image, scene->task_kind == 3 ? (size_t)N * 128 * 128 : 1);
+  ALLOC(seg_image, scene->task_kind == SDX_TASK_SEARCH ? (size_t)N * 128 * 128 : 1);
   ALLOC(seg_pix, (size_t)N * 4);
   ALLOC(emergence, N);
   ALLOC(cstats, 4);
@@ -330,7 +341,7 @@ extern "C" int sdx_create(const sdx_scene_desc* scene, int32_t num_envs, int32_t
   ALLOC(dr_frame, 2);
   ALLOC(dr_draw, (size_t)N + 1);
   B.dr_on = nullptr;
-  if (scene->task_kind == 3) {
+  if (scene->task_kind == SDX_TASK_SEARCH) {
     ALLOC(tvt_buf, (size_t)N * 652);
     ALLOC(tvt_w, (size_t)1024 * 652 + 1024 + 512 * 1024 + 512 + 128 * 512 + 128 + 2 * 128 + 2);
     ALLOC(tvt_h, (size_t)N * (1024 + 512 + 128 + 4));
@@ -377,7 +388,7 @@ extern "C" int sdx_create(const sdx_scene_desc* scene, int32_t num_envs, int32_t
   set_tensor(h, SDX_T_TV_KEYS, B.tv_key, SDX_I64, {2, SDX_TV_LOG_SLOTS});
   set_tensor(h, SDX_T_HARVEST_KEYS, B.harvest_key, SDX_I64, {8, SDX_HARVEST_SLOTS});
   set_tensor(h, SDX_T_PILE_HARVEST_KEYS, B.pile_key, SDX_I64, {8, B.pile_slots});
-  if (scene->task_kind == 3) set_tensor(h, SDX_T_SEG_IMAGE, B.seg_image, SDX_I16, {N, 128, 128});
+  if (scene->task_kind == SDX_TASK_SEARCH) set_tensor(h, SDX_T_SEG_IMAGE, B.seg_image, SDX_I16, {N, 128, 128});
   else set_tensor(h, SDX_T_SEG_IMAGE, B.seg_image, SDX_I16, {1, 1, 1});   // placeholder: the camera belongs to Search
   set_tensor(h, SDX_T_SEG_PIXELS, B.seg_pix, SDX_F32, {N, 4});
   set_tensor(h, SDX_T_EMERGENCE, B.emergence, SDX_F32, {N});
@@ -397,7 +408,7 @@ extern "C" int sdx_create(const sdx_scene_desc* scene, int32_t num_envs, int32_t
   set_tensor(h, SDX_T_DR_GRAVITY, B.dr_grav, SDX_F32, {3});
   set_tensor(h, SDX_T_DR_FRAME, B.dr_frame, SDX_I64, {2});
   set_tensor(h, SDX_T_JACOBIAN, B.jac_full, SDX_F32, {N, SDX_NLINK - 1, 6, SDX_NDOF});
-  if (scene->task_kind == 3) set_tensor(h, SDX_T_TVALUE_OBS, B.tvt_buf, SDX_F32, {N, 652});
+  if (scene->task_kind == SDX_TASK_SEARCH) set_tensor(h, SDX_T_TVALUE_OBS, B.tvt_buf, SDX_F32, {N, 652});
   else set_tensor(h, SDX_T_TVALUE_OBS, B.seg_pix, SDX_F32, {1, 1});   // placeholder: the temporal buffer belongs to Search
 
   // ---- initial actor states (what create_actor's start poses give, GS:897-1000)
@@ -422,7 +433,7 @@ extern "C" int sdx_create(const sdx_scene_desc* scene, int32_t num_envs, int32_t
     memcpy(r + 26, scene->goal_reset_pos, 12);
     for (int s = 0; s < 6; ++s) memcpy(r + (3 + s) * 13, scene->static_actor_pos[s], 12);
     memcpy(r + SDX_ACTOR_BRICK0 * 13, pile0.data(), pile0.size() * 4);
-    memcpy(r + 141 * 13, scene->base_plate_pos, 12);
+    memcpy(r + SDX_ACTOR_PLATE * 13, scene->base_plate_pos, 12);
     float* b = &rbv[(size_t)e * SDX_BODIES * 13];
     for (int a = 1; a < SDX_ACTORS; ++a) memcpy(b + (SDX_NLINK + a - 1) * 13, r + a * 13, 13 * 4);
   }
@@ -502,7 +513,7 @@ extern "C" int sdx_set_tvalue_weights(sdx_handle h, const float* w, int32_t n) {
 
 extern "C" int sdx_set_retri_tvalue_weights(sdx_handle h, const float* w, int32_t n) {
   if (!h) return SDX_ERR_INVALID;
-  if (h->h_const.sc.task_kind != 3) { h->err = "sdx_set_retri_tvalue_weights: RetriGraspTValue belongs to BlockAssemblySearch (task_kind 3)"; return SDX_ERR_STATE; }
+  if (h->h_const.sc.task_kind != SDX_TASK_SEARCH) { h->err = "sdx_set_retri_tvalue_weights: RetriGraspTValue belongs to BlockAssemblySearch (task_kind 3)"; return SDX_ERR_STATE; }
   if (!w || n != SDX_RETRI_TV_PARAMS) { h->err = "sdx_set_retri_tvalue_weights: expected SDX_RETRI_TV_PARAMS floats"; return SDX_ERR_INVALID; }
   // device layout = host layout with the rows of W1 padded from 650 to 652 columns (16-byte rows for the float4 loads of the GEMM)
   std::vector<float> t((size_t)1024 * 652 + (n - (size_t)1024 * 650), 0.0f);
@@ -571,20 +582,30 @@ extern "C" int sdx_compute_observations(sdx_handle h, void* stream) {
   sdxk_post_physics(h->d_const, &h->buf, 0, (hipStream_t)stream);
   return check_launch(h, "sdx_compute_observations");
 }
+// The shared opening of Orient's and Search's reset events: the reset flags are read on the host (as reset_buf.nonzero() does), with
+// progress_buf[0] in the same round trip when `progress0` is given; when some env resets, *mask holds the flags as 0 / 1 and its
+// device copy is h->orient_mask; when none does, *mask comes back empty.
+static int reset_mask_from_flags(sdx_handle h, hipStream_t st, std::vector<uint8_t>* mask, int64_t* progress0) {
+  const int N = h->buf.N;
+  std::vector<int64_t> flags(N);
+  HIPCHK(h, hipMemcpyAsync(flags.data(), h->buf.reset, sizeof(int64_t) * N, hipMemcpyDeviceToHost, st));
+  if (progress0) HIPCHK(h, hipMemcpyAsync(progress0, h->buf.progress, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(h, hipStreamSynchronize(st));
+  mask->assign(N, 0);
+  int any = 0;
+  for (int i = 0; i < N; ++i) { (*mask)[i] = flags[i] != 0; any |= (*mask)[i]; }
+  if (!any) { mask->clear(); return SDX_OK; }
+  if (!h->orient_mask) { HIPCHK(h, hipMalloc((void**)&h->orient_mask, N)); h->allocs.push_back(h->orient_mask); }
+  HIPCHK(h, hipMemcpyAsync(h->orient_mask, mask->data(), N, hipMemcpyHostToDevice, st));
+  return SDX_OK;
+}
 // BlockAssemblyOrient reset (OR:1390-1695).  Like the reference (reset_buf.nonzero()) this reads the reset flags on the host; a reset
 // event costs 50 (only when steps have been taken) + 2 + 1 + 50 simulator steps of ALL envs, during which the resetting envs' arms
 // are scripted by the tracking IK.  The shipped task only resets on time-out, so all envs reset together every episodeLength steps.
 static int orient_reset_if_needed(sdx_handle h, hipStream_t st) {
-  const int N = h->buf.N;
-  std::vector<int64_t> flags(N);
-  HIPCHK(h, hipMemcpyAsync(flags.data(), h->buf.reset, sizeof(int64_t) * N, hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipStreamSynchronize(st));
-  std::vector<uint8_t> mask(N);
-  int any = 0;
-  for (int i = 0; i < N; ++i) { mask[i] = flags[i] != 0; any |= mask[i]; }
-  if (!any) return SDX_OK;
-  if (!h->orient_mask) { HIPCHK(h, hipMalloc((void**)&h->orient_mask, N)); h->allocs.push_back(h->orient_mask); }
-  HIPCHK(h, hipMemcpyAsync(h->orient_mask, mask.data(), N, hipMemcpyHostToDevice, st));
+  std::vector<uint8_t> mask;
+  const int rc = reset_mask_from_flags(h, st, &mask, nullptr);
+  if (rc != SDX_OK || mask.empty()) return rc;
   uint32_t steps = 0;
   HIPCHK(h, hipMemcpyAsync(&steps, h->buf.step_count, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIPCHK(h, hipStreamSynchronize(st));
@@ -607,17 +628,9 @@ extern "C" void sdxk_search_set_hand(const SdxConst*, const SdxBuf*, const uint8
 // (emergence bookkeeping), hand to the prepare pose.  *progress0 = progress_buf[0] before this step (the end-of-episode render keys
 // on it, SE:992).
 static int search_reset_if_needed(sdx_handle h, hipStream_t st, int64_t* progress0) {
-  const int N = h->buf.N;
-  std::vector<int64_t> flags(N);
-  HIPCHK(h, hipMemcpyAsync(flags.data(), h->buf.reset, sizeof(int64_t) * N, hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipMemcpyAsync(progress0, h->buf.progress, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(h, hipStreamSynchronize(st));
-  std::vector<uint8_t> mask(N);
-  int any = 0;
-  for (int i = 0; i < N; ++i) { mask[i] = flags[i] != 0; any |= mask[i]; }
-  if (!any) return SDX_OK;
-  if (!h->orient_mask) { HIPCHK(h, hipMalloc((void**)&h->orient_mask, N)); h->allocs.push_back(h->orient_mask); }
-  HIPCHK(h, hipMemcpyAsync(h->orient_mask, mask.data(), N, hipMemcpyHostToDevice, st));
+  std::vector<uint8_t> mask;
+  const int rc = reset_mask_from_flags(h, st, &mask, progress0);
+  if (rc != SDX_OK || mask.empty()) return rc;
   sdxk_pre_physics(h->d_const, &h->buf, nullptr, h->orient_mask, nullptr, 2, st);      // outcome, harvest, lattice + noise, target drop, default pose
   for (int i = 0; i < 60; ++i) sdxk_physics(h->d_const, &h->buf, st);                  // SE:1437-1439
   sdxk_seg_camera(h->d_const, &h->buf, st);                                            // SE:1444-1455
@@ -630,7 +643,7 @@ extern "C" int sdx_step(sdx_handle h, const float* actions_dev, void* stream) {
   if (!h || !actions_dev) return SDX_ERR_INVALID;
   hipStream_t st = (hipStream_t)stream;
   if (h->buf.dr_on) dr_sample(h, 0, st);   // before any reset physics of this step, Orient's / Search's settling launches included
-  if (h->h_const.sc.task_kind == 3) {
+  if (h->h_const.sc.task_kind == SDX_TASK_SEARCH) {
     int64_t p0 = 0;
     const int rc = search_reset_if_needed(h, st, &p0);
     if (rc != SDX_OK) return rc;
@@ -644,7 +657,7 @@ extern "C" int sdx_step(sdx_handle h, const float* actions_dev, void* stream) {
     sdxk_post_physics(h->d_const, &h->buf, 1, st);
     return check_launch(h, "sdx_step");
   }
-  if (h->h_const.sc.task_kind == 1) {
+  if (h->h_const.sc.task_kind == SDX_TASK_ORIENT) {
     const int rc = orient_reset_if_needed(h, st);
     if (rc != SDX_OK) return rc;
     sdxk_pre_physics(h->d_const, &h->buf, actions_dev, nullptr, nullptr, 4, st);
@@ -673,7 +686,7 @@ extern "C" int sdx_reset_idx(sdx_handle h, const uint8_t* env_mask_dev, const in
 }
 extern "C" int sdx_render_segmentation(sdx_handle h, void* stream) {
   if (!h) return SDX_ERR_INVALID;
-  if (h->h_const.sc.task_kind != 3) { h->err = "sdx_render_segmentation: the segmentation camera belongs to BlockAssemblySearch (task_kind 3)"; return SDX_ERR_STATE; }
+  if (h->h_const.sc.task_kind != SDX_TASK_SEARCH) { h->err = "sdx_render_segmentation: the segmentation camera belongs to BlockAssemblySearch (task_kind 3)"; return SDX_ERR_STATE; }
   sdxk_seg_camera(h->d_const, &h->buf, (hipStream_t)stream);
   return check_launch(h, "sdx_render_segmentation");
 }

@@ -163,7 +163,7 @@ class Scene:
         d.orient_tvalue_gate = 0.99                        # OR:1203
         d.robot_angular_damping = 0.01                     # GS:546 (asset_options.angular_damping of the arm-hand asset)
         d.grasp_tvalue_gate = 0.8                          # GS:1406
-        d.task_kind = 0                                   # BlockAssemblyGraspSim; 1 = BlockAssemblyOrient (per-step tensor code only)
+        d.task_kind = _abi.TASK_GRASP                     # the tasks of seqdex_amd/tasks/ override it with their TASK_KIND
         d.target_euler[:] = [0.0, 3.1415, 1.571]          # OR:477
         d.seg_mass_scale = 1.0                            # GS:980-981 (x1); Orient x50 (OR:977)
         d.static_var_slot = -1
@@ -178,7 +178,7 @@ class Scene:
                 getattr(d, k_)[:] = list(v)
             else:
                 setattr(d, k_, v)
-        if d.task_kind == 2:
+        if d.task_kind == _abi.TASK_INSERT:
             self._place_insert_plates(d, overrides.get("seg_hollow", 1))
         return d
 

@@ -12,7 +12,7 @@ from ..sim import SdxSim
 
 
 class BlockAssemblyGraspSim:
-    TASK_KIND = 0                     # sdx_scene_desc.task_kind
+    TASK_KIND = _abi.TASK_GRASP                     # sdx_scene_desc.task_kind
     ONE_FRAME_NUM_OBS = _abi.OBS_FRAME
     STACK_OBS = 3                     # GS:189
 

@@ -27,7 +27,7 @@ from .block_assembly_grasp_sim import BlockAssemblyGraspSim
 
 
 class BlockAssemblyInsertSim(BlockAssemblyGraspSim):
-    TASK_KIND = 2
+    TASK_KIND = _abi.TASK_INSERT
     ONE_FRAME_NUM_OBS = 75                                                     # IS:175
     STACK_OBS = 1                                                              # IS:172
 

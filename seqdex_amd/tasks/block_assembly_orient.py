@@ -20,7 +20,7 @@ from .block_assembly_grasp_sim import BlockAssemblyGraspSim
 
 
 class BlockAssemblyOrient(BlockAssemblyGraspSim):
-    TASK_KIND = 1
+    TASK_KIND = _abi.TASK_ORIENT
     ONE_FRAME_NUM_OBS = 62                                                     # OR:191-192
 
     def __init__(self, *args, tvalue_gate=0.99, **kw):

@@ -18,11 +18,12 @@ reference, where it does not enter the reward either).  Not reproduced: teleoper
 perturbations, cv2 debug windows, the hand states saved next to the piles (SE:1325).  The pixel counts come from box geometry, not
 from the studded meshes: thresholds tuned on Isaac Gym's renderer are only approximately meaningful (parity unpinned).
 """
+from .. import _abi
 from .block_assembly_orient import BlockAssemblyOrient
 
 
 class BlockAssemblySearch(BlockAssemblyOrient):
-    TASK_KIND = 3
+    TASK_KIND = _abi.TASK_SEARCH
     ONE_FRAME_NUM_OBS = 62                                                     # SE:155
 
     def _scene_overrides(self, scene):

@@ -101,6 +101,15 @@ def test_orient_reward_golden(golden_dir):
         s.close()
 
 
+def test_orient_pile_harvest_on_reset(scene):
+    """OR:1463-1488 through one masked reset_idx with the accept rule's inputs set by hand: the accepted masked envs (hand withdrawn,
+    target brick in the bin half, accepting T-value) append their 132 brick rows, bit for bit, and the key (step << 24 | env) to the
+    ring of their brick-type group; every masked env logs its camera-frame quaternion as a T-value success or failure; unmasked
+    envs are untouched."""
+    from tests.helpers.pile_harvest import check_pile_harvest_on_reset
+    check_pile_harvest_on_reset(1, scene)
+
+
 def test_orient_task_end_to_end_with_scripted_reset(scene):
     """BlockAssemblyOrient through the VecTask surface for two episodes (episodeLength 75): every env times out together, the reset
     event runs its scripted pre-grasp (50 + 2 + 1 + 50 simulator steps with the tracking IK), and afterwards the hand base hovers

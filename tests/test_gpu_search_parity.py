@@ -155,6 +155,15 @@ def test_search_reward_golden(golden_dir):
         s.close()
 
 
+def test_search_pile_harvest_on_reset(scene):
+    """SE:1289-1343,1367-1421 through one masked reset_idx with the pixel counts set by hand: envs above their brick type's pixel
+    threshold are successes (success_buf, T-value datasets) and append their pile, bit for bit, to the ring of their group; then the
+    lattice comes back with +-0.02 of x / y noise on the free bricks, the target brick hangs at z = 0.9 on the line one draw moves
+    it along, and the hand is parked at the default pose."""
+    from tests.helpers.pile_harvest import check_pile_harvest_on_reset
+    check_pile_harvest_on_reset(3, scene, max_episode_length=75.0, act_moving_average=0.6, target_euler=[0.0, 3.14, 1.57])
+
+
 def test_search_task_end_to_end(scene):
     """BlockAssemblySearch through the VecTask surface: the first step drops the pile (60 settling steps) and renders; the last step of
     the episode parks the hand and renders again; the reset event that follows labels every env success / failure by its pixel count

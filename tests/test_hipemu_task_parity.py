@@ -125,6 +125,19 @@ def test_segmentation_camera_matches_numpy_ray_caster(scene):
     GS.test_segmentation_camera_matches_numpy_ray_caster(scene)
 
 
+# ---------------------------------------------------------------- the reset-time branches: pile harvests, InsertSim's reset tail
+def test_orient_pile_harvest_on_reset(scene):
+    GO.test_orient_pile_harvest_on_reset(scene)
+
+
+def test_search_pile_harvest_on_reset(scene):
+    GS.test_search_pile_harvest_on_reset(scene)
+
+
+def test_insert_reset_from_grasp_states_and_success_flag():
+    GI.test_insert_reset_from_grasp_states_and_success_flag()
+
+
 # ---------------------------------------------------------------- the full-size observation checks of the other three tasks (numpy oracle)
 def test_orient_1024_observations_against_oracle(scene):
     import test_gpu_fullsize_tasks as GF
