@@ -131,7 +131,7 @@ typedef enum {
                             *                    (body pairs > 1535, candidate box pairs > 16384, surviving box pairs > 3072: the excess was not tested, its contacts are MISSING) - like [1] it
                             *                    must stay 0, the full-size tests assert it and bench.py flags it */
   SDX_T_WARM_COUNT = 44,   /* i32 [N]           contacts in each env's warm-start cache (scene.warm_start); the engine clears an
-                            *                    env's entry when it resets the env; a caller that teleports bodies by hand may zero it too */
+                            *                    env's entry when it resets the env; sdx_state_save / restore / clone (below) carry the cache with the state */
   SDX_T_CAM_ROT = 45,      /* f32 [N,4]         camera_view_segmentation_target_rot: the target brick's quaternion in the camera frame, the input of
                             *                    GraspInsertTValue (GS:1196-1201, OR:1201); written by sdx_compute_observations / sdx_post_physics */
   SDX_T_TV_KEYS = 46,      /* i64 [2,SDX_TV_LOG_SLOTS]  (step << 24 | env) of the append that filled each slot of the success / failure ring.  Ring
@@ -397,6 +397,42 @@ typedef struct {
 } sdx_view_desc;
 int sdx_render_view(sdx_handle h, const sdx_view_desc* view, const int32_t* env_ids_dev, int32_t n,
                     float* depth_out_dev, int16_t* label_out_dev, uint8_t* rgb_out_dev, void* stream);
+
+/* ---- Sim snapshots: save, restore and clone the complete state of envs on the device, so that a run continues
+ * from a restored or cloned state bit for bit (set_*_state_tensor_indexed / mj_copyData, for every buffer at once).
+ * A snapshot is `rows` rows of device memory; an ENV ROW holds every per-env buffer that a later call reads before it writes: the
+ * actor / DOF / body / contact / Jacobian states, targets, the stacked observation and state frames with their clamped copies, reward,
+ * reset / progress / randomize counters, actions, the init pose, success and T-value bookkeeping, the camera rows (Search: the
+ * segmentation image and the ten-frame T-value buffer too), the randomization rows SDX_T_DR_DOF / LINK / BRICK with the env's draw counter,
+ * and the warm-start cache (the count, and the first `count` keys and impulses; a count outside [0, 1536] is clamped).  The GLOBAL part,
+ * which only save_all / restore_all move: the step counter (it keys every reset draw and the ring keys), the double-buffered reset
+ * statistics and SDX_T_CONS_SUCCESSES, SDX_T_DR_GRAVITY, SDX_T_DR_FRAME and gravity's draw counter.
+ * NOT part of any snapshot: the logs (the harvest, pile and T-value rings with their counts and keys, SDX_T_CONTACT_STATS, SDX_T_DEBUG),
+ * the launch-order hints of k_physics, and configuration (loaded piles, T-value weights, the randomization descriptor and whether it is
+ * on).  A restore_all rewinds the step counter: ring rows appended afterwards can REPEAT the keys of rows appended before the restore.
+ * Env classes: a row may only be put into an env of the class it came from - env & 7 (the target brick), and additionally env % 3 for
+ * InsertSim (the base plate and the insertion site); the RNG keys stay with the destination env.  Each row records its source env.
+ * restore and clone never fault on a bad entry: they skip it and count it in sdx_state_stats - [0] env id or row index out of range
+ * (save counts these too), [1] class mismatch, [2] restore of a row that was never saved.
+ * Across handles: a snapshot remembers its layout (task kind, warm start on / off, observation width, varying base plate, bytes per row)
+ * and may be saved from / restored into any simulator with the same layout; another layout is SDX_ERR_INVALID.  restore_all also needs the
+ * same number of envs, and gives SDX_ERR_STATE when the snapshot's last save was not save_all.
+ * create, destroy and stats block; the others are stream-ordered with no host synchronisation, allocation or blocking copy (they may be
+ * captured); n == 0 is SDX_OK without a launch.  Id arrays are device i32 [n]. */
+typedef struct sdx_state* sdx_state_handle;
+int sdx_state_create(sdx_handle h, int32_t rows, sdx_state_handle* out);   /* blocking; rows >= 1 */
+int sdx_state_destroy(sdx_state_handle s);                                 /* blocking */
+/* env env_ids_dev[i] -> row rows_dev[i]; rows_dev NULL = row i.  Rows must be unique. */
+int sdx_state_save(sdx_handle h, sdx_state_handle s, const int32_t* env_ids_dev, const int32_t* rows_dev, int32_t n, void* stream);
+/* row rows_dev[i] -> env env_ids_dev[i]; rows_dev NULL = row i.  A row may be repeated (fan-out), envs must be unique. */
+int sdx_state_restore(sdx_handle h, sdx_state_handle s, const int32_t* rows_dev, const int32_t* env_ids_dev, int32_t n, void* stream);
+/* every env (row e = env e; needs rows >= N) plus the global part */
+int sdx_state_save_all(sdx_handle h, sdx_state_handle s, void* stream);
+int sdx_state_restore_all(sdx_handle h, sdx_state_handle s, void* stream);
+/* env src[i] -> env dst[i] inside one simulator.  A source may be repeated (fan-out); destination envs must be unique and none of them
+ * may also be a source. */
+int sdx_state_clone(sdx_handle h, const int32_t* src_env_ids_dev, const int32_t* dst_env_ids_dev, int32_t n, void* stream);
+int sdx_state_stats(sdx_handle h, int32_t out[3]);                         /* blocking; counters since sdx_create */
 
 int sdx_num_envs(sdx_handle h);
 const char* sdx_last_error(sdx_handle h);   /* never NULL; h may be NULL for create-time errors */

@@ -104,6 +104,8 @@ SDX_EXPORTS = ["sdx_create", "sdx_destroy", "sdx_tensor", "sdx_load_initial_stat
                "sdx_step", "sdx_pre_physics", "sdx_simulate", "sdx_post_physics", "sdx_compute_observations",
                "sdx_reset_idx", "sdx_set_indexed", "sdx_refresh_kinematics", "sdx_render_segmentation", "sdx_num_envs", "sdx_last_error",
                "sdx_set_randomization", "sdx_render_view",
+               "sdx_state_create", "sdx_state_destroy", "sdx_state_save", "sdx_state_restore", "sdx_state_save_all", "sdx_state_restore_all",
+               "sdx_state_clone", "sdx_state_stats",
                "sdxp_create", "sdxp_destroy", "sdxp_tensor", "sdxp_param_count", "sdxp_act", "sdxp_store_rewards",
                "sdxp_finish_rollout", "sdxp_get_values", "sdxp_discount_values", "sdxp_prepare_dataset", "sdxp_update", "sdxp_update_impl", "sdxp_update_status", "sdxp_backward", "sdxp_apply", "sdxp_backward_factors",
                "sdxp_grads_from_factors", "sdxp_apply_factors", "sdxp_get_state", "sdxp_set_state", "sdxp_last_error",
@@ -137,6 +139,14 @@ def load_library():
     lib.sdx_set_indexed.argtypes = [vp, i32, vp, vp, i32, vp]
     lib.sdx_set_randomization.argtypes = [vp, vp, vp]
     lib.sdx_render_view.argtypes = [vp, C.POINTER(ViewDesc), vp, i32, vp, vp, vp, vp]
+    lib.sdx_state_create.argtypes = [vp, i32, C.POINTER(vp)]
+    lib.sdx_state_destroy.argtypes = [vp]
+    lib.sdx_state_save.argtypes = [vp, vp, vp, vp, i32, vp]
+    lib.sdx_state_restore.argtypes = [vp, vp, vp, vp, i32, vp]
+    lib.sdx_state_save_all.argtypes = [vp, vp, vp]
+    lib.sdx_state_restore_all.argtypes = [vp, vp, vp]
+    lib.sdx_state_clone.argtypes = [vp, vp, vp, i32, vp]
+    lib.sdx_state_stats.argtypes = [vp, i32p]
     lib.sdx_num_envs.argtypes = [vp]
     lib.sdx_last_error.argtypes = [vp]
     lib.sdx_last_error.restype = C.c_char_p

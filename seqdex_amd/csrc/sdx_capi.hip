@@ -10,6 +10,7 @@
 
 #include "sdx_common.h"
 #include "sdx_const_build.h"
+#include "sdx_state.h"
 
 extern "C" {
 void sdxk_pre_physics(const SdxConst*, const SdxBuf*, const float*, const uint8_t*, const int32_t*, int, hipStream_t);
@@ -32,6 +33,8 @@ struct sdx_sim {
   struct TensorInfo { void* ptr; int64_t shape[4]; int ndim; int dtype; } tinfo[SDX_T_COUNT];
   bool has_piles = false;
   sdx_dr_desc dr{};           // the randomization in force (meaningful while buf.dr_on != nullptr)
+  SdxStateTab st_tab{};       // what an env's state is (sdx_state.h); d_st_tab: its device copy
+  SdxStateTab* d_st_tab = nullptr;
   std::string err;
 };
 
@@ -219,6 +222,170 @@ __global__ __launch_bounds__(128) void k_dr_sample(const SdxConst* __restrict__ 
 static void dr_sample(sdx_sim* h, int first, hipStream_t st, const uint8_t* mask = nullptr) {
   hipLaunchKernelGGL(k_dr_gravity, dim3(1), dim3(256), 0, st, h->d_const, h->buf, h->dr, first, mask);
   hipLaunchKernelGGL(k_dr_sample, dim3(h->buf.N), dim3(128), 0, st, h->d_const, h->buf, h->dr, first, mask);
+}
+
+// ---------------------------------------------------------------- sim snapshots (include/seqdex.h sdx_state_*)
+// The segment table: every per-env buffer of SdxBuf that a later call reads before it writes.  This list is the one place that says what
+// an env's state is; the logs (harvest / pile / T-value rings with their counts and keys, cstats, dbg), the scheduling hints (order,
+// cost), scratch (cscratch, tvt_h, orient_mask) and configuration (piles, tv_w, tvt_w, the randomization descriptor, dr_on) are not in it.
+static int state_table_build(sdx_sim* h) {
+  SdxBuf& B = h->buf;
+  SdxStateTab& S = h->st_tab;
+  const sdx_scene_desc& sc = h->h_const.sc;
+  const int N = B.N;
+  const bool search = sc.task_kind == SDX_TASK_SEARCH, warm = sc.warm_start > 0.0f;
+  S.N = N;
+  S.var3 = (sc.static_var_slot >= 0 || sc.task_kind == SDX_TASK_INSERT) ? 1 : 0;   // the base plate / the insertion site depend on env % 3
+  S.row_bytes = 16;   // the row header: source env, warm count, SDX_ST_MAGIC, 0
+  S.wcount = B.wcount;
+  bool ok = true;
+#define SEG(field, per_env) ok = ok && sdx_state_add(&S, B.field, (size_t)(per_env) * sizeof(*B.field), (size_t)(per_env) * sizeof(*B.field), 0)
+  SEG(root, SDX_ACTORS * 13); SEG(dof, SDX_NDOF * 2); SEG(rb, SDX_BODIES * 13); SEG(contact, SDX_BODIES * 3);
+  SEG(jac, 42); SEG(jac_full, (SDX_NLINK - 1) * 6 * SDX_NDOF); SEG(targets, SDX_NDOF); SEG(prev_targets, SDX_NDOF);
+  SEG(obs, B.obs_w); SEG(states, SDX_NUM_STATES); SEG(obs_c, B.obs_w); SEG(states_c, SDX_NUM_STATES);
+  SEG(rew, 1); SEG(reset, 1); SEG(progress, 1); SEG(randomize, 1); SEG(actions, SDX_NDOF);
+  SEG(init_pos, 3); SEG(init_rot, 4); SEG(successes, 1); SEG(meta_rew, 1); SEG(finger_dist, 1); SEG(tvalue, 1);
+  SEG(arm_contacts, 6); SEG(student_obs, 30); SEG(success_buf, 1); SEG(pile_choice, 1); SEG(ncontacts, 1);
+  SEG(cam_rot, 4); SEG(insert_aux, 8); SEG(seg_stats, 4); SEG(seg_pix, 4); SEG(emergence, 1);
+  if (search) { SEG(seg_image, 128 * 128); SEG(tvt_buf, 652); }
+  SEG(dr_dof, 4 * SDX_NDOF); SEG(dr_link, 2 * SDX_NLINK); SEG(dr_brick, 2 * SDX_NFREE); SEG(dr_draw, 1);
+#undef SEG
+  if (warm) {   // wcount[e] travels in the row header; of the key row and the three impulse rows only the first wcount[e] entries are state
+    ok = ok && sdx_state_add(&S, B.wkey, (size_t)SDX_MAXC * 4, (size_t)SDX_MAXC * 4, 1);
+    for (int r = 0; r < 3; ++r) ok = ok && sdx_state_add(&S, B.wlam + (size_t)r * SDX_MAXC, (size_t)3 * SDX_MAXC * 4, (size_t)SDX_MAXC * 4, 1);
+  }
+  if (!ok) { h->err = "sdx_create: state segment table (a buffer is missing, misaligned or not a multiple of 4 bytes per env)"; return SDX_ERR_INVALID; }
+  S.nunits = (int32_t)(S.row_bytes / 16);
+  void* globs[SDX_ST_NGLOB] = {B.step_count, B.stat, B.cons, B.dr_grav, B.dr_frame, B.dr_draw + N};
+  const uint32_t gb[SDX_ST_NGLOB] = {4, 16, 4, 12, 16, 4};
+  for (int g = 0; g < SDX_ST_NGLOB; ++g) { S.glob[g] = (char*)globs[g]; S.glob_bytes[g] = gb[g]; }
+  std::vector<uint8_t> us((size_t)S.nunits, 255);
+  for (int i = 0; i < S.nseg; ++i) {
+    const uint32_t slot = ((S.seg[i].bytes + 15) & ~15u) + 16;
+    for (uint32_t u = S.seg[i].off / 16; u < (S.seg[i].off + slot) / 16; ++u) us[u] = (uint8_t)i;
+  }
+  uint8_t* d_us = nullptr;
+  int rc;
+  if ((rc = dalloc(h, &d_us, us.size())) != SDX_OK) return rc;
+  if ((rc = dalloc(h, &S.stats, 4)) != SDX_OK) return rc;
+  if ((rc = dalloc(h, &h->d_st_tab, 1)) != SDX_OK) return rc;
+  S.unit_seg = d_us;
+  HIPCHK(h, hipMemcpy(d_us, us.data(), us.size(), hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpy(h->d_st_tab, &S, sizeof(S), hipMemcpyHostToDevice));
+  return SDX_OK;
+}
+
+struct sdx_state {
+  int device = 0;
+  int32_t sig[5] = {0, 0, 0, 0, 0};   // layout signature: task kind, warm start on, obs_w, var3, row bytes
+  int32_t rows = 0;
+  int32_t full_n = -1;                // N of the simulator whose save_all was the last save, -1: the last save was not a save_all
+  char* d_rows = nullptr;
+  char* d_glob = nullptr;             // [SDX_ST_NGLOB x 16 bytes]
+};
+static void state_sig(const sdx_sim* h, int32_t sig[5]) {
+  sig[0] = h->h_const.sc.task_kind; sig[1] = h->h_const.sc.warm_start > 0.0f; sig[2] = h->buf.obs_w; sig[3] = h->st_tab.var3;
+  sig[4] = (int32_t)h->st_tab.row_bytes;
+}
+static bool state_sig_ok(sdx_sim* h, const sdx_state* s, const char* what) {
+  int32_t sig[5];
+  state_sig(h, sig);
+  if (memcmp(sig, s->sig, sizeof(sig)) == 0) return true;
+  char b[320];
+  snprintf(b, sizeof(b), "%s: the snapshot's layout (task kind %d, warm start %d, obs_w %d, varying base plate %d, %d bytes per row) is not this "
+           "simulator's (%d, %d, %d, %d, %d)", what, s->sig[0], s->sig[1], s->sig[2], s->sig[3], s->sig[4], sig[0], sig[1], sig[2], sig[3], sig[4]);
+  h->err = b;
+  return false;
+}
+static int check_launch(sdx_handle h, const char* what);
+
+extern "C" int sdx_state_create(sdx_handle h, int32_t rows, sdx_state_handle* out) {
+  if (!h) return SDX_ERR_INVALID;
+  if (!out || rows < 1) { h->err = "sdx_state_create: rows >= 1 and a non-NULL out"; return SDX_ERR_INVALID; }
+  HIPCHK(h, hipSetDevice(h->device));
+  sdx_state* s = new sdx_state();
+  s->device = h->device;
+  s->rows = rows;
+  state_sig(h, s->sig);
+  const size_t bytes = (size_t)rows * h->st_tab.row_bytes;
+  hipError_t e = hipMalloc((void**)&s->d_rows, bytes);
+  if (e == hipSuccess) e = hipMalloc((void**)&s->d_glob, SDX_ST_NGLOB * 16);
+  if (e != hipSuccess) {
+    if (s->d_rows) (void)hipFree(s->d_rows);
+    delete s;
+    h->err = std::string("sdx_state_create: hipMalloc failed: ") + hipGetErrorString(e);
+    return SDX_ERR_NOMEM;
+  }
+  e = hipMemset(s->d_rows, 0, bytes);   // no row has been saved: header word 2 != SDX_ST_MAGIC
+  if (e == hipSuccess) e = hipMemset(s->d_glob, 0, SDX_ST_NGLOB * 16);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    (void)hipFree(s->d_rows); (void)hipFree(s->d_glob);
+    delete s;
+    h->err = std::string("sdx_state_create: hipMemset failed: ") + hipGetErrorString(e);
+    return SDX_ERR_HIP;
+  }
+  *out = s;
+  return SDX_OK;
+}
+extern "C" int sdx_state_destroy(sdx_state_handle s) {
+  if (!s) return SDX_ERR_INVALID;
+  (void)hipSetDevice(s->device);
+  (void)hipDeviceSynchronize();
+  (void)hipFree(s->d_rows);
+  (void)hipFree(s->d_glob);
+  delete s;
+  return SDX_OK;
+}
+extern "C" int sdx_state_save(sdx_handle h, sdx_state_handle s, const int32_t* env_ids_dev, const int32_t* rows_dev, int32_t n, void* stream) {
+  if (!h) return SDX_ERR_INVALID;
+  if (!s || n < 0 || (n > 0 && !env_ids_dev)) { h->err = "sdx_state_save: snapshot / env_ids NULL or n < 0"; return SDX_ERR_INVALID; }
+  if (!state_sig_ok(h, s, "sdx_state_save")) return SDX_ERR_INVALID;
+  if (n == 0) return SDX_OK;
+  s->full_n = -1;
+  sdx_state_launch(h->d_st_tab, SDX_ST_SAVE, s->d_rows, s->rows, s->d_glob, env_ids_dev, rows_dev, n, 0, (hipStream_t)stream);
+  return check_launch(h, "sdx_state_save");
+}
+extern "C" int sdx_state_restore(sdx_handle h, sdx_state_handle s, const int32_t* rows_dev, const int32_t* env_ids_dev, int32_t n, void* stream) {
+  if (!h) return SDX_ERR_INVALID;
+  if (!s || n < 0 || (n > 0 && !env_ids_dev)) { h->err = "sdx_state_restore: snapshot / env_ids NULL or n < 0"; return SDX_ERR_INVALID; }
+  if (!state_sig_ok(h, s, "sdx_state_restore")) return SDX_ERR_INVALID;
+  if (n == 0) return SDX_OK;
+  sdx_state_launch(h->d_st_tab, SDX_ST_RESTORE, s->d_rows, s->rows, s->d_glob, rows_dev, env_ids_dev, n, 0, (hipStream_t)stream);
+  return check_launch(h, "sdx_state_restore");
+}
+extern "C" int sdx_state_save_all(sdx_handle h, sdx_state_handle s, void* stream) {
+  if (!h) return SDX_ERR_INVALID;
+  if (!s) { h->err = "sdx_state_save_all: snapshot NULL"; return SDX_ERR_INVALID; }
+  if (!state_sig_ok(h, s, "sdx_state_save_all")) return SDX_ERR_INVALID;
+  if (s->rows < h->buf.N) { h->err = "sdx_state_save_all: the snapshot has fewer rows than the simulator has envs"; return SDX_ERR_INVALID; }
+  s->full_n = h->buf.N;
+  sdx_state_launch(h->d_st_tab, SDX_ST_SAVE, s->d_rows, s->rows, s->d_glob, nullptr, nullptr, h->buf.N, 1, (hipStream_t)stream);
+  return check_launch(h, "sdx_state_save_all");
+}
+extern "C" int sdx_state_restore_all(sdx_handle h, sdx_state_handle s, void* stream) {
+  if (!h) return SDX_ERR_INVALID;
+  if (!s) { h->err = "sdx_state_restore_all: snapshot NULL"; return SDX_ERR_INVALID; }
+  if (!state_sig_ok(h, s, "sdx_state_restore_all")) return SDX_ERR_INVALID;
+  if (s->full_n < 0) { h->err = "sdx_state_restore_all: the snapshot's last save was not sdx_state_save_all (it holds no global state)"; return SDX_ERR_STATE; }
+  if (s->full_n != h->buf.N) { h->err = "sdx_state_restore_all: the snapshot was taken from a simulator with another number of envs"; return SDX_ERR_INVALID; }
+  sdx_state_launch(h->d_st_tab, SDX_ST_RESTORE, s->d_rows, s->rows, s->d_glob, nullptr, nullptr, h->buf.N, 1, (hipStream_t)stream);
+  return check_launch(h, "sdx_state_restore_all");
+}
+extern "C" int sdx_state_clone(sdx_handle h, const int32_t* src_env_ids_dev, const int32_t* dst_env_ids_dev, int32_t n, void* stream) {
+  if (!h) return SDX_ERR_INVALID;
+  if (n < 0 || (n > 0 && (!src_env_ids_dev || !dst_env_ids_dev))) { h->err = "sdx_state_clone: env ids NULL or n < 0"; return SDX_ERR_INVALID; }
+  if (n == 0) return SDX_OK;
+  sdx_state_launch(h->d_st_tab, SDX_ST_CLONE, nullptr, 0, nullptr, src_env_ids_dev, dst_env_ids_dev, n, 0, (hipStream_t)stream);
+  return check_launch(h, "sdx_state_clone");
+}
+extern "C" int sdx_state_stats(sdx_handle h, int32_t out[3]) {
+  if (!h) return SDX_ERR_INVALID;
+  if (!out) { h->err = "sdx_state_stats: out NULL"; return SDX_ERR_INVALID; }
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipDeviceSynchronize());
+  HIPCHK(h, hipMemcpy(out, h->st_tab.stats, 3 * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return SDX_OK;
 }
 
 extern "C" int sdx_create(const sdx_scene_desc* scene, int32_t num_envs, int32_t device, uint64_t seed, sdx_handle* out) {
@@ -448,6 +615,7 @@ extern "C" int sdx_create(const sdx_scene_desc* scene, int32_t num_envs, int32_t
     std::vector<int64_t> ones(N, 1);  // reset_buf = ONES: every env resets on the first step (BT:63)
     HIPCHK(h, hipMemcpy(B.reset, ones.data(), (size_t)N * 8, hipMemcpyHostToDevice));
   }
+  if ((rc = state_table_build(h)) != SDX_OK) { g_create_err = h->err; sdx_destroy(h); return rc; }
   hipLaunchKernelGGL(k_dr_defaults, dim3(N), dim3(128), 0, 0, h->d_const, B);   // the randomization rows hold the scene's values
   sdxk_kinematics(h->d_const, &h->buf, 0);  // first refresh (GS:243-246)
   HIPCHK(h, hipDeviceSynchronize());

@@ -37,6 +37,89 @@ class SdxError(RuntimeError):
     pass
 
 
+class SimState:
+    """Device memory for `rows` env states of one simulator layout (include/seqdex.h sdx_state_*): made by SdxSim.snapshot().  save() /
+    restore() are stream-ordered single launches; a run continues from a restored state bit for bit.  Not in a snapshot: the logs (rings,
+    CONTACT_STATS, DEBUG), the launch-order hints and configuration (piles, T-value weights, the randomization descriptor)."""
+
+    def __init__(self, sim, rows):
+        self.sim, self.rows = sim, int(rows)
+        s = C.c_void_p()
+        sim._check(sim.lib.sdx_state_create(sim.h, C.c_int32(self.rows), C.byref(s)))
+        self.s = s
+        self._row_env = {}        # row -> source env of the saves made with host lists (None: saved through a device tensor)
+        self._keep = None
+
+    def save(self, env_ids=None, rows=None, sim=None):
+        """env env_ids[i] -> row rows[i] (rows None: row i); env_ids None: every env plus the global state (save_all)"""
+        sim = sim or self.sim
+        if env_ids is None:
+            if rows is not None:
+                raise ValueError("SimState.save: rows without env_ids")
+            sim._check(sim.lib.sdx_state_save_all(sim.h, self.s, sim._stream_or_none()))
+            self._row_env = {e: e for e in range(sim.num_envs)}
+            return
+        e, he = sim._ids(env_ids, "SimState.save: env_ids", sim.num_envs)
+        n = int(e.numel())
+        if rows is None:
+            if n > self.rows:
+                raise ValueError("SimState.save: %d envs into %d rows" % (n, self.rows))
+            r, hr, rp = None, list(range(n)), None
+        else:
+            r, hr = sim._ids(rows, "SimState.save: rows", self.rows, unique=True)
+            rp = C.c_void_p(r.data_ptr())
+            if int(r.numel()) != n:
+                raise ValueError("SimState.save: %d envs for %d rows" % (n, int(r.numel())))
+        sim._check(sim.lib.sdx_state_save(sim.h, self.s, C.c_void_p(e.data_ptr()), rp, C.c_int32(n), sim._stream_or_none()))
+        if hr is not None:
+            for i, row in enumerate(hr):
+                self._row_env[row] = he[i] if he is not None else None
+        else:
+            self._row_env = {row: None for row in range(self.rows)}
+        self._keep = (e, r)
+
+    def restore(self, rows=None, env_ids=None, sim=None):
+        """row rows[i] -> env env_ids[i] (rows None: row i); both None: every env plus the global state (restore_all).  `sim`: another
+        simulator of the same layout (default: the one the snapshot was made by)"""
+        sim = sim or self.sim
+        if env_ids is None:
+            if rows is not None:
+                raise ValueError("SimState.restore: rows without env_ids")
+            sim._check(sim.lib.sdx_state_restore_all(sim.h, self.s, sim._stream_or_none()))
+            return
+        e, he = sim._ids(env_ids, "SimState.restore: env_ids", sim.num_envs, unique=True)
+        n = int(e.numel())
+        if rows is None:
+            if n > self.rows:
+                raise ValueError("SimState.restore: %d envs from %d rows" % (n, self.rows))
+            r, hr, rp = None, list(range(n)), None
+        else:
+            r, hr = sim._ids(rows, "SimState.restore: rows", self.rows)
+            rp = C.c_void_p(r.data_ptr())
+            if int(r.numel()) != n:
+                raise ValueError("SimState.restore: %d rows for %d envs" % (int(r.numel()), n))
+        if hr is not None and he is not None:
+            for row, env in zip(hr, he):
+                if row not in self._row_env:
+                    raise ValueError("SimState.restore: row %d was never saved" % row)
+                src = self._row_env[row]
+                if src is not None and sim.env_class(src) != sim.env_class(env):
+                    raise ValueError("SimState.restore: row %d holds env %d, which is not of env %d's class" % (row, src, env))
+        sim._check(sim.lib.sdx_state_restore(sim.h, self.s, rp, C.c_void_p(e.data_ptr()), C.c_int32(n), sim._stream_or_none()))
+        self._keep = (e, r)
+
+    def close(self):
+        if getattr(self, "s", None) is not None and self.s.value:
+            self.sim.lib.sdx_state_destroy(self.s)
+            self.s = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SdxSim:
     """One simulator+task instance on one GPU (one process per GPU; envs shard across ranks)."""
 
@@ -228,6 +311,65 @@ class SdxSim:
         stream = _stream_ptr(self.device) if self.device.type == "cuda" else None
         self._check(self.lib.sdx_set_randomization(self.h, ptr, stream))
         return report
+
+    # ------------------------------------------------------------------ sim snapshots (include/seqdex.h sdx_state_*)
+    def _stream_or_none(self):
+        return _stream_ptr(self.device) if self.device.type == "cuda" else None
+
+    def env_class(self, env):
+        """the class of an env: a saved state may only be put into an env of the class it came from (env & 7 = the target brick; InsertSim:
+        additionally env % 3 = the base plate)"""
+        e = int(env)
+        var3 = self._desc.static_var_slot >= 0 or self._desc.task_kind == _abi.TASK_INSERT
+        return (e & 7) + (8 * (e % 3) if var3 else 0)
+
+    def same_class_envs(self, env):
+        """the envs of this simulator that the state of `env` may be restored or cloned into (`env` itself included)"""
+        if not 0 <= int(env) < self.num_envs:
+            raise ValueError("same_class_envs: env %d outside [0, %d)" % (int(env), self.num_envs))
+        c = self.env_class(env)
+        return [e for e in range(self.num_envs) if self.env_class(e) == c]
+
+    def _ids(self, ids, what, limit=None, unique=False):
+        """an id list for a snapshot call -> (int32 device tensor, host list or None).  Host sequences are validated here (ValueError);
+        device tensors go through unchecked (the kernel skips and counts bad entries)"""
+        if torch.is_tensor(ids):
+            assert ids.dtype == torch.int32 and ids.is_contiguous() and ids.device.type == self.device.type, (what, ids.dtype, ids.device)
+            return ids, None
+        host = [int(i) for i in ids]
+        if limit is not None and any(i < 0 or i >= limit for i in host):
+            raise ValueError("%s: an index lies outside [0, %d): %s" % (what, limit, host))
+        if unique and len(set(host)) != len(host):
+            raise ValueError("%s: entries must be unique: %s" % (what, host))
+        return torch.as_tensor(host, dtype=torch.int32).to(self.device), host
+
+    def snapshot(self, rows=None):
+        """device memory for `rows` env states (default: one per env) of this simulator's layout: a SimState"""
+        return SimState(self, self.num_envs if rows is None else int(rows))
+
+    def clone_envs(self, src, dst):
+        """the state of env src[i] -> env dst[i] on the device (a source may repeat: fan-out).  Destinations must be unique, of their
+        source's class and not sources themselves; host lists are checked (ValueError), device int32 tensors are not (bad entries are
+        skipped and counted, state_stats())"""
+        s, hs = self._ids(src, "clone_envs: src", self.num_envs)
+        d, hd = self._ids(dst, "clone_envs: dst", self.num_envs, unique=True)
+        if int(s.numel()) != int(d.numel()):
+            raise ValueError("clone_envs: %d sources for %d destinations" % (int(s.numel()), int(d.numel())))
+        if hs is not None and hd is not None:
+            if set(hs) & set(hd):
+                raise ValueError("clone_envs: envs %s are both a source and a destination" % sorted(set(hs) & set(hd)))
+            bad = [(a, b) for a, b in zip(hs, hd) if self.env_class(a) != self.env_class(b)]
+            if bad:
+                raise ValueError("clone_envs: (src, dst) pairs of different env classes: %s" % bad)
+        self._check(self.lib.sdx_state_clone(self.h, C.c_void_p(s.data_ptr()), C.c_void_p(d.data_ptr()), C.c_int32(int(s.numel())),
+                                             self._stream_or_none()))
+        self._clone_ids = (s, d)              # (keeps the id tensors alive until the next call)
+
+    def state_stats(self):
+        """entries the snapshot kernels skipped since create: [out of range, class mismatch, restore of a row never saved].  Blocking."""
+        out = (C.c_int32 * 3)()
+        self._check(self.lib.sdx_state_stats(self.h, out))
+        return [int(v) for v in out]
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h.value:
