@@ -9,7 +9,7 @@
 // (a2c_continuous.py / RC:1796-1877) + CentralValueTrain.train_net for all three networks of one minibatch:
 //
 //   forward 3 nets x 3 trunk layers (NT GEMM, bias + ELU fused) -> mu head (NT GEMM) + two value heads (row dots)
-//   k_big_head: per-sample PPO losses and their head gradients (same formulas as k_head of sdxp_kernels.hip), block partials
+//   k_big_head: per-sample PPO losses and their head gradients (the formulas of sdxp_ppo_terms.h), block partials
 //   k_big_fin:  statistics, d logstd, KL word, minibatch bookkeeping of the control block
 //   backward: head data gradients, then per net  G_l = dY_l^T X_l (TN GEMM, split over the minibatch rows, partials reduced in a
 //   fixed order: deterministic), b_l = column sums of dY_l, dY_{l-1} = (dY_l W_l) * ELU'(H_{l-1}) (NN GEMM, fused)
@@ -19,6 +19,7 @@
 // mini-epoch 0; frozen afterwards) is hoisted out of the loop as in the small-minibatch path, with column statistics reduced in fp64.
 #include "sdx_common.h"
 #include "sdxp_types.h"
+#include "sdxp_ppo_terms.h"
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(256) void k_wave_reduce(const float* __restrict__ p
 }
 
 // ------------------------------------------------------------------------------------------------ losses
-// thread = sample s of the minibatch (dataset row r0 + s).  Formulas as k_head of sdxp_kernels.hip (RC:1796-1830, 2114-2126):
+// thread = sample s of the minibatch (dataset row r0 + s).  The formulas are sdxp_ppo_terms.h's (RC:1796-1830, 2114-2126):
 // Gaussian neglogp, clipped surrogate, (clipped) value losses of the critic and the central value, bound loss, KL to the stored
 // mu/sigma.  Writes dmu [MB][24] (column 23 = 0), dv [2][MB], the refreshed mu/sigma rows (RC:1358) and block partials
 // part[block][40]: 0..22 d logstd, 32..37 the six loss sums.
@@ -115,37 +116,14 @@ __global__ __launch_bounds__(256) void k_big_head(SdxpDev D, size_t r0, int MB, 
   if (live) {
     const size_t r = r0 + s;
     for (int a = 0; a < A; ++a) {
-      const float ls = ls_p[a], sg = expf(ls), m = mu[(size_t)s * 24 + a];
-      const float z = (D.mb_actions[r * A + a] - m) / sg;
-      nlp += 0.5f * z * z + ls;
-      const float omu = D.mb_mus[r * A + a], osg = D.mb_sigmas[r * A + a];
-      kl += logf(osg / sg + 1e-5f) + (sg * sg + (omu - m) * (omu - m)) / (2.0f * (osg * osg + 1e-5f)) - 0.5f;
-      const float hi = fmaxf(m - 1.1f, 0.0f), lo = fminf(m + 1.1f, 0.0f);
-      bl += hi * hi + lo * lo;
-      ent += 0.5f + 0.5f * 1.8378770664093453f + ls;
+      const float ls = ls_p[a];
+      const PpoActionTerms t = ppo_action_terms(ls, expf(ls), mu[(size_t)s * 24 + a], D.mb_actions[r * A + a], D.mb_mus[r * A + a], D.mb_sigmas[r * A + a]);
+      nlp += t.nlp; kl += t.kl; bl += t.bl; ent += t.ent;
     }
-    nlp += 0.5f * 1.8378770664093453f * (float)A;
-    const float adv = D.adv[r];
-    const float ratio = expf(D.mb_neglogp[r] - nlp);
-    const float L1 = -adv * ratio, L2 = -adv * clampf(ratio, 1.0f - D.e_clip, 1.0f + D.e_clip);
-    const bool inr = ratio >= 1.0f - D.e_clip && ratio <= 1.0f + D.e_clip;
-    gnlp = (L1 > L2 || inr) ? adv * ratio : 0.0f;
-    const float R = D.returns[r], vo = D.mb_values[r];
-    float closs[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const float v = j == 0 ? vc[s] : vcv[s];
-      const float vcl = vo + clampf(v - vo, -D.e_clip, D.e_clip);
-      const float c1 = (v - R) * (v - R), c2 = (vcl - R) * (vcl - R);
-      float d;
-      if (D.clip_value) {
-        closs[j] = fmaxf(c1, c2);
-        const bool inv = fabsf(v - vo) <= D.e_clip;
-        d = (c1 > c2 || inv) ? 2.0f * (v - R) : 0.0f;
-      } else { closs[j] = c1; d = 2.0f * (v - R); }
-      dv[(size_t)j * MB + s] = (j == 0 ? 0.5f * D.critic_coef : 1.0f) * d * invM;
-    }
-    stat[0] = fmaxf(L1, L2); stat[1] = closs[0]; stat[2] = bl; stat[3] = kl; stat[4] = closs[1]; stat[5] = ent;
+    const PpoRowTerms t = ppo_row_terms(D, D.adv[r], D.mb_neglogp[r], ppo_neglogp(nlp, A), D.returns[r], D.mb_values[r], vc[s], vcv[s], invM);
+    gnlp = t.gnlp;
+    dv[s] = t.dv[0]; dv[(size_t)MB + s] = t.dv[1];
+    stat[0] = t.a_loss; stat[1] = t.closs[0]; stat[2] = bl; stat[3] = kl; stat[4] = t.closs[1]; stat[5] = ent;
   }
   // head gradients + d logstd partial sums (one wave reduction per action)
   for (int a = 0; a < 24; ++a) {
@@ -154,11 +132,9 @@ __global__ __launch_bounds__(256) void k_big_head(SdxpDev D, size_t r0, int MB, 
       float d = 0.0f;
       if (a < A) {
         const size_t r = r0 + s;
-        const float ls = ls_p[a], sg = expf(ls), m = mu[(size_t)s * 24 + a];
-        const float z = (D.mb_actions[r * A + a] - m) / sg;
-        const float hi = fmaxf(m - 1.1f, 0.0f), lo = fminf(m + 1.1f, 0.0f);
-        d = gnlp * (-(z / sg)) * invM + D.bounds_coef * (2.0f * hi + 2.0f * lo) * invM;
-        dls = gnlp * (1.0f - z * z) * invM;
+        const float sg = expf(ls_p[a]), m = mu[(size_t)s * 24 + a];
+        const PpoActionGrad g = ppo_action_grad(gnlp, ppo_z(D.mb_actions[r * A + a], m, sg), sg, m, D.bounds_coef, invM);
+        d = g.dmu; dls = g.dls;
         D.mb_mus[r * A + a] = m;
         D.mb_sigmas[r * A + a] = sg;
       }
@@ -184,8 +160,16 @@ __global__ __launch_bounds__(256) void k_big_head(SdxpDev D, size_t r0, int MB, 
     part[(size_t)blockIdx.x * BIGP + j] = used ? (s_red[0][j] + s_red[1][j]) + (s_red[2][j] + s_red[3][j]) : 0.0f;
   }
 }
-// one block: fold the block partials, write d logstd into the flat gradient, the KL word, the loss sums and advance the minibatch
-// cursor of the control block (what k_ctrl does in explicit mode for the small-minibatch path)
+// one thread: the minibatch's six loss sums into the control block, the KL word behind the gradients (multi-rank all-reduce; read by
+// k_apply_fin2), Adam left to the apply kernels, the cursor moved on (what k_ctrl does in explicit mode for the small-minibatch path)
+__device__ __forceinline__ void big_minibatch_done(const SdxpDev& D, int MB, const float* sums) {
+  SdxpCtrl& c = *D.ctrl;
+  for (int q = 0; q < 6; ++q) c.acc[1 + q] = sums[q];
+  ppo_account_minibatch(c, 1.0f / (float)MB, &D.ac_g[D.g_tail]);
+  ppo_explicit_reset(c);
+  ppo_advance_cursor(c, D.num_minibatches, true);
+}
+// one block: fold the block partials, write d logstd into the flat gradient, then big_minibatch_done
 __global__ __launch_bounds__(64) void k_big_fin(SdxpDev D, int nblocks, int MB, const float* __restrict__ part) {
   __shared__ float s_t[BIGP];
   const int j = threadIdx.x;
@@ -195,23 +179,8 @@ __global__ __launch_bounds__(64) void k_big_fin(SdxpDev D, int nblocks, int MB, 
     s_t[j] = t;
   }
   __syncthreads();
-  if (j < D.act_dim) D.ac_g[D.off.logstd + j] = s_t[j] - D.entropy_coef;   // d(-coef * mean entropy)/d logstd = -coef
-  if (j == 0) {
-    SdxpCtrl* ctl = D.ctrl;
-    const float invM = 1.0f / (float)MB;
-    const float kl = s_t[35] * invM;
-    for (int q = 0; q < 6; ++q) ctl->acc[1 + q] = s_t[32 + q];
-    ctl->sum_a_loss += s_t[32] * invM; ctl->sum_c_loss += s_t[33] * invM; ctl->sum_b_loss += s_t[34] * invM;
-    ctl->sum_kl += kl; ctl->sum_cv_loss += s_t[36] * invM; ctl->sum_entropy += s_t[37] * invM;
-    ctl->n_mb += 1; ctl->last_kl = kl;
-    D.ac_g[D.g_tail] = kl;                        // rides with the gradients (multi-rank all-reduce), read by k_apply_fin2
-    ctl->gn2_ac = 0.0f; ctl->gn2_cv = 0.0f; ctl->ac_pending = 0; ctl->cv_pending = 0;
-    ctl->prev_mb = ctl->mb_index; ctl->prev_mini_epoch = ctl->mini_epoch;
-    int mbn = ctl->mb_index + 1;
-    if (mbn >= D.num_minibatches) { mbn = 0; ctl->mini_epoch += 1; }
-    ctl->mb_index = mbn;
-    ctl->step += 1;
-  }
+  if (j < D.act_dim) D.ac_g[D.off.logstd + j] = ppo_dlogstd(s_t[j], D.entropy_coef);
+  if (j == 0) big_minibatch_done(D, MB, &s_t[32]);
 }
 
 // ------------------------------------------------------------------------------------------------ fused heads (round 6)
@@ -318,7 +287,7 @@ __global__ __launch_bounds__(512) void k_big_heads(SdxpDev D, size_t r0, int MB,
       }
     }
     __syncthreads();
-    // ---- phase 2: losses and head gradients (formulas: k_big_head; RC:1796-1830, 2114-2126).  Thread = (row rr, action group g): the
+    // ---- phase 2: losses and head gradients (formulas: sdxp_ppo_terms.h).  Thread = (row rr, action group g): the
     // actions g, g + 8, g + 16 of row s0 + rr; the per-row sums over the actions are folded over the 8 lanes of the row (xor 1, 2, 4),
     // the per-action sums over the rows over the wave's 8 rows (xor 8, 16, 32), then over the 4 waves in index order
     if (t < 256) {
@@ -333,44 +302,21 @@ __global__ __launch_bounds__(512) void k_big_heads(SdxpDev D, size_t r0, int MB,
         zq[j] = 0.0f; sgq[j] = 1.0f; mq[j] = 0.0f;
         if (live && a < A) {
           const float ls = ls_p[a], sg = expf(ls), m = L.mu[rr][a];
-          const float z = (D.mb_actions[r * A + a] - m) / sg;
-          nlp += 0.5f * z * z + ls;
-          const float omu = D.mb_mus[r * A + a], osg = D.mb_sigmas[r * A + a];
-          kl += logf(osg / sg + 1e-5f) + (sg * sg + (omu - m) * (omu - m)) / (2.0f * (osg * osg + 1e-5f)) - 0.5f;
-          const float hi = fmaxf(m - 1.1f, 0.0f), lo = fminf(m + 1.1f, 0.0f);
-          bl += hi * hi + lo * lo;
-          ent += 0.5f + 0.5f * 1.8378770664093453f + ls;
-          zq[j] = z; sgq[j] = sg; mq[j] = m;
+          const PpoActionTerms t = ppo_action_terms(ls, sg, m, D.mb_actions[r * A + a], D.mb_mus[r * A + a], D.mb_sigmas[r * A + a]);
+          nlp += t.nlp; kl += t.kl; bl += t.bl; ent += t.ent;
+          zq[j] = t.z; sgq[j] = sg; mq[j] = m;
         }
       }
 #pragma unroll
       for (int o = 1; o < 8; o <<= 1) { nlp += __shfl_xor(nlp, o, 64); kl += __shfl_xor(kl, o, 64); bl += __shfl_xor(bl, o, 64); ent += __shfl_xor(ent, o, 64); }
-      nlp += 0.5f * 1.8378770664093453f * (float)A;
       float gnlp = 0.0f;
       float stat[6] = {0, 0, 0, 0, 0, 0};
-      if (live) {
-        const float adv = D.adv[r];
-        const float ratio = expf(D.mb_neglogp[r] - nlp);
-        const float L1 = -adv * ratio, L2 = -adv * clampf(ratio, 1.0f - D.e_clip, 1.0f + D.e_clip);
-        const bool inr = ratio >= 1.0f - D.e_clip && ratio <= 1.0f + D.e_clip;
-        gnlp = (L1 > L2 || inr) ? adv * ratio : 0.0f;
+      if (live) {   // (every lane of the row needs gnlp; lane g = 0 keeps the row's value gradients and statistics)
+        const PpoRowTerms t = ppo_row_terms(D, D.adv[r], D.mb_neglogp[r], ppo_neglogp(nlp, A), D.returns[r], D.mb_values[r], L.v[0][rr], L.v[1][rr], invM);
+        gnlp = t.gnlp;
         if (g == 0) {
-          const float R = D.returns[r], vo = D.mb_values[r];
-          float closs[2];
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            const float v = L.v[j][rr];
-            const float vcl = vo + clampf(v - vo, -D.e_clip, D.e_clip);
-            const float c1 = (v - R) * (v - R), c2 = (vcl - R) * (vcl - R);
-            float d;
-            if (D.clip_value) {
-              closs[j] = fmaxf(c1, c2);
-              const bool inv = fabsf(v - vo) <= D.e_clip;
-              d = (c1 > c2 || inv) ? 2.0f * (v - R) : 0.0f;
-            } else { closs[j] = c1; d = 2.0f * (v - R); }
-            L.dv[j][rr] = (j == 0 ? 0.5f * D.critic_coef : 1.0f) * d * invM;
-          }
-          stat[0] = fmaxf(L1, L2); stat[1] = closs[0]; stat[2] = bl; stat[3] = kl; stat[4] = closs[1]; stat[5] = ent;
+          L.dv[0][rr] = t.dv[0]; L.dv[1][rr] = t.dv[1];
+          stat[0] = t.a_loss; stat[1] = t.closs[0]; stat[2] = bl; stat[3] = kl; stat[4] = t.closs[1]; stat[5] = ent;
         }
       } else if (g == 0) { L.dv[0][rr] = 0.0f; L.dv[1][rr] = 0.0f; }
 #pragma unroll
@@ -378,12 +324,10 @@ __global__ __launch_bounds__(512) void k_big_heads(SdxpDev D, size_t r0, int MB,
         const int a = g + 8 * j;
         float d = 0.0f, dls = 0.0f;
         if (live && a < A) {
-          const float z = zq[j], sg = sgq[j], m = mq[j];
-          const float hi = fmaxf(m - 1.1f, 0.0f), lo = fminf(m + 1.1f, 0.0f);
-          d = gnlp * (-(z / sg)) * invM + D.bounds_coef * (2.0f * hi + 2.0f * lo) * invM;
-          dls = gnlp * (1.0f - z * z) * invM;
-          D.mb_mus[r * A + a] = m;
-          D.mb_sigmas[r * A + a] = sg;
+          const PpoActionGrad ag = ppo_action_grad(gnlp, zq[j], sgq[j], mq[j], D.bounds_coef, invM);
+          d = ag.dmu; dls = ag.dls;
+          D.mb_mus[r * A + a] = mq[j];
+          D.mb_sigmas[r * A + a] = sgq[j];
         }
         if (a < 24) L.dmu[rr][a] = d;
 #pragma unroll
@@ -451,7 +395,7 @@ __global__ __launch_bounds__(512) void k_big_heads(SdxpDev D, size_t r0, int MB,
   if (t == 23) P[BIGP + 23 * HU + 23 + HU] = bsum;
   if (t == 24) P[BIGP + 23 * HU + 23 + HU + 1 + HU] = bsum;
 }
-// fold of the heads' partials over the workgroups (index order: deterministic) into the flat gradients + what k_big_fin does
+// fold of the heads' partials over the workgroups (index order: deterministic) into the flat gradients, then big_minibatch_done
 __global__ __launch_bounds__(256) void k_big_heads_reduce(SdxpDev D, int nblocks, int MB, const float* __restrict__ part) {
   __shared__ float s_t[BIGP];
   // eight lanes per output element: lane l sums the workgroups b = l, l + 8, ... in order, the eight sums are added in a fixed tree
@@ -473,23 +417,8 @@ __global__ __launch_bounds__(256) void k_big_heads_reduce(SdxpDev D, int nblocks
   if (l == 0 && i < 32) s_t[i] = x;    // block 0 folds elements 0 .. 31: the d logstd sums 0 .. 22 and the six loss sums 24 .. 29
   __syncthreads();
   const int j = threadIdx.x;
-  if (j < A) D.ac_g[D.off.logstd + j] = s_t[j] - D.entropy_coef;   // d(-coef * mean entropy)/d logstd = -coef
-  if (j == 0) {
-    SdxpCtrl* ctl = D.ctrl;
-    const float invM = 1.0f / (float)MB;
-    const float kl = s_t[27] * invM;
-    for (int q = 0; q < 6; ++q) ctl->acc[1 + q] = s_t[24 + q];
-    ctl->sum_a_loss += s_t[24] * invM; ctl->sum_c_loss += s_t[25] * invM; ctl->sum_b_loss += s_t[26] * invM;
-    ctl->sum_kl += kl; ctl->sum_cv_loss += s_t[28] * invM; ctl->sum_entropy += s_t[29] * invM;
-    ctl->n_mb += 1; ctl->last_kl = kl;
-    D.ac_g[D.g_tail] = kl;
-    ctl->gn2_ac = 0.0f; ctl->gn2_cv = 0.0f; ctl->ac_pending = 0; ctl->cv_pending = 0;
-    ctl->prev_mb = ctl->mb_index; ctl->prev_mini_epoch = ctl->mini_epoch;
-    int mbn = ctl->mb_index + 1;
-    if (mbn >= D.num_minibatches) { mbn = 0; ctl->mini_epoch += 1; }
-    ctl->mb_index = mbn;
-    ctl->step += 1;
-  }
+  if (j < A) D.ac_g[D.off.logstd + j] = ppo_dlogstd(s_t[j], D.entropy_coef);
+  if (j == 0) big_minibatch_done(D, MB, &s_t[24]);
 }
 static int heads_nrb(int MB) { int n = MB / (HR * 512); return n < 1 ? 1 : n; }
 static int heads_blocks(int MB) { const int nrb = heads_nrb(MB); return (MB + HR * nrb - 1) / (HR * nrb); }

@@ -16,6 +16,7 @@
 // Per optimiser step: L1, L2, L3, HEAD(+loss +backward of the heads), B3, B2, CTRL = 7 launches for all three nets.
 #include "sdx_common.h"
 #include "sdxp_types.h"
+#include "sdxp_ppo_terms.h"
 #include <cstddef>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -594,13 +595,6 @@ __device__ void block_gram(const float* v, int K, float* out, float* s_scr /*>= 
   if (tid < MB * MB) { const int a = tid / MB, b = tid % MB; out[tid] = a >= b ? s_scr[a * MB + b] : s_scr[b * MB + a]; }
 }
 
-// Adam step of one parameter (torch.optim.Adam, betas 0.9/0.999, eps 1e-8, bias corrections bc1/bc2 precomputed)
-__device__ __forceinline__ float adam1(float w, float g, float& m, float& v, float lr_bc1, float isq_bc2) {
-  m = 0.9f * m + 0.1f * g;
-  v = 0.999f * v + 0.001f * g * g;
-  return w - lr_bc1 * m / (sqrtf(v) * isq_bc2 + 1e-8f);
-}
-
 // L-kernel: lazy Adam of the previous minibatch + forward of the current one for trunk layer `l` of all three nets.
 // block = 256 threads = 4 waves; a wave owns RPW consecutive weight rows; lanes run along K with float4 accesses.
 // All global loads of a wave (RPW rows x KI float4 columns x {w,m,v}) are issued before any arithmetic so that the
@@ -852,24 +846,17 @@ __global__ __launch_bounds__(1024) void k_head(SdxpDev D, int flush) {
   }
   const float invM = 1.0f / (float)MB;
   STAMP(2);
-  if (tid < MB * 32) {
-    const int s = tid / 32, a = tid % 32;
-    s_z[s][a] = (a < A) ? (s_act[s][a] - s_mu[s][a]) / expf(s_ls[a]) : 0.0f;
-  }
-  __syncthreads();
-  // ---- per-sample scalars: lanes (s, a) reduce over the 32-lane half-wave of sample s
+  // ---- per-sample scalars (sdxp_ppo_terms.h): lanes (s, a) reduce over the 32-lane half-wave of sample s; z stays in LDS for dmu / dlogstd
   float r_nlp = 0.0f, r_kl = 0.0f, r_bl = 0.0f, r_ent = 0.0f;
   if (tid < MB * 32) {
     const int s = tid / 32, a = tid % 32;
+    float z = 0.0f;
     if (a < A) {
-      const float ls = s_ls[a], sg = expf(ls), mu = s_mu[s][a];
-      r_nlp = 0.5f * s_z[s][a] * s_z[s][a] + ls;                                                  // RC:2114-2126
-      const float omu = s_omu[s][a], osg = s_osg[s][a];
-      r_kl = logf(osg / sg + 1e-5f) + (sg * sg + (omu - mu) * (omu - mu)) / (2.0f * (osg * osg + 1e-5f)) - 0.5f;
-      const float hi = fmaxf(mu - 1.1f, 0.0f), lo = fminf(mu + 1.1f, 0.0f);
-      r_bl = hi * hi + lo * lo;
-      r_ent = 0.5f + 0.5f * 1.8378770664093453f + ls;
+      const float ls = s_ls[a];
+      const PpoActionTerms t = ppo_action_terms(ls, expf(ls), s_mu[s][a], s_act[s][a], s_omu[s][a], s_osg[s][a]);
+      z = t.z; r_nlp = t.nlp; r_kl = t.kl; r_bl = t.bl; r_ent = t.ent;
     }
+    s_z[s][a] = z;
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1) {
       r_nlp += __shfl_xor(r_nlp, o, 64); r_kl += __shfl_xor(r_kl, o, 64);
@@ -878,28 +865,12 @@ __global__ __launch_bounds__(1024) void k_head(SdxpDev D, int flush) {
   }
   if (tid < MB * 32 && (tid % 32) == 0) {
     const int s = tid / 32;
-    const float nlp = r_nlp + 0.5f * 1.8378770664093453f * (float)A, kl = r_kl, bl = r_bl, ent = r_ent;
-    const float adv = D.adv[r0 + s];
-    const float ratio = expf(D.mb_neglogp[r0 + s] - nlp);
-    const float L1 = -adv * ratio, L2 = -adv * clampf(ratio, 1.0f - D.e_clip, 1.0f + D.e_clip);   // RC:1813
-    const bool inr = ratio >= 1.0f - D.e_clip && ratio <= 1.0f + D.e_clip;
-    s_gnlp[s] = (L1 > L2 || inr) ? adv * ratio : 0.0f;     // d max(L1,L2)/d nlp (L2 is constant outside the clip range)
-    const float R = D.returns[r0 + s], vo = D.mb_values[r0 + s];
-    float closs[2];
-    for (int j = 0; j < 2; ++j) {                                                                 // RC:1818-1822
-      const float v = s_v[j][s];
-      const float vc = vo + clampf(v - vo, -D.e_clip, D.e_clip);
-      const float c1 = (v - R) * (v - R), c2 = (vc - R) * (vc - R);
-      float d;
-      if (D.clip_value) {
-        closs[j] = fmaxf(c1, c2);
-        const bool inv = fabsf(v - vo) <= D.e_clip;
-        d = (c1 > c2 || inv) ? 2.0f * (v - R) : 0.0f;      // outside the clip range v_clipped is constant
-      } else { closs[j] = c1; d = 2.0f * (v - R); }
-      s_dv[j][s] = (j == 0 ? 0.5f * D.critic_coef : 1.0f) * d * invM;
-    }
-    s_stat[s][1] = fmaxf(L1, L2); s_stat[s][2] = closs[0]; s_stat[s][3] = bl; s_stat[s][4] = kl;
-    s_stat[s][5] = closs[1]; s_stat[s][6] = ent;
+    const PpoRowTerms t = ppo_row_terms(D, D.adv[r0 + s], D.mb_neglogp[r0 + s], ppo_neglogp(r_nlp, A), D.returns[r0 + s], D.mb_values[r0 + s],
+                                        s_v[0][s], s_v[1][s], invM);
+    s_gnlp[s] = t.gnlp;
+    s_dv[0][s] = t.dv[0]; s_dv[1][s] = t.dv[1];
+    s_stat[s][1] = t.a_loss; s_stat[s][2] = t.closs[0]; s_stat[s][3] = r_bl; s_stat[s][4] = r_kl;
+    s_stat[s][5] = t.closs[1]; s_stat[s][6] = r_ent;
   }
   __syncthreads();
   if (tid < MB * 32) {
@@ -907,8 +878,7 @@ __global__ __launch_bounds__(1024) void k_head(SdxpDev D, int flush) {
     float dmu = 0.0f;
     if (a < A) {
       const float sg = expf(s_ls[a]), mu = s_mu[s][a];
-      const float hi = fmaxf(mu - 1.1f, 0.0f), lo = fminf(mu + 1.1f, 0.0f);
-      dmu = s_gnlp[s] * (-(s_z[s][a] / sg)) * invM + D.bounds_coef * (2.0f * hi + 2.0f * lo) * invM;
+      dmu = ppo_action_grad(s_gnlp[s], s_z[s][a], sg, mu, D.bounds_coef, invM).dmu;
       D.mb_mus[(r0 + s) * A + a] = mu;                                                            // RC:1358
       D.mb_sigmas[(r0 + s) * A + a] = sg;
     }
@@ -919,8 +889,8 @@ __global__ __launch_bounds__(1024) void k_head(SdxpDev D, int flush) {
   if (tid >= 512 && tid < 512 + A) {
     const int a = tid - 512;
     float dls = 0.0f;
-    for (int s = 0; s < MB; ++s) dls += s_gnlp[s] * (1.0f - s_z[s][a] * s_z[s][a]) * invM;
-    dls -= D.entropy_coef;   // d(-coef * mean entropy)/d logstd = -coef (k_big_fin does the same); the norm below sees this value
+    for (int s = 0; s < MB; ++s) dls += ppo_dlogstd_term(s_gnlp[s], s_z[s][a], invM);
+    dls = ppo_dlogstd(dls, D.entropy_coef);   // the norm below sees this value
     D.dlogstd[(size_t)par * 32 + a] = dls;
     s_dls[a] = dls;
   }
@@ -1123,8 +1093,8 @@ __global__ __launch_bounds__(1024) void k_ctrl(SdxpDev D, int advance) {
       }
       const float ac_norm = sqrtf(n2[0] + n2[1]), cv_norm = sqrtf(n2[2]);
       ctl->ac_gnorm = ac_norm; ctl->cv_gnorm = cv_norm;
-      ctl->ac_gscale = D.truncate_grads ? fminf(1.0f, D.grad_norm / (ac_norm + 1e-6f)) : 1.0f;   // clip_grad_norm_
-      ctl->cv_gscale = D.truncate_grads ? fminf(1.0f, D.grad_norm / (cv_norm + 1e-6f)) : 1.0f;
+      ctl->ac_gscale = ppo_clip_scale(D, ac_norm);
+      ctl->cv_gscale = ppo_clip_scale(D, cv_norm);
       const bool explicit_mode = (advance & 8) != 0;   // multi-rank: Adam/LR happen in sdxp_apply after the all-reduce
       if (!explicit_mode) {
         ctl->ac_t += 1; ctl->cv_t += 1;
@@ -1133,31 +1103,17 @@ __global__ __launch_bounds__(1024) void k_ctrl(SdxpDev D, int advance) {
         ctl->cv_bc1 = (float)(1.0 - ctl->cv_b1pow); ctl->cv_bc2 = (float)(1.0 - ctl->cv_b2pow);
         ctl->ac_lr_applied = ctl->ac_lr; ctl->cv_lr_applied = ctl->cv_lr;
         ctl->ac_pending = 1; ctl->cv_pending = 1;
-      } else { ctl->gn2_ac = 0.0f; ctl->gn2_cv = 0.0f; ctl->ac_pending = 0; ctl->cv_pending = 0; }
-      const float invM = 1.0f / (float)MB;
-      const float kl = ctl->acc[4] * invM;
-      if (explicit_mode) { D.fact[D.foff.kl] = kl; D.ac_g[D.g_tail] = kl; }   // this rank's minibatch KL rides with factors / gradients
-      ctl->sum_a_loss += ctl->acc[1] * invM; ctl->sum_c_loss += ctl->acc[2] * invM; ctl->sum_b_loss += ctl->acc[3] * invM;
-      ctl->sum_kl += kl; ctl->sum_cv_loss += ctl->acc[5] * invM; ctl->sum_entropy += ctl->acc[6] * invM;
-      ctl->n_mb += 1; ctl->last_kl = kl;
-      if (D.adaptive_lr && !explicit_mode) {   // legacy schedule: after every minibatch (PS:306-312)
-        if (kl > 2.0f * D.kl_threshold) ctl->ac_lr = fmaxf(ctl->ac_lr / 1.5f, 1e-6f);
-        if (kl < 0.5f * D.kl_threshold) ctl->ac_lr = fminf(ctl->ac_lr * 1.5f, 1e-2f);
-      }
+      } else ppo_explicit_reset(*ctl);
+      // explicit mode: this rank's minibatch KL rides with factors / gradients, and the learning rate moves in the apply
+      const float kl = ppo_account_minibatch(*ctl, 1.0f / (float)MB, explicit_mode ? &D.ac_g[D.g_tail] : nullptr);
+      if (explicit_mode) D.fact[D.foff.kl] = kl;
+      else ppo_lr_advance(*ctl, D, kl);
     }
     __syncthreads();
   }
   if (threadIdx.x == 0) D.dbg[10] = (long long)__builtin_readcyclecounter();
   if (advance & 2) {
-    if (tid == 0) {
-      ctl->prev_mb = ctl->mb_index; ctl->prev_mini_epoch = ctl->mini_epoch;
-      if (advance & 1) {
-        int mbn = ctl->mb_index + 1;
-        if (mbn >= D.num_minibatches) { mbn = 0; ctl->mini_epoch += 1; }
-        ctl->mb_index = mbn;
-        ctl->step += 1;
-      }
-    }
+    if (tid == 0) ppo_advance_cursor(*ctl, D.num_minibatches, (advance & 1) != 0);
     // the split-N accumulators of the parity that the NEXT step will write must start from zero
     const int npar = (advance & 1) ? (par ^ 1) : par;
     for (int net = 0; net < 3; ++net)
@@ -1425,14 +1381,17 @@ template <int MB>
 __global__ __launch_bounds__(256) void k_grad_heads_w(SdxpDev D) { grad_heads_w_body<MB>(D, 0, 1); }
 // squared norm of the flat gradient, bit-reproducible (every rank must compute the SAME clip scale from the same gradient, or the
 // replicas drift apart): fixed block -> slice mapping, in-block tree in a fixed order, second stage sums the 512 block partials
-__global__ __launch_bounds__(256) void k_sqnorm(const float* __restrict__ g, size_t n, float scale, float* part) {
+__device__ __forceinline__ void sqnorm_block(const float* __restrict__ g, size_t n, float scale, float* part) {   // part: this block's slot
   __shared__ float sw[4];
   float s = 0.0f;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) { const float v = g[i] * scale; s += v * v; }
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (sw[0] + sw[1]) + (sw[2] + sw[3]);
+  if (threadIdx.x == 0) *part = (sw[0] + sw[1]) + (sw[2] + sw[3]);
+}
+__global__ __launch_bounds__(256) void k_sqnorm(const float* __restrict__ g, size_t n, float scale, float* part) {
+  sqnorm_block(g, n, scale, part + blockIdx.x);
 }
 __global__ __launch_bounds__(512) void k_sqnorm_fin(const float* __restrict__ part, int nparts, float* out) {
   __shared__ float sw[8];
@@ -1442,35 +1401,35 @@ __global__ __launch_bounds__(512) void k_sqnorm_fin(const float* __restrict__ pa
   __syncthreads();
   if (threadIdx.x == 0) *out = ((sw[0] + sw[1]) + (sw[2] + sw[3])) + ((sw[4] + sw[5]) + (sw[6] + sw[7]));
 }
-__global__ __launch_bounds__(256) void k_adam_explicit(SdxpDev D, int which) {
+// clip_grad_norm_ + Adam of one flat buffer (which: 0 actor-critic, 1 central value) whose rank-summed gradient has the squared norm gn2
+// (of the rank average): grid-stride sweep over P / M / V / G with the element function ADAM (adam1 or adam1x)
+typedef float (*AdamFn)(float, float, float&, float&, float, float);
+template <AdamFn ADAM>
+__device__ __forceinline__ void adam_sweep(const SdxpDev& D, int which, float gn2) {
   const SdxpCtrl* ctl = D.ctrl;
   const size_t n = which ? D.coff.total : D.off.total;
   float* P = which ? D.cv : D.ac; float* M = which ? D.cv_m : D.ac_m; float* V = which ? D.cv_v : D.ac_v;
   const float* G = which ? D.cv_g : D.ac_g;
   const float inv_w = 1.0f / (float)ctl->world;
-  const float norm = sqrtf(which ? ctl->gn2_cv : ctl->gn2_ac);
-  const float clip = D.truncate_grads ? fminf(1.0f, D.grad_norm / (norm + 1e-6f)) : 1.0f;
-  const int t = (which ? ctl->cv_t : ctl->ac_t) + 1;
-  const float bc1 = 1.0f - powf(0.9f, (float)t), bc2 = 1.0f - powf(0.999f, (float)t);
-  const float lr = which ? ctl->cv_lr : ctl->ac_lr;
-  const float lr_bc1 = lr / bc1, isq_bc2 = 1.0f / sqrtf(bc2);
+  const float clip = ppo_clip_scale(D, sqrtf(gn2));
+  const PpoAdamScales a = ppo_adam_scales(which ? ctl->cv_lr : ctl->ac_lr, (which ? ctl->cv_t : ctl->ac_t) + 1);
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
     float m = M[i], v = V[i];
-    P[i] = adam1(P[i], G[i] * inv_w * clip, m, v, lr_bc1, isq_bc2);
+    P[i] = ADAM(P[i], G[i] * inv_w * clip, m, v, a.lr_bc1, a.isq_bc2);
     M[i] = m; V[i] = v;
   }
 }
+__global__ __launch_bounds__(256) void k_adam_explicit(SdxpDev D, int which) {
+  adam_sweep<adam1>(D, which, which ? D.ctrl->gn2_cv : D.ctrl->gn2_ac);
+}
 __global__ void k_apply_fin(SdxpDev D, int which, float kl_host) {
   SdxpCtrl* ctl = D.ctrl;
-  if (which) { ctl->cv_t += 1; ctl->cv_b1pow *= 0.9; ctl->cv_b2pow *= 0.999; ctl->cv_gnorm = sqrtf(ctl->gn2_cv); return; }
-  ctl->ac_t += 1; ctl->ac_b1pow *= 0.9; ctl->ac_b2pow *= 0.999; ctl->ac_gnorm = sqrtf(ctl->gn2_ac);
+  ppo_adam_advance(*ctl, which);
+  if (which) return;
   // NaN -> device value, all-reduced in place; -inf -> the KL word that travelled with the gradients in ALL_GRADS
   const float kl = (kl_host != kl_host) ? ctl->last_kl / (float)ctl->world
                  : (kl_host == -INFINITY ? D.ac_g[D.g_tail] / (float)ctl->world : kl_host);
-  if (D.adaptive_lr) {   // legacy schedule after every minibatch, on the rank-averaged KL (PS:306-312)
-    if (kl > 2.0f * D.kl_threshold) ctl->ac_lr = fmaxf(ctl->ac_lr / 1.5f, 1e-6f);
-    if (kl < 0.5f * D.kl_threshold) ctl->ac_lr = fminf(ctl->ac_lr * 1.5f, 1e-2f);
-  }
+  ppo_lr_advance(*ctl, D, kl);
 }
 
 // ------------------------------------------------------------------------------------------------ launch helpers
@@ -1625,104 +1584,41 @@ __global__ __launch_bounds__(256) void k_grad_all_w(SdxpDev D, int with_norm) {
   grad_layer_w_body<MB>(D, l, b, part, blockIdx.x);
 }
 __global__ __launch_bounds__(256) void k_sqnorm2(SdxpDev D, float scale) {
-  __shared__ float sw[4];
   const int which = blockIdx.y;
-  const float* g = which ? D.cv_g : D.ac_g;
-  const size_t n = which ? D.coff.total : D.off.total;
-  float s = 0.0f;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) { const float v = g[i] * scale; s += v * v; }
+  sqnorm_block(which ? D.cv_g : D.ac_g, which ? D.coff.total : D.off.total, scale, D.sqn_part + which * 512 + blockIdx.x);
+}
+// the squared norm of buffer `which` from s, this thread's share of its partials: every block folds them in the same fixed order -> the
+// same clip scale in every block and on every rank; block 0 publishes the sum in the control block
+__device__ __forceinline__ float fold_gn2(SdxpCtrl* ctl, int which, float s) {
+  __shared__ float sw[4];
+  __shared__ float s_n2;
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) D.sqn_part[which * 512 + blockIdx.x] = (sw[0] + sw[1]) + (sw[2] + sw[3]);
+  if (threadIdx.x == 0) {
+    s_n2 = (sw[0] + sw[1]) + (sw[2] + sw[3]);
+    if (blockIdx.x == 0) { if (which) ctl->gn2_cv = s_n2; else ctl->gn2_ac = s_n2; }
+  }
+  __syncthreads();
+  return s_n2;
 }
+// the 512 partials of k_sqnorm2, two per thread
 __global__ __launch_bounds__(256) void k_adam2(SdxpDev D) {
-  __shared__ float sw[4];
-  __shared__ float s_n2;
-  SdxpCtrl* ctl = D.ctrl;
   const int which = blockIdx.y;
-  {   // every block folds the 512 partials in the same fixed order -> the same clip scale everywhere, on every rank
-    float s = D.sqn_part[which * 512 + threadIdx.x] + D.sqn_part[which * 512 + 256 + threadIdx.x];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      s_n2 = (sw[0] + sw[1]) + (sw[2] + sw[3]);
-      if (blockIdx.x == 0) { if (which) ctl->gn2_cv = s_n2; else ctl->gn2_ac = s_n2; }
-    }
-    __syncthreads();
-  }
-  const size_t n = which ? D.coff.total : D.off.total;
-  float* P = which ? D.cv : D.ac; float* M = which ? D.cv_m : D.ac_m; float* V = which ? D.cv_v : D.ac_v;
-  const float* G = which ? D.cv_g : D.ac_g;
-  const float inv_w = 1.0f / (float)ctl->world;
-  const float norm = sqrtf(s_n2);
-  const float clip = D.truncate_grads ? fminf(1.0f, D.grad_norm / (norm + 1e-6f)) : 1.0f;
-  const int t = (which ? ctl->cv_t : ctl->ac_t) + 1;
-  const float bc1 = 1.0f - powf(0.9f, (float)t), bc2 = 1.0f - powf(0.999f, (float)t);
-  const float lr = which ? ctl->cv_lr : ctl->ac_lr;
-  const float lr_bc1 = lr / bc1, isq_bc2 = 1.0f / sqrtf(bc2);
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-    float m = M[i], v = V[i];
-    P[i] = adam1(P[i], G[i] * inv_w * clip, m, v, lr_bc1, isq_bc2);
-    M[i] = m; V[i] = v;
-  }
+  adam_sweep<adam1>(D, which, fold_gn2(D.ctrl, which, D.sqn_part[which * 512 + threadIdx.x] + D.sqn_part[which * 512 + 256 + threadIdx.x]));
 }
-// adam1 with every rounding spelled out (no compiler-chosen contraction): k_adam3 and the one-launch apply (k_apply_factors_fused) inline it
-// in different surroundings, where hipcc picked different fused multiply-adds for `0.9 m + 0.1 g` (first moments one ulp apart after one
-// step); written this way the two forms of the apply are bit-identical (tests/test_gpu_fullsize_properties.py).
-__device__ __forceinline__ float adam1x(float w, float g, float& m, float& v, float lr_bc1, float isq_bc2) {
-#pragma clang fp contract(off)
-  m = __builtin_fmaf(0.1f, g, 0.9f * m);
-  v = __builtin_fmaf(0.001f * g, g, 0.999f * v);
-  const float den = __builtin_fmaf(sqrtf(v), isq_bc2, 1e-8f);
-  const float q = (lr_bc1 * m) / den;
-  return w - q;
-}
-// k_adam2 with the squared norms taken from the per-workgroup partials that k_grad_all_w left in sqn_part (nparts slots per buffer):
-// every block folds them in the same fixed order -> the same clip scale in every block and on every rank
+// the per-workgroup partials that k_grad_all_w left in sqn_part (nparts slots per buffer); adam1x: bit-identical to the one-launch apply
 __global__ __launch_bounds__(256) void k_adam3(SdxpDev D, int nparts) {
-  __shared__ float sw[4];
-  __shared__ float s_n2;
-  SdxpCtrl* ctl = D.ctrl;
   const int which = blockIdx.y;
-  {
-    float s = 0.0f;
-    for (int i = threadIdx.x; i < nparts; i += 256) s += D.sqn_part[which * SDXP_SQN_STRIDE + i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      s_n2 = (sw[0] + sw[1]) + (sw[2] + sw[3]);
-      if (blockIdx.x == 0) { if (which) ctl->gn2_cv = s_n2; else ctl->gn2_ac = s_n2; }
-    }
-    __syncthreads();
-  }
-  const size_t n = which ? D.coff.total : D.off.total;
-  float* P = which ? D.cv : D.ac; float* M = which ? D.cv_m : D.ac_m; float* V = which ? D.cv_v : D.ac_v;
-  const float* G = which ? D.cv_g : D.ac_g;
-  const float inv_w = 1.0f / (float)ctl->world;
-  const float norm = sqrtf(s_n2);
-  const float clip = D.truncate_grads ? fminf(1.0f, D.grad_norm / (norm + 1e-6f)) : 1.0f;
-  const int t = (which ? ctl->cv_t : ctl->ac_t) + 1;
-  const float bc1 = 1.0f - powf(0.9f, (float)t), bc2 = 1.0f - powf(0.999f, (float)t);
-  const float lr = which ? ctl->cv_lr : ctl->ac_lr;
-  const float lr_bc1 = lr / bc1, isq_bc2 = 1.0f / sqrtf(bc2);
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-    float m = M[i], v = V[i];
-    P[i] = adam1x(P[i], G[i] * inv_w * clip, m, v, lr_bc1, isq_bc2);
-    M[i] = m; V[i] = v;
-  }
+  float s = 0.0f;
+  for (int i = threadIdx.x; i < nparts; i += 256) s += D.sqn_part[which * SDXP_SQN_STRIDE + i];
+  adam_sweep<adam1x>(D, which, fold_gn2(D.ctrl, which, s));
 }
 __global__ void k_apply_fin2(SdxpDev D) {
   SdxpCtrl* ctl = D.ctrl;
-  ctl->cv_t += 1; ctl->cv_b1pow *= 0.9; ctl->cv_b2pow *= 0.999; ctl->cv_gnorm = sqrtf(ctl->gn2_cv);
-  ctl->ac_t += 1; ctl->ac_b1pow *= 0.9; ctl->ac_b2pow *= 0.999; ctl->ac_gnorm = sqrtf(ctl->gn2_ac);
-  const float kl = D.ac_g[D.g_tail] / (float)ctl->world;
-  if (D.adaptive_lr) {   // legacy schedule after every minibatch, on the rank-averaged KL (PS:306-312)
-    if (kl > 2.0f * D.kl_threshold) ctl->ac_lr = fmaxf(ctl->ac_lr / 1.5f, 1e-6f);
-    if (kl < 0.5f * D.kl_threshold) ctl->ac_lr = fminf(ctl->ac_lr * 1.5f, 1e-2f);
-  }
+  ppo_adam_advance(*ctl, 1);
+  ppo_adam_advance(*ctl, 0);
+  ppo_lr_advance(*ctl, D, D.ac_g[D.g_tail] / (float)ctl->world);
 }
 // grid of k_grad_all_w / k_apply_factors_fused: four trunk-layer rows of one network per workgroup, then nhb head blocks (one output per thread, + one for the tails)
 struct ApplyGrid { int nb, Kmax; };
@@ -1763,10 +1659,8 @@ __global__ __launch_bounds__(256, 6) void k_apply_factors_fused(SdxpDev D, unsig
   if (!s_ok) return;   // an earlier launch timed out at its ticket: nothing is applied until the host has looked (sdxp_update_status)
   // ---- what this launch needs of the control block (read before the ticket: workgroup 0 advances the block behind it)
   const float inv_w = 1.0f / (float)ctl->world;
-  const int t_ac = ctl->ac_t + 1, t_cv = ctl->cv_t + 1;
-  const float lr_ac = ctl->ac_lr, lr_cv = ctl->cv_lr;
-  const float ac_lr_bc1 = lr_ac / (1.0f - powf(0.9f, (float)t_ac)), ac_isq = 1.0f / sqrtf(1.0f - powf(0.999f, (float)t_ac));
-  const float cv_lr_bc1 = lr_cv / (1.0f - powf(0.9f, (float)t_cv)), cv_isq = 1.0f / sqrtf(1.0f - powf(0.999f, (float)t_cv));
+  const PpoAdamScales sa = ppo_adam_scales(ctl->ac_lr, ctl->ac_t + 1), sv = ppo_adam_scales(ctl->cv_lr, ctl->cv_t + 1);
+  const float ac_lr_bc1 = sa.lr_bc1, ac_isq = sa.isq_bc2, cv_lr_bc1 = sv.lr_bc1, cv_isq = sv.isq_bc2;
   // ---- the job of this workgroup (the map of k_grad_all_w): four rows of a trunk layer of one network, or a slice of the heads
   const int nb0 = 3 * ((D.units[0] + 3) / 4), nb1 = 3 * ((D.units[1] + 3) / 4), nb2 = 3 * ((D.units[2] + 3) / 4);
   int b = blockIdx.x, l = -1;
@@ -1931,8 +1825,7 @@ __global__ __launch_bounds__(256, 6) void k_apply_factors_fused(SdxpDev D, unsig
   __syncthreads();
   if (!s_ok) return;
   const float n2_ac = s_n2[0], n2_cv = s_n2[1];
-  const float clip_ac = D.truncate_grads ? fminf(1.0f, D.grad_norm / (sqrtf(n2_ac) + 1e-6f)) : 1.0f;
-  const float clip_cv = D.truncate_grads ? fminf(1.0f, D.grad_norm / (sqrtf(n2_cv) + 1e-6f)) : 1.0f;
+  const float clip_ac = ppo_clip_scale(D, sqrtf(n2_ac)), clip_cv = ppo_clip_scale(D, sqrtf(n2_cv));
   // ---- Adam of the elements this workgroup holds (k_adam3's arithmetic: adam1x(P, G * inv_w * clip, ...))
   if (l >= 0) {
     if (valid) {
@@ -1974,13 +1867,9 @@ __global__ __launch_bounds__(256, 6) void k_apply_factors_fused(SdxpDev D, unsig
   if (blockIdx.x == 0 && tid == 0) {
     __hip_atomic_store(gen, tag_gen + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     ctl->gn2_ac = n2_ac; ctl->gn2_cv = n2_cv;
-    ctl->cv_t += 1; ctl->cv_b1pow *= 0.9; ctl->cv_b2pow *= 0.999; ctl->cv_gnorm = sqrtf(n2_cv);
-    ctl->ac_t += 1; ctl->ac_b1pow *= 0.9; ctl->ac_b2pow *= 0.999; ctl->ac_gnorm = sqrtf(n2_ac);
-    const float kl = __hip_atomic_load(&D.ac_g[D.g_tail], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) / (float)ctl->world;
-    if (D.adaptive_lr) {
-      if (kl > 2.0f * D.kl_threshold) ctl->ac_lr = fmaxf(ctl->ac_lr / 1.5f, 1e-6f);
-      if (kl < 0.5f * D.kl_threshold) ctl->ac_lr = fminf(ctl->ac_lr * 1.5f, 1e-2f);
-    }
+    ppo_adam_advance(*ctl, 1);
+    ppo_adam_advance(*ctl, 0);
+    ppo_lr_advance(*ctl, D, __hip_atomic_load(&D.ac_g[D.g_tail], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) / (float)ctl->world);
   }
 }
 // 1 when the shapes fit the one-launch apply's tables and every workgroup can be resident at once on the current device (its grid-wide ticket)

@@ -1000,6 +1000,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       }
     }
     const float invM = 1.0f / (float)MB;
+    // (the loss phase restates sdxp_ppo_terms.h in place: calling its functions here changed this kernel's register allocation and schedule)
     {
       float r_nlp = 0.0f, r_kl = 0.0f, r_bl = 0.0f, r_ent = 0.0f;
       if (tid < MB * 32) {

@@ -74,6 +74,22 @@ def build_gemm(force=False):
     return _GEMM_SO
 
 
+_PPO_TERMS_SO = os.path.join(HERE, "libsdx_emu_ppo_terms.so")
+
+
+def build_ppo_terms(force=False):
+    """seqdex_amd/csrc/sdxp_ppo_terms.h (the PPO update's loss terms and step rules: functions of scalars) behind the plain C loops of
+    ppo_terms_driver.cpp"""
+    src = os.path.join(HERE, "ppo_terms_driver.cpp")
+    deps = [src, os.path.abspath(__file__), os.path.join(HERE, "include", "hip", "hip_runtime.h"), os.path.join(ROOT, "include", "seqdex.h")] + \
+        [os.path.join(CSRC, f) for f in ("sdxp_ppo_terms.h", "sdxp_types.h", "sdx_common.h")]
+    if not force and os.path.exists(_PPO_TERMS_SO) and all(os.path.getmtime(_PPO_TERMS_SO) >= os.path.getmtime(d) for d in deps):
+        return _PPO_TERMS_SO
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-omit-frame-pointer", "-w", "-x", "c++",
+                           "-I", os.path.join(HERE, "include"), "-I", CSRC, "-shared", "-Wl,-Bsymbolic", "-Wl,--no-undefined", "-o", _PPO_TERMS_SO, src])
+    return _PPO_TERMS_SO
+
+
 def sim_lib():
     """ctypes handle of the emulated simulator library with the prototypes of seqdex_amd/_abi.py::load_library"""
     global _sim_lib
