@@ -308,6 +308,20 @@ typedef struct {
   sdx_dr_attr brick_friction;/* actor_params.lego.rigid_shape_properties.friction: every free brick            */
 } sdx_dr_desc;
 
+/* One of randomization_params.observations / .actions (BaseTask.apply_randomizations BT:259-329, applied by BaseTask.step BT:131-132,
+ * 149-150): noise on the policy's observation or on the executed action (sdx_set_noise below).
+ *   distribution SDX_DR_GAUSSIAN (range = [mu, sigma]) or SDX_DR_UNIFORM (range = [lo, hi]); SDX_DR_NONE = this side is off
+ *   range            the white part, drawn anew every step;  range_correlated  the correlated part, one draw per (env, column) that
+ *                    stays until the next non-env randomization ([0, 0] = none) */
+typedef struct {
+  int32_t distribution;      /* sdx_dr_distribution without SDX_DR_LOGUNIFORM */
+  int32_t operation;         /* sdx_dr_operation */
+  int32_t schedule;          /* sdx_dr_schedule */
+  int32_t schedule_steps;
+  float range[2];            /* [mu, sigma] or [lo, hi] of the white part */
+  float range_correlated[2]; /* [mu, sigma] or [lo, hi] of the correlated part */
+} sdx_noise_attr;
+
 typedef struct sdx_sim* sdx_handle;
 
 /* Scene build: replaces create_sim/add_ground/load_asset/create_env/create_actor/prepare_sim
@@ -376,6 +390,35 @@ int sdx_set_indexed(sdx_handle h, int32_t id, const float* src_dev, const int32_
  * physics returns to the scene constants.  Stream-ordered; frequency >= 1, enums, finite ranges, lo <= hi (uniform, loguniform: lo > 0),
  * sigma >= 0 (gaussian) are checked (SDX_ERR_INVALID). */
 int sdx_set_randomization(sdx_handle h, const sdx_dr_desc* desc, void* stream);
+
+/* Observation and action noise (randomization_params.observations / .actions).  NULL or distribution SDX_DR_NONE
+ * turns a side off; with both off nothing is launched.  Needs randomization to be on (a desc whose attributes are all SDX_DR_NONE is
+ * enough), because the noise is a pure function of that path's counters: SDX_ERR_STATE otherwise.  sdx_set_randomization(NULL) turns the
+ * noise off too.  Stream-ordered (the next sdx_step / sdx_pre_physics / sdx_post_physics uses the new blocks).  Checked
+ * (SDX_ERR_INVALID with a message): distribution gaussian or uniform, known operation and schedule, schedule_steps > 0 with a
+ * schedule, finite numbers, sigma >= 0 (gaussian) and lo <= hi (uniform) in range and range_correlated.
+ *   schedule  s = the factor of sdx_set_randomization, evaluated at SDX_T_DR_FRAME[1] (the frame of the last non-env randomization: the
+ *             reference freezes the scaled numbers when it rebuilds its lambda at that event, BT:260-329).  Gaussian additive: all
+ *             four numbers x s; gaussian scaling: sigma x s, mu x s + (1 - s); uniform additive: all four ends x s; uniform scaling:
+ *             end x s + (1 - s) - for both parts.  (A scaling block at s = 0 therefore multiplies by 2: both parts become 1.)
+ *   operand   per (env, column): corr + white.  white = mu + sigma z or lo + (hi - lo) u, drawn anew at every step.  corr = mu_c +
+ *             sigma_c z or, for the uniform distribution too, lo_c + (hi_c - lo_c) z with z standard normal (BT:326); it changes when
+ *             SDX_T_DR_FRAME[1] does: some env resets and frame - last_rand_frame >= frequency, whether or not gravity is randomized.
+ *   random    column pair p = column / 2 shares one hash(seed ^ tag, env x 256 + p, counter): u0, u1 = its two 24-bit uniforms,
+ *             z = sqrt(-2 log u0) x (cos, sin)(2 pi u1) and u = (u0, u1) for the (even, odd) column.  counter = gravity's draw count
+ *             (corr) or the step counter (white; actions see the steps completed before this one, observations those including it);
+ *             tags 0x0B5C / 0x0B57 (observations corr / white), 0xAC7C / 0xAC77 (actions).  Nothing depends on N or launch order, no
+ *             state is kept: sdx_state_save_all / restore_all reproduce the noise.
+ *   observations  SDX_T_OBS_CLAMPED = clamp(op(SDX_T_OBS, operand), +-clip_obs) over every column of the row, written by sdx_step and
+ *             sdx_post_physics after the task's kernel (not by sdx_compute_observations: BT:149 sits in step).  SDX_T_OBS stays the clean
+ *             row (so the frames GraspSim stacks carry no earlier noise, GS:1330-1332), SDX_T_STATES* and SDX_T_TVALUE_OBS get none.
+ *   actions   a' = op(clamp(a, +-clip_actions), operand), not clamped again (VR:166, then BT:131); SDX_T_ACTIONS, the targets and the
+ *             action columns of the observation see a'.  The caller's buffer is not written.  Uses the blocks and counters in force
+ *             before this step's re-sampling; the observations use those after it.
+ *   zero      an additive block whose four scaled numbers are all zero (frame 0 of a linear schedule) leaves its tensor bit for bit
+ *             what it is without noise.
+ * op(x, o) = x + o (additive) or x o (scaling). */
+int sdx_set_noise(sdx_handle h, const sdx_noise_attr* observations, const sdx_noise_attr* actions, void* stream);
 
 /* View camera: depth, label and colour images of the listed envs from the current SDX_T_ROOT / SDX_T_RB, for
  * looking at the engine; no task's step launches it.  k_seg_camera's pinhole model: f = normalize(target - pos), r = normalize(f x up),

@@ -33,6 +33,8 @@ struct sdx_sim {
   struct TensorInfo { void* ptr; int64_t shape[4]; int ndim; int dtype; } tinfo[SDX_T_COUNT];
   bool has_piles = false;
   sdx_dr_desc dr{};           // the randomization in force (meaningful while buf.dr_on != nullptr)
+  sdx_noise_attr noise_obs{}, noise_act{};   // sdx_set_noise: distribution SDX_DR_NONE = off (always off while randomization is off)
+  float* act_pre = nullptr;   // [N,23] the clamped and noised actions of this step (scratch of k_noise -> k_pre_physics)
   SdxStateTab st_tab{};       // what an env's state is (sdx_state.h); d_st_tab: its device copy
   SdxStateTab* d_st_tab = nullptr;
   std::string err;
@@ -107,11 +109,12 @@ __device__ __forceinline__ float dr_u(uint64_t hs, int which) {   // uniform in 
   const uint32_t b = which ? (uint32_t)(hs >> 16) & 0xffffffu : (uint32_t)(hs >> 40);
   return ((float)b + 0.5f) * (1.0f / 16777216.0f);
 }
-__device__ __forceinline__ float dr_sched(const sdx_dr_attr& a, long long frame) {
-  if (a.schedule == SDX_DR_SCHED_LINEAR) return (float)(frame < a.schedule_steps ? frame : (long long)a.schedule_steps) / (float)a.schedule_steps;
-  if (a.schedule == SDX_DR_SCHED_CONSTANT) return frame < a.schedule_steps ? 0.0f : 1.0f;
+__device__ __forceinline__ float dr_sched(int schedule, int steps, long long frame) {
+  if (schedule == SDX_DR_SCHED_LINEAR) return (float)(frame < steps ? frame : (long long)steps) / (float)steps;
+  if (schedule == SDX_DR_SCHED_CONSTANT) return frame < steps ? 0.0f : 1.0f;
   return 1.0f;
 }
+__device__ __forceinline__ float dr_sched(const sdx_dr_attr& a, long long frame) { return dr_sched(a.schedule, a.schedule_steps, frame); }
 __device__ __forceinline__ float dr_bucket(float lo, float hi, int k, int nb) { return lo + (hi - lo) * (float)k / (float)nb; }
 // the randomized value of a quantity whose scene value is v0 (s > 0; s == 0 leaves v0)
 __device__ float dr_value(const sdx_dr_attr& a, float s, uint64_t hs, float v0) {
@@ -222,6 +225,114 @@ __global__ __launch_bounds__(128) void k_dr_sample(const SdxConst* __restrict__ 
 static void dr_sample(sdx_sim* h, int first, hipStream_t st, const uint8_t* mask = nullptr) {
   hipLaunchKernelGGL(k_dr_gravity, dim3(1), dim3(256), 0, st, h->d_const, h->buf, h->dr, first, mask);
   hipLaunchKernelGGL(k_dr_sample, dim3(h->buf.N), dim3(128), 0, st, h->d_const, h->buf, h->dr, first, mask);
+}
+
+// ---------------------------------------------------------------- observation / action noise (include/seqdex.h sdx_set_noise,
+// DESIGN.md section 18).  The operand of (env, column) is a pure function of the seed and three counters the randomization path keeps:
+// dr_frame[1] (schedule), dr_draw[N] (correlated part) and step_count (white part).  Column pair p = column / 2 shares one hash per part:
+// sdx_hash(seed ^ tag, env * SDX_NOISE_PAIRS + p, counter).
+#define SDX_NOISE_TAG_OBS 0x0B50ull   // | SDX_NOISE_CORR / SDX_NOISE_WHITE
+#define SDX_NOISE_TAG_ACT 0xAC70ull
+#define SDX_NOISE_CORR 0xCull
+#define SDX_NOISE_WHITE 0x7ull
+#define SDX_NOISE_PAIRS 256           // streams per env (the widest row has 396 / 2 pairs)
+// The sampler's Box-Muller (dr_value) on the two uniforms of one hash, both outputs: the pair's first (cos) or second (sin) standard
+// normal.  log, cos and sin are rounded ONCE from double precision here: with the device's float versions 0.4 % of the draws lay 3 ulp
+// (2 in 47 000: 4 ulp) from the float32 restatement the noise is held to within 2 ulp of.
+__device__ __forceinline__ float noise_normal(uint64_t hs, int second) {
+#pragma clang fp contract(off)
+  const float r = sqrtf(-2.0f * (float)log((double)dr_u(hs, 0))), th = 6.28318530718f * dr_u(hs, 1);
+  return r * (float)(second ? sin((double)th) : cos((double)th));
+}
+// the scaled numbers the reference freezes at a non-env randomization (BT:279-291,309-318): p[0..1] white, p[2..3] correlated
+__device__ __forceinline__ void noise_scaled(const sdx_noise_attr& a, float s, float p[4]) {
+#pragma clang fp contract(off)
+  const bool scaling = a.operation == SDX_DR_SCALING, gauss = a.distribution == SDX_DR_GAUSSIAN;
+  for (int k = 0; k < 2; ++k) {
+    const float* r = k ? a.range_correlated : a.range;
+    p[2 * k] = scaling ? r[0] * s + (1.0f - s) : r[0] * s;
+    p[2 * k + 1] = scaling && !gauss ? r[1] * s + (1.0f - s) : r[1] * s;   // a sigma is only ever scaled
+  }
+}
+// corr + white of one column (BT:299-301,326-327); the correlated part is a NORMAL draw for the uniform distribution too
+__device__ __forceinline__ float noise_operand(bool gauss, const float p[4], uint64_t hc, uint64_t hw, int odd) {
+#pragma clang fp contract(off)
+  const float zc = noise_normal(hc, odd);
+  const float corr = gauss ? p[2] + p[3] * zc : p[2] + (p[3] - p[2]) * zc;
+  const float white = gauss ? p[0] + p[1] * noise_normal(hw, odd) : p[0] + (p[1] - p[0]) * dr_u(hw, odd);
+  return corr + white;
+}
+// One thread per (env, group of 4 columns) = two column pairs.  W % 4 == 0 (GraspSim's 396 columns): one 16-byte load and one 16-byte
+// store per thread; the other widths (186, 75, the 23 action columns) go column by column and the last group of a row is partial.
+// act == 0: dst = clamp(op(src, operand), +-clip_obs) (src = obs, dst = obs_c, which k_post_physics has filled with clamp(obs));
+// act == 1: dst = op(clamp(src, +-clip_actions), operand) (src = the caller's actions, dst = the buffer k_pre_physics then reads).
+// An additive block whose scaled numbers are all zero changes nothing: x + 0 would turn a -0 into +0.
+__global__ __launch_bounds__(256) void k_noise(const SdxConst* __restrict__ C, SdxBuf B, sdx_noise_attr a, const float* __restrict__ src,
+                                               float* __restrict__ dst, int W, int act) {
+#pragma clang fp contract(off)
+  const int G = (W + 3) >> 2;
+  const int tid = blockIdx.x * 256 + threadIdx.x;
+  if (tid >= B.N * G) return;
+  const int e = tid / G, c0 = (tid - e * G) * 4;
+  float p[4];
+  noise_scaled(a, dr_sched(a.schedule, a.schedule_steps, B.dr_frame[1]), p);
+  const bool additive = a.operation == SDX_DR_ADDITIVE, gauss = a.distribution == SDX_DR_GAUSSIAN;
+  const bool zero = additive && p[0] == 0.0f && p[1] == 0.0f && p[2] == 0.0f && p[3] == 0.0f;   // wave-uniform
+  if (zero && !act) return;
+  const float clip = act ? C->sc.clip_actions : C->sc.clip_obs;
+  const bool vec = (W & 3) == 0;
+  const int n = W - c0 < 4 ? W - c0 : 4;
+  const size_t at = (size_t)e * W + c0;
+  float x[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (vec) {
+    const f4v v = *reinterpret_cast<const f4v*>(src + at);
+    x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+  } else {
+    for (int k = 0; k < n; ++k) x[k] = src[at + k];
+  }
+  if (act) for (int k = 0; k < 4; ++k) x[k] = clampf(x[k], -clip, clip);
+  if (!zero) {
+    const uint64_t tag = B.seed ^ (act ? SDX_NOISE_TAG_ACT : SDX_NOISE_TAG_OBS);
+    const uint64_t ccorr = (uint64_t)B.dr_draw[B.N], cwhite = (uint64_t)B.step_count[0];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      if (2 * q >= n) break;
+      const uint64_t stream = (uint64_t)e * SDX_NOISE_PAIRS + (uint64_t)((c0 >> 1) + q);
+      const uint64_t hc = sdx_hash(tag ^ SDX_NOISE_CORR, stream, ccorr), hw = sdx_hash(tag ^ SDX_NOISE_WHITE, stream, cwhite);
+#pragma unroll
+      for (int odd = 0; odd < 2; ++odd) {
+        const int k = 2 * q + odd;
+        if (k >= n) break;
+        const float o = noise_operand(gauss, p, hc, hw, odd);
+        x[k] = additive ? x[k] + o : x[k] * o;
+      }
+    }
+    if (!act) for (int k = 0; k < 4; ++k) x[k] = clampf(x[k], -clip, clip);
+  }
+  if (vec) {
+    f4v v;
+    v.x = x[0]; v.y = x[1]; v.z = x[2]; v.w = x[3];
+    *reinterpret_cast<f4v*>(dst + at) = v;
+  } else {
+    for (int k = 0; k < n; ++k) dst[at + k] = x[k];
+  }
+}
+static void noise_launch(sdx_sim* h, const sdx_noise_attr& a, const float* src, float* dst, int W, int act, hipStream_t st) {
+  const long long threads = (long long)h->buf.N * ((W + 3) / 4);
+  hipLaunchKernelGGL(k_noise, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, h->d_const, h->buf, a, src, dst, W, act);
+}
+// the actions k_pre_physics takes.  With action noise on: h->act_pre, already clamped and noised (flag 8), computed here - before this
+// step's re-sampling, from the blocks and counters in force until now.  The caller's buffer is only read.
+static const float* noise_actions(sdx_sim* h, const float* actions_dev, int* flags, hipStream_t st) {
+  if (h->noise_act.distribution == SDX_DR_NONE) return actions_dev;
+  noise_launch(h, h->noise_act, actions_dev, h->act_pre, SDX_NDOF, 1, st);
+  *flags |= 8;
+  return h->act_pre;
+}
+// post_physics_step, then the observation noise of BaseTask.step (BT:149-150) on the policy's row
+static void post_physics_step(sdx_sim* h, hipStream_t st) {
+  sdxk_post_physics(h->d_const, &h->buf, 1, st);
+  if (h->noise_obs.distribution != SDX_DR_NONE) noise_launch(h, h->noise_obs, h->buf.obs, h->buf.obs_c, h->buf.obs_w, 0, st);
 }
 
 // ---------------------------------------------------------------- sim snapshots (include/seqdex.h sdx_state_*)
@@ -514,6 +625,7 @@ extern "C" int sdx_create(const sdx_scene_desc* scene, int32_t num_envs, int32_t
     ALLOC(tvt_h, (size_t)N * (1024 + 512 + 128 + 4));
   }
 #undef ALLOC
+  if ((rc = dalloc(h, &h->act_pre, (size_t)N * SDX_NDOF)) != SDX_OK) { g_create_err = h->err; sdx_destroy(h); return rc; }
   set_tensor(h, SDX_T_ROOT, B.root, SDX_F32, {(int64_t)N * SDX_ACTORS, 13});
   set_tensor(h, SDX_T_DOF, B.dof, SDX_F32, {(int64_t)N * SDX_NDOF, 2});
   set_tensor(h, SDX_T_RB, B.rb, SDX_F32, {N, SDX_BODIES, 13});
@@ -715,6 +827,8 @@ extern "C" int sdx_set_randomization(sdx_handle h, const sdx_dr_desc* desc, void
   hipStream_t st = (hipStream_t)stream;
   if (!desc) {
     h->buf.dr_on = nullptr;
+    h->noise_obs = sdx_noise_attr{};   // the noise lives on this path's counters: off with it
+    h->noise_act = sdx_noise_attr{};
     hipLaunchKernelGGL(k_dr_defaults, dim3(h->buf.N), dim3(128), 0, st, h->d_const, h->buf);
     return check_launch(h, "sdx_set_randomization");
   }
@@ -729,10 +843,46 @@ extern "C" int sdx_set_randomization(sdx_handle h, const sdx_dr_desc* desc, void
   return check_launch(h, "sdx_set_randomization");
 }
 
+// what sdx_set_noise checks of one block; *why names the first thing that is wrong
+static bool noise_attr_ok(const sdx_noise_attr& a, const char** why) {
+  if (a.distribution == SDX_DR_NONE) return true;
+  *why = "distribution must be SDX_DR_NONE, SDX_DR_GAUSSIAN or SDX_DR_UNIFORM";
+  if (a.distribution != SDX_DR_GAUSSIAN && a.distribution != SDX_DR_UNIFORM) return false;
+  *why = "operation must be SDX_DR_ADDITIVE or SDX_DR_SCALING";
+  if (a.operation != SDX_DR_ADDITIVE && a.operation != SDX_DR_SCALING) return false;
+  *why = "unknown schedule, or a schedule without schedule_steps > 0";
+  if (a.schedule < SDX_DR_SCHED_NONE || a.schedule > SDX_DR_SCHED_CONSTANT || (a.schedule != SDX_DR_SCHED_NONE && a.schedule_steps <= 0)) return false;
+  *why = "range and range_correlated must be finite";
+  if (!std::isfinite(a.range[0]) || !std::isfinite(a.range[1]) || !std::isfinite(a.range_correlated[0]) || !std::isfinite(a.range_correlated[1])) return false;
+  *why = "a gaussian's sigma must be >= 0 (range[1], range_correlated[1])";
+  if (a.distribution == SDX_DR_GAUSSIAN && (a.range[1] < 0.0f || a.range_correlated[1] < 0.0f)) return false;
+  *why = "uniform needs lo <= hi (range, range_correlated)";
+  if (a.distribution == SDX_DR_UNIFORM && (a.range[0] > a.range[1] || a.range_correlated[0] > a.range_correlated[1])) return false;
+  return true;
+}
+extern "C" int sdx_set_noise(sdx_handle h, const sdx_noise_attr* observations, const sdx_noise_attr* actions, void* stream) {
+  if (!h) return SDX_ERR_INVALID;
+  (void)stream;   // the blocks travel with the launches of the calls that follow: nothing to enqueue here
+  const sdx_noise_attr off{};
+  const sdx_noise_attr &o = observations ? *observations : off, &a = actions ? *actions : off;
+  const char* why = "";
+  if (!noise_attr_ok(o, &why)) { h->err = std::string("sdx_set_noise: observations: ") + why; return SDX_ERR_INVALID; }
+  if (!noise_attr_ok(a, &why)) { h->err = std::string("sdx_set_noise: actions: ") + why; return SDX_ERR_INVALID; }
+  if (!h->buf.dr_on) {
+    h->err = "sdx_set_noise: randomization is off (call sdx_set_randomization first, an all-SDX_DR_NONE desc is enough): the noise follows its frame and refresh counters";
+    return SDX_ERR_STATE;
+  }
+  h->noise_obs = o;
+  h->noise_act = a;
+  return SDX_OK;
+}
+
 extern "C" int sdx_pre_physics(sdx_handle h, const float* actions_dev, void* stream) {
   if (!h || !actions_dev) return SDX_ERR_INVALID;
+  int flags = 1 | 4;
+  const float* act = noise_actions(h, actions_dev, &flags, (hipStream_t)stream);
   if (h->buf.dr_on) dr_sample(h, 0, (hipStream_t)stream);   // before this step's resets (BT:229-260 runs inside reset_idx)
-  sdxk_pre_physics(h->d_const, &h->buf, actions_dev, nullptr, nullptr, 1 | 4, (hipStream_t)stream);
+  sdxk_pre_physics(h->d_const, &h->buf, act, nullptr, nullptr, flags, (hipStream_t)stream);
   return check_launch(h, "sdx_pre_physics");
 }
 extern "C" int sdx_simulate(sdx_handle h, void* stream) {
@@ -742,7 +892,7 @@ extern "C" int sdx_simulate(sdx_handle h, void* stream) {
 }
 extern "C" int sdx_post_physics(sdx_handle h, void* stream) {
   if (!h) return SDX_ERR_INVALID;
-  sdxk_post_physics(h->d_const, &h->buf, 1, (hipStream_t)stream);
+  post_physics_step(h, (hipStream_t)stream);
   return check_launch(h, "sdx_post_physics");
 }
 extern "C" int sdx_compute_observations(sdx_handle h, void* stream) {
@@ -810,32 +960,34 @@ static int search_reset_if_needed(sdx_handle h, hipStream_t st, int64_t* progres
 extern "C" int sdx_step(sdx_handle h, const float* actions_dev, void* stream) {
   if (!h || !actions_dev) return SDX_ERR_INVALID;
   hipStream_t st = (hipStream_t)stream;
+  int targets = 4;                          // k_pre_physics flags of the action -> targets launch
+  const float* act = noise_actions(h, actions_dev, &targets, st);
   if (h->buf.dr_on) dr_sample(h, 0, st);   // before any reset physics of this step, Orient's / Search's settling launches included
   if (h->h_const.sc.task_kind == SDX_TASK_SEARCH) {
     int64_t p0 = 0;
     const int rc = search_reset_if_needed(h, st, &p0);
     if (rc != SDX_OK) return rc;
-    sdxk_pre_physics(h->d_const, &h->buf, actions_dev, nullptr, nullptr, 4, st);
+    sdxk_pre_physics(h->d_const, &h->buf, act, nullptr, nullptr, targets, st);
     sdxk_physics(h->d_const, &h->buf, st);
     if ((float)(p0 + 1) >= h->h_const.sc.max_episode_length - 1.0f) {                  // SE:992-1019: park the hand, one more step, render
       sdxk_search_set_hand(h->d_const, &h->buf, nullptr, 1, st);
       sdxk_physics(h->d_const, &h->buf, st);
       sdxk_seg_camera(h->d_const, &h->buf, st);
     }
-    sdxk_post_physics(h->d_const, &h->buf, 1, st);
+    post_physics_step(h, st);
     return check_launch(h, "sdx_step");
   }
   if (h->h_const.sc.task_kind == SDX_TASK_ORIENT) {
     const int rc = orient_reset_if_needed(h, st);
     if (rc != SDX_OK) return rc;
-    sdxk_pre_physics(h->d_const, &h->buf, actions_dev, nullptr, nullptr, 4, st);
+    sdxk_pre_physics(h->d_const, &h->buf, act, nullptr, nullptr, targets, st);
     sdxk_physics(h->d_const, &h->buf, st);
-    sdxk_post_physics(h->d_const, &h->buf, 1, st);
+    post_physics_step(h, st);
     return check_launch(h, "sdx_step");
   }
-  sdxk_pre_physics(h->d_const, &h->buf, actions_dev, nullptr, nullptr, 1 | 4, st);
+  sdxk_pre_physics(h->d_const, &h->buf, act, nullptr, nullptr, 1 | targets, st);
   sdxk_physics(h->d_const, &h->buf, st);   // controlFrequencyInv = 1 (EG:18)
-  sdxk_post_physics(h->d_const, &h->buf, 1, st);
+  post_physics_step(h, st);
   return check_launch(h, "sdx_step");
 }
 // Not part of include/seqdex.h: the scripted stand-in for a trained grasp policy that the chain benchmark and its tests drive the grasp

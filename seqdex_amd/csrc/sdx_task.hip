@@ -420,7 +420,8 @@ __device__ __forceinline__ float search_reward(const PostDerived& D, const float
 }
 
 // ------------------------------------------------------------------------------------------------ K1 + K2
-// flags: bit0 reset envs with reset_buf != 0; bit1 reset envs with ext_mask != 0; bit2 compute targets.
+// flags: bit0 reset envs with reset_buf != 0; bit1 reset envs with ext_mask != 0; bit2 compute targets; bit3 actions_in is already
+// clamped and carries the action noise (sdx_capi.hip k_noise): not clamped a second time.
 // Every `switch (sc.task_kind)` is wave-uniform; an unknown kind runs GraspSim's per-step code.
 __global__ __launch_bounds__(SDX_WAVE) void k_pre_physics(const SdxConst* __restrict__ C, SdxBuf B, const float* __restrict__ actions_in,
                                                           const uint8_t* __restrict__ ext_mask, const int32_t* __restrict__ ext_choice, int flags) {
@@ -482,7 +483,8 @@ __global__ __launch_bounds__(SDX_WAVE) void k_pre_physics(const SdxConst* __rest
   // ---- 5. action -> targets (GS:1570-1638); actions are clamped to +-clip_actions first (VR:166)
   float a = 0.0f;
   if (lane < SDX_NDOF) {
-    a = clampf(actions_in[(size_t)e * SDX_NDOF + lane], -sc.clip_actions, sc.clip_actions);
+    a = actions_in[(size_t)e * SDX_NDOF + lane];
+    if (!(flags & 8)) a = clampf(a, -sc.clip_actions, sc.clip_actions);
     B.actions[(size_t)e * SDX_NDOF + lane] = a;                                   // GS:1570
   }
   if (lane < 42) s_J[lane] = B.jac[(size_t)e * 42 + lane];

@@ -1,9 +1,14 @@
-"""Domain randomization: `cfg["task"]["randomization_params"]` (the reference's schema, BT:229-420) -> sdx_dr_desc of include/seqdex.h.
+"""Domain randomization: `cfg["task"]["randomization_params"]` (the reference's schema, BT:229-420) -> sdx_dr_desc and the two
+sdx_noise_attr of include/seqdex.h.
 
-The sampling itself runs on the device (sdx_set_randomization, sdx_step); this module only parses and validates the YAML block and reports
-what it does with every entry.  The rules are written out in DESIGN.md section 18."""
+The sampling itself runs on the device (sdx_set_randomization, sdx_set_noise, sdx_step); this module only parses and validates the YAML
+block and reports what it does with every entry: `parse` the physics descriptor, `parse_noise` the `observations` / `actions` blocks
+that BaseTask.step applies (BT:131-132,149-150).  The rules are written out in DESIGN.md section 18."""
 import ctypes as C
+import math
 import warnings
+
+from ._abi import NoiseAttr
 
 DISTRIBUTIONS = {"gaussian": 1, "uniform": 2, "loguniform": 3}
 OPERATIONS = {"additive": 1, "scaling": 2}
@@ -22,8 +27,11 @@ SUPPORTED = {
     ("actor_params", "lego", "rigid_body_properties", "mass"): "brick_mass",
     ("actor_params", "lego", "rigid_shape_properties", "friction"): "brick_friction",
 }
-_NOOP_TOP = {"observations": "observation noise: no BlockAssembly task of the reference applies it (dr_randomizations is never read)",
-             "actions": "action noise: no BlockAssembly task of the reference applies it (dr_randomizations is never read)"}
+# not part of the physics descriptor `parse` builds: `parse_noise` reads these two blocks (SdxSim.set_noise applies them)
+_NOOP_TOP = {"observations": "observation noise: not a physics parameter; parse_noise() reads it and SdxSim.set_noise() applies it",
+             "actions": "action noise: not a physics parameter; parse_noise() reads it and SdxSim.set_noise() applies it"}
+NOISE_KEYS = {"range", "range_correlated", "operation", "distribution", "schedule", "schedule_steps"}
+NOISE_DISTRIBUTIONS = {"gaussian": 1, "uniform": 2}
 _NOOP_PROP = {"tendon_properties": "the hand has no tendons", "color": "visual only"}
 _UNSUPPORTED = {"scale": "per-env brick scale needs per-env collision geometry (out of scope)"}
 _ACTOR_PROPS = {"hand": {"dof_properties", "rigid_body_properties", "rigid_shape_properties"},
@@ -136,3 +144,60 @@ def identity_desc(frequency=1):
     d = DrDesc()
     d.frequency = frequency
     return d
+
+
+def _pair(name, key, v):
+    if not isinstance(v, (list, tuple)) or len(v) != 2 or not all(isinstance(x, (int, float)) and not isinstance(x, bool) for x in v):
+        raise ValueError("randomization_params.%s.%s: expected two numbers ([mu, sigma] or [lo, hi]), got %r" % (name, key, v))
+    if not all(math.isfinite(float(x)) for x in v):
+        raise ValueError("randomization_params.%s.%s: not finite: %r" % (name, key, v))
+    return float(v[0]), float(v[1])
+
+
+def _noise_attr(name, spec):
+    if not isinstance(spec, dict):
+        raise ValueError("randomization_params.%s: expected a mapping, got %r" % (name, spec))
+    extra = set(spec) - NOISE_KEYS
+    if extra:
+        raise ValueError("randomization_params.%s: unknown key(s) %s" % (name, sorted(extra)))
+    a = NoiseAttr()
+    for key, table in (("distribution", NOISE_DISTRIBUTIONS), ("operation", OPERATIONS), ("schedule", SCHEDULES)):
+        if spec.get(key) not in table:
+            raise ValueError("randomization_params.%s.%s: unknown %s %r" % (name, key, key, spec.get(key)))
+        setattr(a, key, table[spec.get(key)])
+    if a.schedule:
+        steps = spec.get("schedule_steps")
+        if not isinstance(steps, int) or isinstance(steps, bool) or steps <= 0:
+            raise ValueError("randomization_params.%s.schedule_steps: a schedule needs schedule_steps > 0, got %r" % (name, steps))
+        a.schedule_steps = steps
+    if "range" not in spec:
+        raise ValueError("randomization_params.%s.range: missing" % name)
+    for key in ("range", "range_correlated"):
+        lo, hi = _pair(name, key, spec.get(key, [0.0, 0.0]))          # BT:277,307: range_correlated defaults to [0, 0]
+        if a.distribution == NOISE_DISTRIBUTIONS["gaussian"] and hi < 0:
+            raise ValueError("randomization_params.%s.%s: a gaussian's sigma must be >= 0" % (name, key))
+        if a.distribution == NOISE_DISTRIBUTIONS["uniform"] and lo > hi:
+            raise ValueError("randomization_params.%s.%s: lo > hi" % (name, key))
+        getattr(a, key)[0], getattr(a, key)[1] = lo, hi
+    return a
+
+
+def parse_noise(params):
+    """randomization_params -> (observations NoiseAttr or None, actions NoiseAttr or None, report).  Only the `observations` and
+    `actions` blocks are read (the rest is `parse`'s); report = {block: its values as applied} for the blocks present.  Unknown keys,
+    distributions, operations and schedules, a schedule without schedule_steps and a bad range / range_correlated raise ValueError
+    naming the key."""
+    if params is not None and not isinstance(params, dict):
+        raise ValueError("task.randomization_params: expected a mapping")
+    out, rep = [], {}
+    for name in ("observations", "actions"):
+        spec = (params or {}).get(name)
+        if spec is None:
+            out.append(None)
+            continue
+        a = _noise_attr(name, spec)
+        out.append(a)
+        rep[name] = {"distribution": spec["distribution"], "operation": spec["operation"], "schedule": spec.get("schedule"),
+                     "schedule_steps": int(a.schedule_steps), "range": [float(v) for v in spec["range"]],
+                     "range_correlated": [float(v) for v in spec.get("range_correlated", [0.0, 0.0])]}
+    return out[0], out[1], rep

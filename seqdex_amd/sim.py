@@ -312,6 +312,22 @@ class SdxSim:
         self._check(self.lib.sdx_set_randomization(self.h, ptr, stream))
         return report
 
+    def set_noise(self, spec=None, observations=None, actions=None):
+        """observation / action noise (include/seqdex.h sdx_set_noise).  `spec` = a task YAML's
+        randomization_params mapping (its `observations` / `actions` blocks are applied), or ready _abi.NoiseAttr blocks through the
+        keywords; a side that is None is off, set_noise() turns both off.  Randomization must be on (set_randomization first; an
+        identity_desc() is enough).  Returns the parse report of the mapping (None for ready blocks)."""
+        from . import domain_randomization as dr
+        report = None
+        if spec is not None:
+            if observations is not None or actions is not None:
+                raise ValueError("set_noise: pass either the randomization_params mapping or ready blocks, not both")
+            observations, actions, report = dr.parse_noise(spec)
+        self._noise = (observations, actions)     # (kept alive for the call)
+        ptr = [C.byref(a) if a is not None else None for a in self._noise]
+        self._check(self.lib.sdx_set_noise(self.h, ptr[0], ptr[1], self._stream_or_none()))
+        return report
+
     # ------------------------------------------------------------------ sim snapshots (include/seqdex.h sdx_state_*, DESIGN.md section 20)
     def _stream_or_none(self):
         return _stream_ptr(self.device) if self.device.type == "cuda" else None

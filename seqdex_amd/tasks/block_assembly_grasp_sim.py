@@ -97,6 +97,10 @@ class BlockAssemblyGraspSim:
         self.randomize = bool(cfg.get("task", {}).get("randomize", False))
         self.randomization_params = cfg.get("task", {}).get("randomization_params", {})
         self.randomization_report = s.set_randomization(self.randomization_params) if self.randomize else None
+        if self.randomize:
+            # the `observations` / `actions` blocks, which BaseTask.step applies for every task (BT:131-132,149-150): OBS_CLAMPED (what the
+            # agent is handed, VR:171) carries the observation noise, ACTIONS the action noise; obs_buf stays the clean row
+            self.randomization_report["noise"] = s.set_noise(self.randomization_params)
 
     # ------------------------------------------------------------------ BaseTask.step, BT:130-150
     def step(self, actions):

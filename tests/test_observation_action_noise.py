@@ -1,0 +1,245 @@
+"""CPU (-m "not gpu"): observation and action noise (include/seqdex.h sdx_set_noise).
+
+- the YAML parser on the shipped blocks, errors that name the key;
+- the ABI mirror of sdx_noise_attr, the exported symbol, the call order;
+- the noise kernel (sdx_capi.hip k_noise) on the SIMT emulator against the numpy restatement of tests/helpers/noise_restatement.py:
+  zero operand, known operand for every distribution x operation x schedule, correlation and refresh, isolation, actions not clamped
+  twice, independence of N, snapshots.  The bodies are tests/noise_cases.py, shared with tests/test_gpu_observation_action_noise.py."""
+import copy
+import ctypes as C
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+import yaml
+
+from seqdex_amd import _abi
+from seqdex_amd import domain_randomization as dr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CFG = os.path.join(ROOT, "seqdex_amd", "cfg")
+TASKS = ("grasp_sim", "insert_sim", "orient", "search")
+f32 = np.float32
+N = 8
+
+
+def shipped(name):
+    with open(os.path.join(CFG, "allegro_hand_block_assembly_%s.yaml" % name)) as f:
+        return yaml.safe_load(f)["task"]["randomization_params"]
+
+
+# ------------------------------------------------------------------ 1. parsing
+@pytest.mark.parametrize("task", TASKS)
+def test_shipped_blocks_give_their_values(task):
+    p = shipped(task)
+    o, a, rep = dr.parse_noise(p)
+    for blk, name in ((o, "observations"), (a, "actions")):
+        y = p[name]
+        assert (blk.distribution, blk.operation, blk.schedule, blk.schedule_steps) == (1, 1, 1, y["schedule_steps"]), name
+        np.testing.assert_array_equal(list(blk.range), f32(y["range"]))
+        np.testing.assert_array_equal(list(blk.range_correlated), f32(y["range_correlated"]))
+        assert rep[name]["range"] == [float(v) for v in y["range"]] and rep[name]["distribution"] == "gaussian"
+    assert set(rep) == {"observations", "actions"}
+    if task == "grasp_sim":       # the numbers of the reference's GraspSim block
+        assert (list(o.range), list(o.range_correlated), o.schedule_steps) == ([0.0, f32(0.002)], [0.0, f32(0.001)], 40000)
+        assert (list(a.range), list(a.range_correlated), a.schedule_steps) == ([0.0, f32(0.05)], [0.0, f32(0.015)], 40000)
+    # parse() still files the two blocks under its no-op keys, and now says who reads them
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        _, prep = dr.parse(p)
+    assert "parse_noise" in prep["noop"]["observations"] and "parse_noise" in prep["noop"]["actions"]
+
+
+def test_missing_blocks_are_off_and_range_correlated_defaults_to_zero():
+    assert dr.parse_noise({"frequency": 5}) == (None, None, {})
+    o, a, rep = dr.parse_noise({"actions": {"range": [0.9, 1.1], "operation": "scaling", "distribution": "uniform"}})
+    assert o is None and list(a.range_correlated) == [0.0, 0.0] and (a.distribution, a.operation, a.schedule) == (2, 2, 0)
+    assert list(rep) == ["actions"]
+
+
+def test_parse_noise_errors_name_the_key():
+    base = shipped("grasp_sim")
+    cases = [
+        (lambda p: p["observations"].__setitem__("num_buckets", 4), "observations: unknown key"),
+        (lambda p: p["actions"].__setitem__("rnage", [0, 1]), "actions: unknown key"),
+        (lambda p: p["observations"].__setitem__("distribution", "loguniform"), "observations.distribution"),
+        (lambda p: p["actions"].__setitem__("operation", "multiply"), "actions.operation"),
+        (lambda p: p["actions"].__setitem__("schedule", "cosine"), "actions.schedule"),
+        (lambda p: p["observations"].pop("schedule_steps"), "observations.schedule_steps"),
+        (lambda p: p["observations"].__setitem__("schedule_steps", 0), "observations.schedule_steps"),
+        (lambda p: p["observations"].pop("range"), "observations.range"),
+        (lambda p: p["actions"].__setitem__("range", [0.0, -0.05]), "actions.range"),
+        (lambda p: p["actions"].__setitem__("range_correlated", [0.0, -0.015]), "actions.range_correlated"),
+        (lambda p: p["actions"].__setitem__("range_correlated", [0.0]), "actions.range_correlated"),
+        (lambda p: p["actions"].__setitem__("range_correlated", [0.0, float("nan")]), "actions.range_correlated"),
+        (lambda p: p["observations"].__setitem__("range_correlated", "0.1"), "observations.range_correlated"),
+        (lambda p: p["observations"].update(distribution="uniform", range_correlated=[0.2, 0.1]), "observations.range_correlated"),
+        (lambda p: p["observations"].update(distribution="uniform", range=[0.2, 0.1]), "observations.range"),
+        (lambda p: p.__setitem__("observations", [1, 2]), "randomization_params.observations"),
+    ]
+    for mutate, key in cases:
+        p = copy.deepcopy(base)
+        mutate(p)
+        with pytest.raises(ValueError, match=key.replace(".", r"\.")):
+            dr.parse_noise(p)
+
+
+# ------------------------------------------------------------------ 2. ABI
+def test_noise_attr_layout_matches_header_and_symbol_is_listed():
+    src = '#include <stdio.h>\n#include "seqdex.h"\nint main(){printf("%zu %d\\n", sizeof(sdx_noise_attr), SDX_ABI_VERSION);return 0;}\n'
+    with tempfile.TemporaryDirectory() as d:
+        open(os.path.join(d, "t.c"), "w").write(src)
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "t.c"), "-o", os.path.join(d, "t")])
+        size, abi = subprocess.check_output([os.path.join(d, "t")]).decode().split()
+    assert int(size) == C.sizeof(_abi.NoiseAttr) == 32
+    assert int(abi) == _abi.SDX_ABI_VERSION == 8                       # sdx_dr_desc keeps its layout, the version stays
+    assert "sdx_set_noise" in _abi.SDX_EXPORTS
+
+
+# ------------------------------------------------------------------ 3. the kernel on the emulator
+torch = pytest.importorskip("torch")
+
+import noise_cases as K          # noqa: E402
+
+
+def _make(n, **kw):
+    from tests.hipemu.sim import EmuSim
+    return EmuSim(n, **kw)
+
+
+BACKEND = (_make, lambda t: t)
+
+
+def test_symbol_is_exported_and_needs_randomization_on():
+    from seqdex_amd.sim import SdxError
+    t = K.Tracked(BACKEND, "grasp", 1)
+    try:
+        assert hasattr(t.s.lib, "sdx_set_noise")
+        blk = K.attr(K.GAUSSIAN, K.ADDITIVE, (0.0, 0.05))
+        with pytest.raises(SdxError, match=r"error -4: sdx_set_noise: randomization is off"):      # SDX_ERR_STATE
+            t.s.set_noise(actions=blk)
+        t.randomize(0)
+        t.s.set_noise(actions=blk)
+        t.s.set_noise()                                                                           # both sides off
+        t.s.set_randomization(None)                                                               # ... takes the noise with it
+        with pytest.raises(SdxError, match="error -4"):
+            t.s.set_noise(actions=blk)
+    finally:
+        t.close()
+
+
+def test_bad_blocks_are_refused_with_a_message():
+    from seqdex_amd.sim import SdxError
+    t = K.Tracked(BACKEND, "grasp", 1)
+    try:
+        t.randomize(0)
+        good = dict(distribution=K.GAUSSIAN, operation=K.ADDITIVE, rng=(0.0, 0.05), corr=(0.0, 0.015), schedule=1, steps=40000)
+        for change, word in ((dict(distribution=3), "distribution"), (dict(distribution=7), "distribution"), (dict(operation=0), "operation"),
+                             (dict(schedule=5), "schedule"), (dict(steps=0), "schedule"), (dict(rng=(0.0, float("inf"))), "finite"),
+                             (dict(corr=(float("nan"), 0.0)), "finite"), (dict(rng=(0.0, -0.1)), "sigma"), (dict(corr=(0.0, -0.1)), "sigma"),
+                             (dict(distribution=K.UNIFORM, rng=(0.2, 0.1)), "lo <= hi"), (dict(distribution=K.UNIFORM, corr=(0.2, 0.1)), "lo <= hi")):
+            blk = K.attr(**dict(good, **change))
+            for side in ("observations", "actions"):
+                with pytest.raises(SdxError, match=r"error -1: sdx_set_noise: %s: .*%s" % (side, word)):      # SDX_ERR_INVALID
+                    t.s.set_noise(**{side: blk})
+    finally:
+        t.close()
+
+
+@pytest.fixture(scope="module")
+def baseline():
+    """ten steps of N envs with randomization on (identity rows) and noise off: what the zero-operand and isolation runs must reproduce"""
+    t = K.Tracked(BACKEND, "grasp", N)
+    try:
+        t.randomize(0)
+        return K.run(t, K.fixed_actions(N, 10))
+    finally:
+        t.close()
+
+
+def test_zero_operand_is_bit_identical_to_noise_off(baseline):
+    K.case_zero_operand(BACKEND, "grasp", N, shipped("grasp_sim"), base=baseline)
+
+
+def test_observation_noise_touches_obs_clamped_only(baseline):
+    K.case_isolation(BACKEND, "grasp", N, 10, base=baseline)
+
+
+def test_search_tvalue_buffer_gets_no_noise():
+    """Search's ten-frame buffer is fed from the clean row; no env resets here (a Search reset is 60 settling launches)"""
+    recs = []
+    for on in (False, True):
+        t = K.Tracked(BACKEND, "search", 2)
+        try:
+            t.randomize(50000)
+            if on:
+                t.s.set_noise(observations=K.attr(K.GAUSSIAN, K.ADDITIVE, (0.0, 0.002), (0.0, 0.001)))
+            t.s.RESET.zero_()
+            recs.append(K.run(t, K.fixed_actions(2, 2), ("TVALUE_OBS", "OBS", "STATES", "OBS_CLAMPED", "TVALUE")))
+        finally:
+            t.close()
+    for a, b in zip(*recs):
+        for k in ("TVALUE_OBS", "OBS", "STATES", "TVALUE"):
+            K.assert_same_bits(a[k], b[k], k)
+        assert (a["OBS_CLAMPED"] != b["OBS_CLAMPED"]).mean() > 0.9
+    assert np.abs(recs[1][-1]["TVALUE_OBS"]).max() > 0
+
+
+@pytest.fixture(scope="module")
+def tracked():
+    t = K.Tracked(BACKEND, "grasp", N)
+    yield t
+    t.close()
+
+
+@pytest.mark.parametrize("schedule", ["none", "linear-mid", "constant"])
+@pytest.mark.parametrize("operation", [K.ADDITIVE, K.SCALING])
+@pytest.mark.parametrize("distribution", [K.GAUSSIAN, K.UNIFORM])
+def test_known_operand(tracked, distribution, operation, schedule):
+    K.case_known_operand(tracked, distribution, operation, schedule)
+
+
+def test_known_operand_on_a_narrow_row():
+    """InsertSim: 75 columns (no vector path, a 3-column tail), never-written columns 16..22 and 60"""
+    t = K.Tracked(BACKEND, "insert", 3)
+    try:
+        K.case_known_operand(t, K.GAUSSIAN, K.ADDITIVE, "linear-mid")
+        K.case_known_operand(t, K.UNIFORM, K.SCALING, "none")
+    finally:
+        t.close()
+
+
+def test_scaling_at_s_zero_multiplies_by_two():
+    """the quirk DESIGN.md names: both parts of a scaling block interpolate to 1 at s = 0 and are summed"""
+    t = K.Tracked(BACKEND, "grasp", 2)
+    try:
+        t.randomize(0)
+        t.s.set_noise(actions=K.attr(K.GAUSSIAN, K.SCALING, (1.0, 0.05), (1.0, 0.015), 1, K.STEPS))
+        t.s.RESET.zero_()
+        t.pre_physics(torch.full((2, 23), 0.25))
+        np.testing.assert_array_equal(t.s.ACTIONS.numpy(), f32(0.5))
+    finally:
+        t.close()
+
+
+@pytest.mark.parametrize("gravity", [False, True])
+def test_correlated_part_holds_until_a_due_reset(gravity):
+    K.case_refresh(BACKEND, 4, gravity)
+
+
+def test_actions_are_clamped_then_noised_and_the_callers_buffer_is_untouched():
+    K.case_actions_not_reclamped(BACKEND, N)
+
+
+def test_operand_does_not_depend_on_n():
+    K.case_independent_of_n(BACKEND, 8, 16)
+
+
+def test_snapshot_replays_the_noise():
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        K.case_snapshot(BACKEND, N, shipped("grasp_sim"))
