@@ -6,7 +6,7 @@
 // origin in the box frame), nearest hit wins.  Box geometry instead of the studded meshes is the approximation of this whole build
 // (DESIGN.md section 3); the pixel counts are therefore NOT comparable digit by digit with Isaac Gym's renderer (parity unpinned) -
 // the kernel is checked against oracle/camera_oracle.py, a numpy ray caster of the same boxes.
-#include "sdx_common.h"
+#include "sdx_kernels.h"   // (includes sdx_common.h)
 
 #define CAM_W 128
 #define CAM_H 128

@@ -1,0 +1,28 @@
+// sdx_kernels.h — the one declaration of every host launcher that crosses a file boundary of libseqdex_hip.so.  Included by
+// sdx_capi.hip (the caller) and by every file that defines one of them, so that a definition whose parameters differ from the
+// declaration fails to compile instead of linking silently.  SdxBuf goes to a launcher by pointer and to its kernels by value.
+#pragma once
+#include "sdx_common.h"
+
+extern "C" {
+// sdx_task.hip
+void sdxk_pre_physics(const SdxConst* C, const SdxBuf* B, const float* actions, const uint8_t* mask, const int32_t* choice, int flags, hipStream_t st);
+void sdxk_post_physics(const SdxConst* C, const SdxBuf* B, int flags, hipStream_t st);
+void sdxk_orient_pregrasp(const SdxConst* C, const SdxBuf* B, const uint8_t* mask, int mode, int iter, hipStream_t st);
+void sdxk_orient_post_reset(const SdxConst* C, const SdxBuf* B, const uint8_t* mask, hipStream_t st);
+void sdxk_search_set_hand(const SdxConst* C, const SdxBuf* B, const uint8_t* mask, int mode, hipStream_t st);
+void sdxk_scripted_grasp(const SdxConst* C, const SdxBuf* B, float* state, float* act, hipStream_t st);
+void sdxk_set_indexed(const SdxBuf* B, int id, const float* src, const int32_t* ids, int n, hipStream_t st);
+// sdx_physics.hip
+void sdxk_physics(const SdxConst* C, const SdxBuf* B, hipStream_t st);
+void sdxk_kinematics(const SdxConst* C, const SdxBuf* B, hipStream_t st);
+// sdx_camera.hip
+void sdxk_seg_camera(const SdxConst* C, const SdxBuf* B, hipStream_t st);
+void sdxk_render_view(const SdxConst* C, const SdxBuf* B, const sdx_view_desc* v, const int32_t* env_ids, int n, float* depth, int16_t* label, uint8_t* rgb, hipStream_t st);
+// sdx_randomize.hip
+void sdxk_dr_defaults(const SdxConst* C, const SdxBuf* B, hipStream_t st);
+void sdxk_dr_sample(const SdxConst* C, const SdxBuf* B, const sdx_dr_desc* desc, int first, const uint8_t* mask, hipStream_t st);
+void sdxk_noise(const SdxConst* C, const SdxBuf* B, const sdx_noise_attr* attr, const float* src, float* dst, int W, int act, hipStream_t st);
+// sdxp_kernels.hip (the PPO library's MFMA linear layer, which Search's RetriGraspTValue in sdx_task.hip borrows)
+void sdxpk_linear(const float* X, const float* W, const float* b, float* Y, int M, int N, int K, int elu_flag, const double* nmean, const double* nvar, hipStream_t st);
+}

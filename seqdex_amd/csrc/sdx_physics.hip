@@ -23,7 +23,7 @@
 //     narrowphase: lane = box pair picks the samples, lane = contact computes their geometry.
 #include <stdlib.h>
 
-#include "sdx_common.h"
+#include "sdx_kernels.h"   // (includes sdx_common.h)
 
 #define NL SDX_NLINK
 #define ND SDX_NDOF

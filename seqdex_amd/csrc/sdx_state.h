@@ -1,6 +1,6 @@
 // sdx_state.h — sim snapshots (include/seqdex.h sdx_state_*): the segment table that says what an env's state is, and
 // the one copy kernel that moves env states env -> snapshot row (save), row -> env (restore) and env -> env (clone).  Included by
-// sdx_capi.hip only; plain C++ loads and stores, so that tests/hipemu compiles it with g++.
+// sdx_capi.hip only (it fills the table from sdx_buffers.h); plain C++ loads and stores, so that tests/hipemu compiles it with g++.
 #pragma once
 #include "sdx_common.h"
 

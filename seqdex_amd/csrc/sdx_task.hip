@@ -17,7 +17,7 @@
 //
 // HBM-bound by design: every per-env row is loaded once with lane-strided (coalesced) accesses into LDS,
 // derived quantities are computed once per wave, rows are written back lane-strided.
-#include "sdx_common.h"
+#include "sdx_kernels.h"   // (includes sdx_common.h)
 
 // orientation_error(quat_from_euler_xyz(euler), current) (OR:1922-1925; quat_from_euler_xyz of isaacgym.torch_utils: half-angle
 // products): vector part of desired * conj(current), flipped into the w >= 0 hemisphere
@@ -421,7 +421,7 @@ __device__ __forceinline__ float search_reward(const PostDerived& D, const float
 
 // ------------------------------------------------------------------------------------------------ K1 + K2
 // flags: bit0 reset envs with reset_buf != 0; bit1 reset envs with ext_mask != 0; bit2 compute targets; bit3 actions_in is already
-// clamped and carries the action noise (sdx_capi.hip k_noise): not clamped a second time.
+// clamped and carries the action noise (sdx_randomize.hip k_noise): not clamped a second time.
 // Every `switch (sc.task_kind)` is wave-uniform; an unknown kind runs GraspSim's per-step code.
 __global__ __launch_bounds__(SDX_WAVE) void k_pre_physics(const SdxConst* __restrict__ C, SdxBuf B, const float* __restrict__ actions_in,
                                                           const uint8_t* __restrict__ ext_mask, const int32_t* __restrict__ ext_choice, int flags) {
@@ -841,8 +841,6 @@ __global__ __launch_bounds__(SDX_WAVE) void k_search_tvalue_append(SdxBuf B) {
   row[9 * TVT_FRAME + lane] = v;
   if (lane == 0) row[9 * TVT_FRAME + 64] = B.seg_pix[(size_t)e * 4 + 0] / 100.0f;
 }
-extern "C" void sdxpk_linear(const float* X, const float* W, const float* b, float* Y, int M, int N, int K, int elu_flag,
-                             const double* nmean, const double* nvar, hipStream_t st);
 
 // ------------------------------------------------------------------------------------------------ host launchers
 // ------------------------------------------------------------------------------------------------ BlockAssemblyOrient reset
@@ -959,6 +957,28 @@ __global__ __launch_bounds__(256) void k_scripted_grasp(const SdxConst* __restri
   state[2 * e + 1] = hold;
   for (int j = 7; j < SDX_NDOF; ++j) a[j] = 2.0f * frac - 1.0f;
   a[7] = 0.0f; a[11] = 0.0f; a[15] = 0.0f;                                      // abduction joints of the three fingers stay centred
+}
+// sdx_set_indexed (include/seqdex.h): one thread per (listed actor, column)
+// src may BE the library's own tensor (the documented use: edit SDX_T_ROOT / SDX_T_DOF in place, then name the rows that changed): no __restrict__ on it
+__global__ void k_set_indexed(SdxBuf B, int id, const float* src, const int32_t* __restrict__ ids, int n) {
+  const int i = blockIdx.x, t = threadIdx.x;
+  if (i >= n) return;
+  const int actor = ids[i];
+  if (actor < 0 || actor >= B.N * SDX_ACTORS) return;
+  const int e = actor / SDX_ACTORS, slot = actor % SDX_ACTORS;
+  if (id == SDX_T_ROOT) {
+    if (slot == 0 || t >= 13) return;                       // the hand actor has a fixed base: its root state is not settable
+    const float v = src[(size_t)actor * 13 + t];
+    B.root[(size_t)actor * 13 + t] = v;
+    B.rb[((size_t)e * SDX_BODIES + SDX_NLINK + slot - 1) * 13 + t] = v;
+    if (t == 0) B.wcount[e] = 0;                            // a teleported body invalidates the env's cached contact impulses (warm start)
+  } else if (slot == 0) {
+    if (id == SDX_T_DOF) { if (t < SDX_NDOF * 2) B.dof[(size_t)e * SDX_NDOF * 2 + t] = src[(size_t)e * SDX_NDOF * 2 + t]; }
+    else if (t < SDX_NDOF) B.targets[(size_t)e * SDX_NDOF + t] = src[(size_t)e * SDX_NDOF + t];
+  }
+}
+extern "C" void sdxk_set_indexed(const SdxBuf* B, int id, const float* src, const int32_t* ids, int n, hipStream_t st) {
+  hipLaunchKernelGGL(k_set_indexed, dim3(n), dim3(64), 0, st, *B, id, src, ids, n);
 }
 extern "C" void sdxk_scripted_grasp(const SdxConst* C, const SdxBuf* B, float* state, float* act, hipStream_t st) {
   hipLaunchKernelGGL(k_scripted_grasp, dim3((B->N + 255) / 256), dim3(256), 0, st, C, *B, state, act);

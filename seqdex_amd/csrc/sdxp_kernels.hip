@@ -15,6 +15,7 @@
 //     dataset; rl_games runs train_central_value first, RC:1323-1324 - interleaving is arithmetically identical).
 // Per optimiser step: L1, L2, L3, HEAD(+loss +backward of the heads), B3, B2, CTRL = 7 launches for all three nets.
 #include "sdx_common.h"
+#include "sdx_kernels.h"
 #include "sdxp_types.h"
 #include "sdxp_ppo_terms.h"
 #include <cstddef>

@@ -17,7 +17,8 @@ _DEPS = _SRCS + [os.path.abspath(__file__), os.path.join(HERE, "include", "hip",
 # extra g++ flags for every emulator build (e.g. "-DSDX_D_SORT": a compile-time variant of a kernel under test); rebuild with force=True after changing it
 _EXTRA = os.environ.get("SDX_EMU_CXXFLAGS", "").split()
 _lib = None
-# the whole simulator behind the C ABI of include/seqdex.h (sdx_capi + task + physics + camera sources) on the emulator
+# the whole simulator behind the C ABI of include/seqdex.h (sdx_capi + task + physics + camera sources) on the emulator.  sdx_randomize.hip is NOT
+# listed: under HIPEMU sdx_capi.hip includes it (its last lines), and listing it too would define the samplers twice
 _SIM_SO = os.path.join(HERE, "libsdx_emu_sim.so")
 _SIM_SRCS = [os.path.join(HERE, "hipemu.cpp"), os.path.join(HERE, "sim_driver.cpp")] + \
             [os.path.join(CSRC, f) for f in ("sdx_capi.hip", "sdx_task.hip", "sdx_physics.hip", "sdx_camera.hip")]
@@ -40,7 +41,7 @@ def build(force=False):
 
 def build_sim(force=False):
     deps = _SIM_SRCS + [os.path.abspath(__file__), os.path.join(HERE, "include", "hip", "hip_runtime.h"), os.path.join(ROOT, "include", "seqdex.h")] + \
-        [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+        [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(CSRC, "sdx_randomize.hip")]   # sdx_capi.hip includes it here
     if not force and os.path.exists(_SIM_SO) and all(os.path.getmtime(_SIM_SO) >= os.path.getmtime(d) for d in deps):
         return _SIM_SO
     objs = []

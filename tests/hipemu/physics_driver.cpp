@@ -8,9 +8,8 @@
 
 #include "sdx_common.h"
 #include "sdx_const_build.h"
+#include "sdx_kernels.h"
 
-extern "C" void sdxk_physics(const SdxConst* C, const SdxBuf* B, hipStream_t st);
-extern "C" void sdxk_kinematics(const SdxConst* C, const SdxBuf* B, hipStream_t st);
 extern "C" size_t sdxk_physics_lds_bytes();
 
 static int32_t g_cstats[4];   // SDX_T_CONTACT_STATS of the emulated launches since the last emu_cstats(reset = 1)

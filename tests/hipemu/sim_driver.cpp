@@ -4,6 +4,8 @@
 // are not emulated, and this stub is NOT the kernel under test.
 #include <hip/hip_runtime.h>
 
+#include "sdx_kernels.h"
+
 extern "C" void sdxpk_linear(const float* X, const float* W, const float* b, float* Y, int M, int N, int K, int elu_flag,
                              const double* nmean, const double* nvar, hipStream_t) {
   for (int m = 0; m < M; ++m)

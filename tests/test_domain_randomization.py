@@ -2,7 +2,7 @@
 
 - the YAML parser: the shipped blocks, errors that name the key, the report of no-ops and unsupported entries;
 - the ABI mirror of sdx_dr_desc;
-- the device sampler (sdx_capi.hip k_dr_sample / k_dr_gravity) on the SIMT emulator against the numpy restatement of the rules below;
+- the device sampler (sdx_randomize.hip k_dr_sample / k_dr_gravity) on the SIMT emulator against the numpy restatement of the rules below;
 - the randomization variant of k_physics on the emulator: bit-identical to the default kernel with the scene's rows, and per env equal to the
   C oracle run with that env's values as scene constants."""
 import copy
@@ -61,7 +61,7 @@ def _f(fn, x):   # a correctly rounded float32 libm function (float64 evaluation
 
 
 def value(a, s, h, v0):
-    """dr_value of sdx_capi.hip in float32 arithmetic"""
+    """dr_value of sdx_randomize.hip in float32 arithmetic"""
     scaling = a.operation == 2
     lo, hi, one = f32(a.range[0]), f32(a.range[1]), f32(1.0)
     if a.distribution == 1:

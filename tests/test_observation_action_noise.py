@@ -2,7 +2,7 @@
 
 - the YAML parser on the shipped blocks, errors that name the key;
 - the ABI mirror of sdx_noise_attr, the exported symbol, the call order;
-- the noise kernel (sdx_capi.hip k_noise) on the SIMT emulator against the numpy restatement of tests/helpers/noise_restatement.py:
+- the noise kernel (sdx_randomize.hip k_noise) on the SIMT emulator against the numpy restatement of tests/helpers/noise_restatement.py:
   zero operand, known operand for every distribution x operation x schedule, correlation and refresh, isolation, actions not clamped
   twice, independence of N, snapshots.  The bodies are tests/noise_cases.py, shared with tests/test_gpu_observation_action_noise.py."""
 import copy

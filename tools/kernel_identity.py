@@ -1,7 +1,8 @@
 """Is the device code of two trees the same?  Every .hip of seqdex_amd/csrc of this tree and of another checkout (the parent commit, say)
 is compiled for gfx950 with the Makefile's flags plus -save-temps=obj; for every kernel (.amdhsa_kernel) the instruction text from its
 label to .end_amdhsa_kernel, the .amdhsa_* resource lines included, must be the same on both sides, and neither side may have a kernel
-the other lacks.  Comments, debug / .loc / .file lines, the function numbers inside local labels and the order of the symbols are ignored.
+the other lacks.  Kernels are matched by symbol across all files of a side: one that changed files is reported as `moved a.hip -> b.hip`
+next to its verdict, not as dropped and added.  Comments, debug / .loc / .file lines, the function numbers inside local labels and the order of the symbols are ignored.
 
     git worktree add /tmp/parent HEAD~1      (a whole checkout: the sources include ../../include/seqdex.h)
     python tools/kernel_identity.py /tmp/parent/seqdex_amd/csrc [--out profiles/kernel_identity.txt] [--work DIR] [--jobs 8]
@@ -70,18 +71,28 @@ def main():
     a = ap.parse_args()
     mine = os.path.join(ROOT, "seqdex_amd", "csrc")
     work = a.work or tempfile.mkdtemp(prefix="kernel_identity_")
-    files = sorted(set(os.path.basename(f)[:-4] for d in (mine, a.other) for f in glob.glob(os.path.join(d, "*.hip"))))
+    sides = (("other", a.other), ("this", mine))
+    files = {side: sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(d, "*.hip"))) for side, d in sides}
     with concurrent.futures.ThreadPoolExecutor(a.jobs) as ex:
-        fut = {(side, n): ex.submit(compile_one, d, n, os.path.join(work, side, n)) for side, d in (("other", a.other), ("this", mine)) for n in files}
+        fut = {(side, n): ex.submit(compile_one, d, n, os.path.join(work, side, n)) for side, d in sides for n in files[side]}
         asm = {k: f.result() for k, f in fut.items()}
-    report, bad = [], 0
-    for n in files:
-        ko, kt = kernels(asm[("other", n)]), kernels(asm[("this", n)])
-        for k in sorted(set(ko) | set(kt)):
-            verdict = "identical" if ko.get(k) == kt.get(k) else ("DIFFERS" if k in ko and k in kt else ("ADDED" if k in kt else "DROPPED"))
-            bad += verdict != "identical"
-            report.append("%-18s %-10s %s" % (n + ".hip", verdict, k))
-    report.append("%d kernels, %d not identical" % (len(report), bad))
+    # {(file, symbol): text} per side; a kernel is matched in its own file first (two files may each have a static kernel of one name),
+    # then by symbol across all files of a side when exactly one of that name is left over on either side: it moved
+    found = {side: {(n, k): text for (s, n), path in asm.items() if s == side for k, text in kernels(path).items()} for side, _ in sides}
+    ko, kt = found["other"], found["this"]
+    pairs = [(fk, fk) for fk in sorted(set(ko) & set(kt))]
+    left_o, left_t = sorted(set(ko) - set(kt)), sorted(set(kt) - set(ko))
+    for sym in sorted(set(k for _, k in left_o + left_t)):
+        o, t = [fk for fk in left_o if fk[1] == sym], [fk for fk in left_t if fk[1] == sym]
+        pairs += [(o[0], t[0])] if len(o) == 1 and len(t) == 1 else [(fk, None) for fk in o] + [(None, fk) for fk in t]
+    report, bad, nmoved = [], 0, 0
+    for o, t in sorted(pairs, key=lambda p: p[1] or p[0]):
+        verdict = "identical" if o and t and ko[o] == kt[t] else ("DIFFERS" if o and t else ("ADDED" if t else "DROPPED"))
+        bad += verdict != "identical"
+        moved = "   moved %s.hip -> %s.hip" % (o[0], t[0]) if o and t and o[0] != t[0] else ""
+        nmoved += bool(moved)
+        report.append("%-18s %-10s %s%s" % ((t or o)[0] + ".hip", verdict, (t or o)[1], moved))
+    report.append("%d kernels, %d not identical, %d moved" % (len(report), bad, nmoved))
     text = "\n".join(report) + "\n"
     sys.stdout.write(text)
     if a.out:
