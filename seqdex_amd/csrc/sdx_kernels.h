@@ -23,6 +23,6 @@ void sdxk_render_view(const SdxConst* C, const SdxBuf* B, const sdx_view_desc* v
 void sdxk_dr_defaults(const SdxConst* C, const SdxBuf* B, hipStream_t st);
 void sdxk_dr_sample(const SdxConst* C, const SdxBuf* B, const sdx_dr_desc* desc, int first, const uint8_t* mask, hipStream_t st);
 void sdxk_noise(const SdxConst* C, const SdxBuf* B, const sdx_noise_attr* attr, const float* src, float* dst, int W, int act, hipStream_t st);
-// sdxp_kernels.hip (the PPO library's MFMA linear layer, which Search's RetriGraspTValue in sdx_task.hip borrows)
+// sdxp_rollout.hip (the PPO library's MFMA linear layer, which Search's RetriGraspTValue in sdx_task.hip borrows)
 void sdxpk_linear(const float* X, const float* W, const float* b, float* Y, int M, int N, int K, int elu_flag, const double* nmean, const double* nvar, hipStream_t st);
 }

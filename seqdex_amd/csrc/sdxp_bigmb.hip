@@ -2,7 +2,7 @@
 //
 // The reference trains the insert policy with minibatch_size 4096 (cfg/lego/ppo_continuous_insert.yaml:50,75) and BASELINE.md asks
 // for a labelled large-minibatch variant next to the shipped minibatch of 4.  With thousands of samples per step the update is
-// GEMM-shaped, not the rank-MB weight streaming of sdxp_kernels.hip / sdxp_persist.hip: forward Y = ELU(X W^T + b), data gradient
+// GEMM-shaped, not the rank-MB weight streaming of sdxp_update.hip / sdxp_persist.hip: forward Y = ELU(X W^T + b), data gradient
 // dX = (dY W) * ELU'(H), weight gradient G = dY^T X, all three on the f32-input matrix cores (v_mfma_f32_32x32x2_f32: exact fp32,
 // k-ordered fma chain), LDS-tiled 128x128x32 per 256-thread workgroup (4 waves of 64x64; 64x64x16 for small problems), the
 // same layer of the three networks in one launch.  rl_games' calc_gradients
@@ -13,12 +13,12 @@
 //   k_big_fin:  statistics, d logstd, KL word, minibatch bookkeeping of the control block
 //   backward: head data gradients, then per net  G_l = dY_l^T X_l (TN GEMM, split over the minibatch rows, partials reduced in a
 //   fixed order: deterministic), b_l = column sums of dY_l, dY_{l-1} = (dY_l W_l) * ELU'(H_{l-1}) (NN GEMM, fused)
-//   -> flat gradients in ac_g / cv_g (parameter layout), then the explicit clip + Adam of sdxp_kernels.hip (k_sqnorm2 / k_adam2).
+//   -> flat gradients in ac_g / cv_g (parameter layout), then the explicit clip + Adam of sdxp_multirank.hip (k_sqnorm2 / k_adam2).
 //
 // The central-value input normalisation (RunningMeanStd in train mode: update with the minibatch, then normalise it, during
 // mini-epoch 0; frozen afterwards) is hoisted out of the loop as in the small-minibatch path, with column statistics reduced in fp64.
 #include "sdx_common.h"
-#include "sdxp_types.h"
+#include "sdxp_launch.h"
 #include "sdxp_ppo_terms.h"
 #include <cstddef>
 #include <cstdint>
@@ -481,7 +481,7 @@ static HeadParts head_parts(const SdxpDev& D, int MB) {
   const size_t vp0 = (size_t)Sh * ((size_t)D.act_dim * D.units[2] + D.act_dim);
   return {(MB + 255) / 256, Sh, VS, vp0, vp0 + (size_t)VS * (D.units[2] + 1)};
 }
-extern "C" size_t sdxpk_big_part_floats(const SdxpDev* D, int MB) {
+static size_t big_part_floats(const SdxpDev* D, int MB) {
   const int S = big_splits(MB);
   const size_t in0 = D->obs_dim > D->state_dim ? D->obs_dim : D->state_dim;
   size_t mx = (size_t)D->units[0] * in0 + D->units[0];
@@ -495,9 +495,8 @@ extern "C" size_t sdxpk_big_part_floats(const SdxpDev* D, int MB) {
   const size_t m1 = need > hp ? need : hp;
   return m1 > hf ? m1 : hf;          // per network; the workspace holds three such regions
 }
-extern "C" int sdxpk_big_nsplit(int MB) { return big_splits(MB); }
 // lowers the large-minibatch options to what shapes and device allow, sets the LDS attributes of the kernels that stay (NT path: 16-byte aligned windows)
-extern "C" void sdxpk_big_prepare(const SdxpDev* D, int MB, SdxpOpts* o) {
+static void big_prepare(const SdxpDev* D, int MB, SdxpOpts* o) {
   int dev = 0, lds = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) lds = 0;
   o->bigmb_fused_heads = o->bigmb_fused_heads && D->units[2] == HU && D->act_dim <= 23;
@@ -515,6 +514,57 @@ extern "C" void sdxpk_big_prepare(const SdxpDev* D, int MB, SdxpOpts* o) {
     o->bigmb_nt = o->bigmb_tt = 0;
   }
   (void)hipGetLastError();
+}
+// The workspace of one large minibatch (SdxpBigWs): activations and pre-activation gradients, split partials of the weight gradients and,
+// on the NT path, the staged operands of sdx_gemm_nt.h.  Every buffer comes zero-filled from `alloc`: the padding the kernels never write stays zero
+extern "C" int sdxpk_big_setup(const SdxpDev* D, int MB, SdxpOpts* o, SdxpAllocFn alloc, void* ctx, SdxpBigWs* ws) {
+  big_prepare(D, MB, o);
+  SdxpBigWs& w = *ws;
+  int rc = 0;
+  auto get = [&](auto*& p, size_t count, size_t elem) {
+    void* q = nullptr;
+    if (rc == 0) rc = alloc(ctx, &q, count * elem);
+    p = static_cast<std::remove_reference_t<decltype(p)>>(q);
+  };
+  const int* units = D->units;
+  const size_t BM = (size_t)MB, R = (size_t)D->N * D->horizon;
+  w.MB = MB; w.nsplit = big_splits(MB);
+  for (int net = 0; net < 3; ++net)
+    for (int l = 0; l < 3; ++l) { get(w.h[net][l], BM * units[l], 4); get(w.dy[net][l], BM * units[l], 4); }
+  get(w.mu, BM * 24, 4); get(w.dmu, BM * 24, 4); get(w.v, 2 * BM, 4); get(w.dv, 2 * BM, 4);
+  w.part_region = big_part_floats(D, MB);
+  get(w.part, 3 * w.part_region, 4);
+  get(w.dpart, (size_t)w.nsplit * D->state_dim * 2, 8);
+  w.nt = o->bigmb_nt; w.tt = o->bigmb_tt; w.nt_tile = o->nt_tile; w.fused_heads = o->bigmb_fused_heads;
+  w.zeros = nullptr; if (w.tt) get(w.zeros, 64, 4);
+  if (w.nt) {   // every operand of the NT products k-contiguous in the element type of the run
+    const size_t ES = D->bf16 ? 2 : 4;
+    w.KC = D->bf16 ? 64 : 32; w.MBp = (MB + w.KC - 1) / w.KC * w.KC; w.Rp = (int)R + 64;
+    for (int net = 0; net < 3; ++net)
+      for (int l = 0; l < 3; ++l) {
+        const int K = l == 0 ? (net == 2 ? D->state_dim : D->obs_dim) : units[l - 1];
+        w.kp[net][l] = (K + w.KC - 1) / w.KC * w.KC;
+      }
+    for (int i = 0; i < 3; ++i) {
+      const int kp0 = w.kp[i == 0 ? 0 : 2][0];
+      get(w.xn[i], R * kp0, ES); get(w.xt[i], (size_t)kp0 * w.Rp, ES);
+    }
+    for (int net = 0; net < 3; ++net)
+      for (int l = 0; l < 3; ++l) {
+        get(w.wn[net][l], (size_t)units[l] * w.kp[net][l], ES);
+        w.wt[net][l] = nullptr;
+        if (l > 0) get(w.wt[net][l], (size_t)w.kp[net][l] * units[l], ES);
+        get(w.dyt[net][l], (size_t)units[l] * w.MBp, ES);
+        w.dyn[net][l] = nullptr;
+        if (l == 2 && !D->bf16) w.dyn[net][l] = w.dy[net][l];
+        else if (l > 0) get(w.dyn[net][l], BM * units[l], ES);
+        if (l < 2) {
+          get(w.ht[net][l], (size_t)units[l] * w.MBp, ES);
+          if (D->bf16) get(w.hn[net][l], BM * units[l], ES); else w.hn[net][l] = w.h[net][l];
+        }
+      }
+  }
+  return rc;
 }
 template <int BF>
 static void stage_launch(const StageArgs* a, int count, hipStream_t st) {

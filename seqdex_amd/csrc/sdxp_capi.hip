@@ -10,40 +10,7 @@
 #include <vector>
 
 #include "sdx_common.h"
-#include "sdxp_types.h"
-
-extern "C" {
-void sdxpk_linear_as(const float*, const float*, const float*, float*, int, int, int, int, const double*, const double*, int, hipStream_t);
-void sdxpk_linear2_as(const float*, const float*, const float*, float*, int, int, const double*, const double*,
-                      const float*, const float*, const float*, float*, int, int, const double*, const double*, int, int, int, hipStream_t);
-void sdxpk_act_heads(const SdxpDev*, int, const float*, const float*, const int64_t*, const float*, float*, uint64_t, hipStream_t);
-void sdxpk_store_rewards(const SdxpDev*, int, const float*, const int64_t*, hipStream_t);
-void sdxpk_value_head(const SdxpDev*, float*, hipStream_t);
-void sdxpk_gae(const SdxpDev*, const float*, const int64_t*, hipStream_t);
-int sdxpk_update_step(const SdxpDev*, int, hipStream_t);
-int sdxpk_update_begin(const SdxpDev*, int, hipStream_t);
-int sdxpk_update_flush_layers(const SdxpDev*, int, hipStream_t);
-int sdxpk_backward_explicit(const SdxpDev*, int, hipStream_t);
-int sdxpk_persist_supported(const SdxpDev*, int, int);
-void sdxpk_pad_obs(const SdxpDev*, const float*, hipStream_t);
-int sdxpk_backward_factors(const SdxpDev*, int, hipStream_t);
-int sdxpk_grads_from_factors(const SdxpDev*, int, hipStream_t);
-int sdxpk_apply_factors(const SdxpDev*, int, hipStream_t);
-int sdxpk_apply_fused_prepare(const SdxpDev*, int);
-void sdxpk_apply_factors_fused(const SdxpDev*, int, unsigned*, hipStream_t);
-int sdxpk_persist_prepare(int);
-int sdxpk_update_persistent(const SdxpDev*, int, unsigned*, int, int, hipStream_t);
-int sdxpk_fwd_bwd_persistent(const SdxpDev*, unsigned*, hipStream_t);
-int sdxpk_prenorm(const SdxpDev*, int, hipStream_t);
-void sdxpk_apply_explicit(const SdxpDev*, int, float, int, hipStream_t);
-}
-
-extern "C" size_t sdxpk_big_part_floats(const SdxpDev* D, int MB);
-extern "C" int sdxpk_big_nsplit(int MB);
-extern "C" void sdxpk_big_prepare(const SdxpDev* D, int MB, SdxpOpts* o);
-extern "C" void sdxpk_big_prenorm(const SdxpDev* D, const SdxpBigWs* ws, hipStream_t st);
-extern "C" void sdxpk_big_step(const SdxpDev* D, const SdxpBigWs* ws, int mb, int me, hipStream_t st);
-extern "C" void sdxpk_apply_flat(const SdxpDev* D, hipStream_t st);
+#include "sdxp_launch.h"
 
 struct sdxp_agent {
   int device = 0;
@@ -55,7 +22,6 @@ struct sdxp_agent {
   uint64_t act_counter = 0;
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
-  int graph_chunk = 0;
   bool use_persist = false;      // persistent register-resident update kernel (sdxp_persist.hip)
   SdxpOpts opts;                 // the SDXP_* switches as sdxp_create found them, lowered to what this device can run (prepare_device)
   unsigned* bar_dev = nullptr;   // [SDXP_BAR_WORDS] grid-barrier counter, fail flags and launch counter (sdxp_types.h)
@@ -65,9 +31,7 @@ struct sdxp_agent {
   unsigned* fail_host = nullptr; // pinned mirror of the fail flag, refreshed after every persistent update
   // what a persistent update touches before it can fail (old mu/sigma rows, running mean/std, control block): saved at the start
   // of the call so that sdxp_update_status can put it back and the caller can repeat the epoch on the hipGraph path
-  float *mus_bak = nullptr, *sig_bak = nullptr;
-  double* rms_bak = nullptr;
-  SdxpCtrl* ctrl_bak = nullptr;
+  struct Backup { void* live; void* bak; size_t bytes; } backup[5] = {};
   bool big = false;              // minibatch_size > 8: GEMM-shaped update path (sdxp_bigmb.hip)
   SdxpBigWs bigws;
   int big_me = 0, big_next = 0;  // multi-rank big path: mini-epoch / expected minibatch of the next sdxp_backward call
@@ -88,26 +52,20 @@ static_assert(sizeof(SdxpCtrl) == 2544, "keep seqdex_amd/ppo.py::Ctrl in sync wi
     }                                                                                                  \
   } while (0)
 
-template <typename T>
-static int palloc(sdxp_agent* h, T** p, size_t count) {
+// zero-filled device memory owned by the handle (ctx); also the SdxpAllocFn that sdxpk_big_setup allocates through
+static int palloc_bytes(void* ctx, void** p, size_t bytes) {
+  sdxp_agent* h = (sdxp_agent*)ctx;
   void* q = nullptr;
-  if (count == 0) count = 1;
-  hipError_t e = hipMalloc(&q, count * sizeof(T));
+  hipError_t e = hipMalloc(&q, bytes);
   if (e != hipSuccess) { h->err = std::string("hipMalloc failed: ") + hipGetErrorString(e); return SDX_ERR_NOMEM; }
-  e = hipMemset(q, 0, count * sizeof(T));
+  e = hipMemset(q, 0, bytes);
   if (e != hipSuccess) { h->err = std::string("hipMemset failed: ") + hipGetErrorString(e); return SDX_ERR_HIP; }
   h->allocs.push_back(q);
-  *p = (T*)q;
+  *p = q;
   return SDX_OK;
 }
-
-static void pset(sdxp_agent* h, int id, void* p, int dtype, std::initializer_list<int64_t> shape) {
-  auto& t = h->tinfo[id];
-  t.ptr = p; t.dtype = dtype; t.ndim = (int)shape.size();
-  int i = 0;
-  for (auto s : shape) t.shape[i++] = s;
-  for (; i < 4; ++i) t.shape[i] = 1;
-}
+template <typename T>
+static int palloc(sdxp_agent* h, T** p, size_t count) { return palloc_bytes(h, (void**)p, (count ? count : 1) * sizeof(T)); }
 
 // torch.nn.Linear default init: kaiming_uniform_(a=sqrt(5)) -> U(-1/sqrt(fan_in), 1/sqrt(fan_in)); rl_games then
 // zeroes every bias (App. C).  Host-side, seeded.
@@ -148,8 +106,7 @@ static int prepare_device(sdxp_agent* h) {
   h->use_persist = persist && !h->opts.update_graph;
   h->use_persist_step = persist && !h->opts.step_kernels;
   h->use_fused_apply = h->opts.apply_fused && sdxpk_apply_fused_prepare(&h->D, h->cfg.minibatch);
-  if (h->big) sdxpk_big_prepare(&h->D, h->cfg.minibatch, &h->opts);
-  return SDX_OK;
+  return SDX_OK;   // (the large-minibatch options are lowered by sdxpk_big_setup)
 }
 
 extern "C" int sdxp_create(const sdxp_config* cfg, int32_t device, uint64_t seed, sdxp_handle* out) {
@@ -184,6 +141,7 @@ extern "C" int sdxp_create(const sdxp_config* cfg, int32_t device, uint64_t seed
   D.act_dim = cfg->act_dim;
   for (int i = 0; i < 3; ++i) D.units[i] = cfg->units[i];
   D.num_minibatches = B / cfg->minibatch;
+  D.world = cfg->world_size > 0 ? cfg->world_size : 1;
   D.rows_per_wave = 1;
   D.bsplit = 8;
   D.clip_value = cfg->clip_value; D.truncate_grads = cfg->truncate_grads; D.normalize_advantage = cfg->normalize_advantage;
@@ -238,7 +196,14 @@ extern "C" int sdxp_create(const sdxp_config* cfg, int32_t device, uint64_t seed
   PAL(h->bar_dev, SDXP_BAR_WORDS); PAL(D.ll, SDXP_LL_WORDS);
   D.obs_cols = cfg->obs_cols > 0 ? cfg->obs_cols : cfg->obs_dim;
   PAL(D.obs_pad, (size_t)N * cfg->obs_dim);
-  PAL(h->mus_bak, R * cfg->act_dim); PAL(h->sig_bak, R * cfg->act_dim); PAL(h->rms_bak, (size_t)2 * cfg->state_dim); PAL(h->ctrl_bak, 1);
+  {   // the persistent update's backup list: sdxp_update copies live -> backup, sdxp_update_status backup -> live
+    float *mus_bak, *sig_bak; double* rms_bak; SdxpCtrl* ctrl_bak;
+    PAL(mus_bak, R * cfg->act_dim); PAL(sig_bak, R * cfg->act_dim); PAL(rms_bak, (size_t)2 * cfg->state_dim); PAL(ctrl_bak, 1);
+    const size_t ra = R * cfg->act_dim * sizeof(float), sd = (size_t)cfg->state_dim * sizeof(double);
+    const sdxp_agent::Backup list[5] = {{D.mb_mus, mus_bak, ra}, {D.mb_sigmas, sig_bak, ra}, {D.rms_mean, rms_bak, sd}, {D.rms_var, rms_bak + cfg->state_dim, sd},
+                                        {D.ctrl, ctrl_bak, sizeof(SdxpCtrl)}};
+    memcpy(h->backup, list, sizeof(list));
+  }
   {   // factor exchange buffers of the multi-rank path
     uint32_t o = 0;
     for (int net = 0; net < 3; ++net)
@@ -248,54 +213,9 @@ extern "C" int sdxp_create(const sdxp_config* cfg, int32_t device, uint64_t seed
     for (int net = 0; net < 3; ++net) { D.foff.h[net] = o; o += MB * cfg->units[2]; }
     D.foff.dh = o; o += MB * 34; D.foff.dls = o; o += 32; D.foff.kl = o; o += 1;
     D.foff.total = (o + 63) / 64 * 64;
-    D.world = cfg->world_size > 0 ? cfg->world_size : 1;
-    PAL(D.fact, D.foff.total); PAL(D.fact_all, (size_t)D.foff.total * D.world); PAL(D.sqn_part, 16384);   // 2 x SDXP_SQN_STRIDE partials, then (SDXP_TW_OFF) the tagged 16-byte words of the one-launch apply (sdxp_kernels.hip)
+    PAL(D.fact, D.foff.total); PAL(D.fact_all, (size_t)D.foff.total * D.world); PAL(D.sqn_part, SDXP_SQN_FLOATS);
   }
-  if (h->big) {   // activations and pre-activation gradients of one large minibatch, split partials of the weight gradients
-    SdxpBigWs& w = h->bigws;
-    const size_t BM = (size_t)cfg->minibatch;
-    w.MB = cfg->minibatch;
-    w.nsplit = sdxpk_big_nsplit(cfg->minibatch);
-    for (int net = 0; net < 3; ++net)
-      for (int l = 0; l < 3; ++l) { PAL(w.h[net][l], BM * cfg->units[l]); PAL(w.dy[net][l], BM * cfg->units[l]); }
-    PAL(w.mu, BM * 24); PAL(w.dmu, BM * 24); PAL(w.v, 2 * BM); PAL(w.dv, 2 * BM);
-    w.part_region = sdxpk_big_part_floats(&D, cfg->minibatch);
-    PAL(w.part, 3 * w.part_region);
-    PAL(w.dpart, (size_t)w.nsplit * cfg->state_dim * 2);
-    w.nt = h->opts.bigmb_nt; w.tt = h->opts.bigmb_tt; w.nt_tile = h->opts.nt_tile; w.fused_heads = h->opts.bigmb_fused_heads;
-    w.zeros = nullptr; if (w.tt) PAL(w.zeros, 64);
-    if (w.nt) {   // staged operands of the NT products (sdx_gemm_nt.h); hipMemset by palloc: the padding the kernels never write stays zero
-      const size_t ES = D.bf16 ? 2 : 4;
-      char* q;
-      w.KC = D.bf16 ? 64 : 32;
-      w.MBp = (cfg->minibatch + w.KC - 1) / w.KC * w.KC;
-      w.Rp = (int)R + 64;
-      for (int net = 0; net < 3; ++net)
-        for (int l = 0; l < 3; ++l) {
-          const int K = l == 0 ? (net == 2 ? cfg->state_dim : cfg->obs_dim) : cfg->units[l - 1];
-          w.kp[net][l] = (K + w.KC - 1) / w.KC * w.KC;
-        }
-      for (int i = 0; i < 3; ++i) {
-        const int kp0 = w.kp[i == 0 ? 0 : 2][0];
-        PAL(q, R * kp0 * ES); w.xn[i] = q;
-        PAL(q, (size_t)kp0 * w.Rp * ES); w.xt[i] = q;
-      }
-      for (int net = 0; net < 3; ++net)
-        for (int l = 0; l < 3; ++l) {
-          PAL(q, (size_t)cfg->units[l] * w.kp[net][l] * ES); w.wn[net][l] = q;
-          w.wt[net][l] = nullptr;
-          if (l > 0) { PAL(q, (size_t)w.kp[net][l] * cfg->units[l] * ES); w.wt[net][l] = q; }
-          PAL(q, (size_t)cfg->units[l] * w.MBp * ES); w.dyt[net][l] = q;
-          w.dyn[net][l] = nullptr;
-          if (l == 2 && !D.bf16) w.dyn[net][l] = w.dy[net][l];
-          else if (l > 0) { PAL(q, BM * cfg->units[l] * ES); w.dyn[net][l] = q; }
-          if (l < 2) {
-            PAL(q, (size_t)cfg->units[l] * w.MBp * ES); w.ht[net][l] = q;
-            if (D.bf16) { PAL(q, BM * cfg->units[l] * ES); w.hn[net][l] = q; } else w.hn[net][l] = w.h[net][l];
-          }
-        }
-    }
-  }
+  if (h->big && (rc = sdxpk_big_setup(&D, cfg->minibatch, &h->opts, palloc_bytes, h, &h->bigws)) != SDX_OK) { gp_create_err = h->err; sdxp_destroy(h); return rc; }
 #undef PAL
   // ---- parameter init
   {
@@ -320,38 +240,37 @@ extern "C" int sdxp_create(const sdxp_config* cfg, int32_t device, uint64_t seed
     ctl.ac_bc1 = ctl.ac_bc2 = ctl.cv_bc1 = ctl.cv_bc2 = 1.0f;
     ctl.rms_count = 1.0;
     ctl.ac_b1pow = ctl.ac_b2pow = ctl.cv_b1pow = ctl.cv_b2pow = 1.0;
-    ctl.world = cfg->world_size > 0 ? cfg->world_size : 1;
+    ctl.world = D.world;
     PCHK(h, hipMemcpy(D.ctrl, &ctl, sizeof(ctl), hipMemcpyHostToDevice));
   }
   PCHK(h, hipHostMalloc((void**)&h->fail_host, sizeof(unsigned), hipHostMallocDefault));
   *h->fail_host = 0;
-  pset(h, SDXP_T_AC_PARAMS, D.ac, SDX_F32, {(int64_t)D.off.total});
-  pset(h, SDXP_T_AC_GRADS, D.ac_g, SDX_F32, {(int64_t)D.off.total});
-  pset(h, SDXP_T_CV_PARAMS, D.cv, SDX_F32, {(int64_t)D.coff.total});
-  pset(h, SDXP_T_CV_GRADS, D.cv_g, SDX_F32, {(int64_t)D.coff.total});
-  pset(h, SDXP_T_MB_OBS, D.mb_obs, SDX_F32, {(int64_t)N, (int64_t)H, cfg->obs_dim});
-  pset(h, SDXP_T_MB_STATES, D.mb_states, SDX_F32, {(int64_t)N, (int64_t)H, cfg->state_dim});
-  pset(h, SDXP_T_MB_ACTIONS, D.mb_actions, SDX_F32, {(int64_t)N, (int64_t)H, cfg->act_dim});
-  pset(h, SDXP_T_MB_MUS, D.mb_mus, SDX_F32, {(int64_t)N, (int64_t)H, cfg->act_dim});
-  pset(h, SDXP_T_MB_SIGMAS, D.mb_sigmas, SDX_F32, {(int64_t)N, (int64_t)H, cfg->act_dim});
-  pset(h, SDXP_T_MB_NEGLOGP, D.mb_neglogp, SDX_F32, {(int64_t)N, (int64_t)H});
-  pset(h, SDXP_T_MB_VALUES, D.mb_values, SDX_F32, {(int64_t)N, (int64_t)H});
-  pset(h, SDXP_T_MB_REWARDS, D.mb_rewards, SDX_F32, {(int64_t)N, (int64_t)H});
-  pset(h, SDXP_T_MB_DONES, D.mb_dones, SDX_F32, {(int64_t)N, (int64_t)H});
-  pset(h, SDXP_T_RETURNS, D.returns, SDX_F32, {(int64_t)R});
-  pset(h, SDXP_T_ADVANTAGES, D.adv, SDX_F32, {(int64_t)R});
-  pset(h, SDXP_T_CV_RMS_MEAN, D.rms_mean, SDX_F64, {cfg->state_dim});
-  pset(h, SDXP_T_CV_RMS_VAR, D.rms_var, SDX_F64, {cfg->state_dim});
-  pset(h, SDXP_T_STATS, D.ctrl, SDX_F32, {(int64_t)(sizeof(SdxpCtrl) / 4)});
-  pset(h, SDXP_T_LAST_VALUES, D.last_values, SDX_F32, {(int64_t)N});
-  pset(h, SDXP_T_DEBUG, D.dbg, SDX_I64, {64});
-  pset(h, SDXP_T_ALL_GRADS, D.ac_g, SDX_F32, {(int64_t)(D.g_tail + 64)});
-  pset(h, SDXP_T_FACTORS, D.fact, SDX_F32, {(int64_t)D.foff.total});
-  pset(h, SDXP_T_FACTORS_ALL, D.fact_all, SDX_F32, {(int64_t)D.world, (int64_t)D.foff.total});
-  pset(h, SDXP_T_AC_ADAM_M, D.ac_m, SDX_F32, {(int64_t)D.off.total});
-  pset(h, SDXP_T_AC_ADAM_V, D.ac_v, SDX_F32, {(int64_t)D.off.total});
-  pset(h, SDXP_T_CV_ADAM_M, D.cv_m, SDX_F32, {(int64_t)D.coff.total});
-  pset(h, SDXP_T_CV_ADAM_V, D.cv_v, SDX_F32, {(int64_t)D.coff.total});
+  {   // the tensor registry: one row per sdxp_tensor_id (include/seqdex.h)
+    const int64_t n = N, hz = H, r = R, od = cfg->obs_dim, sd = cfg->state_dim, ad = cfg->act_dim, pa = D.off.total, pc = D.coff.total;
+    const struct { int id; void* ptr; int dtype; std::vector<int64_t> shape; } rows[] = {
+        {SDXP_T_AC_PARAMS, D.ac, SDX_F32, {pa}},             {SDXP_T_AC_GRADS, D.ac_g, SDX_F32, {pa}},
+        {SDXP_T_CV_PARAMS, D.cv, SDX_F32, {pc}},             {SDXP_T_CV_GRADS, D.cv_g, SDX_F32, {pc}},
+        {SDXP_T_MB_OBS, D.mb_obs, SDX_F32, {n, hz, od}},     {SDXP_T_MB_STATES, D.mb_states, SDX_F32, {n, hz, sd}},
+        {SDXP_T_MB_ACTIONS, D.mb_actions, SDX_F32, {n, hz, ad}},
+        {SDXP_T_MB_MUS, D.mb_mus, SDX_F32, {n, hz, ad}},     {SDXP_T_MB_SIGMAS, D.mb_sigmas, SDX_F32, {n, hz, ad}},
+        {SDXP_T_MB_NEGLOGP, D.mb_neglogp, SDX_F32, {n, hz}}, {SDXP_T_MB_VALUES, D.mb_values, SDX_F32, {n, hz}},
+        {SDXP_T_MB_REWARDS, D.mb_rewards, SDX_F32, {n, hz}}, {SDXP_T_MB_DONES, D.mb_dones, SDX_F32, {n, hz}},
+        {SDXP_T_RETURNS, D.returns, SDX_F32, {r}},           {SDXP_T_ADVANTAGES, D.adv, SDX_F32, {r}},
+        {SDXP_T_CV_RMS_MEAN, D.rms_mean, SDX_F64, {sd}},     {SDXP_T_CV_RMS_VAR, D.rms_var, SDX_F64, {sd}},
+        {SDXP_T_STATS, D.ctrl, SDX_F32, {(int64_t)(sizeof(SdxpCtrl) / 4)}},
+        {SDXP_T_LAST_VALUES, D.last_values, SDX_F32, {n}},   {SDXP_T_DEBUG, D.dbg, SDX_I64, {64}},
+        {SDXP_T_ALL_GRADS, D.ac_g, SDX_F32, {(int64_t)(D.g_tail + 64)}},
+        {SDXP_T_FACTORS, D.fact, SDX_F32, {D.foff.total}},   {SDXP_T_FACTORS_ALL, D.fact_all, SDX_F32, {D.world, D.foff.total}},
+        {SDXP_T_AC_ADAM_M, D.ac_m, SDX_F32, {pa}},           {SDXP_T_AC_ADAM_V, D.ac_v, SDX_F32, {pa}},
+        {SDXP_T_CV_ADAM_M, D.cv_m, SDX_F32, {pc}},           {SDXP_T_CV_ADAM_V, D.cv_v, SDX_F32, {pc}},
+    };
+    static_assert(sizeof(rows) / sizeof(rows[0]) == SDXP_T_COUNT, "one row per sdxp_tensor_id");
+    for (const auto& row : rows) {
+      auto& t = h->tinfo[row.id];
+      t.ptr = row.ptr; t.dtype = row.dtype; t.ndim = (int)row.shape.size();
+      for (int i = 0; i < 4; ++i) t.shape[i] = i < t.ndim ? row.shape[i] : 1;
+    }
+  }
   *out = h;
   return SDX_OK;
 }
@@ -390,13 +309,6 @@ static int plaunch_ok(sdxp_handle h, const char* what) {
   return SDX_OK;
 }
 
-__global__ void k_ctrl_begin_epoch(SdxpCtrl* c) {
-  c->mb_index = 0; c->mini_epoch = 0; c->n_mb = 0; c->prev_mb = 0; c->prev_mini_epoch = 0;
-  c->sum_a_loss = c->sum_c_loss = c->sum_b_loss = c->sum_kl = c->sum_cv_loss = c->sum_entropy = 0.0f;
-  for (int i = 0; i < 8; ++i) c->acc[i] = 0.0f;
-}
-__global__ void k_ctrl_begin_rollout(SdxpCtrl* c) { c->games_sum_rew = c->games_sum_len = c->games_cnt = 0.0f; }
-
 // trunk forward of `net` (0 actor, 2 central value) over M rows into the h_* activation buffers
 static void trunk_forward(sdxp_agent* h, int net, const float* x, int M, hipStream_t st) {
   const SdxpDev& D = h->D;
@@ -432,7 +344,7 @@ extern "C" int sdxp_act(sdxp_handle h, int32_t t, const float* obs_dev, const fl
                         const float* eps_dev, float* actions_out_dev, void* stream) {
   if (!h || !obs_dev || !states_dev || !actions_out_dev || t < 0 || t >= h->D.horizon) { if (h) h->err = "sdxp_act: bad argument"; return SDX_ERR_INVALID; }
   hipStream_t st = (hipStream_t)stream;
-  if (t == 0) hipLaunchKernelGGL(k_ctrl_begin_rollout, dim3(1), dim3(1), 0, st, h->D.ctrl);
+  if (t == 0) sdxpk_begin_rollout(&h->D, st);
   if (h->D.obs_cols != h->D.obs_dim) { sdxpk_pad_obs(&h->D, obs_dev, st); obs_dev = h->D.obs_pad; }
   trunk_forward2(h, obs_dev, states_dev, h->D.N, st);
   sdxpk_act_heads(&h->D, t, obs_dev, states_dev, dones_dev, eps_dev, actions_out_dev, h->act_counter++, st);
@@ -450,7 +362,8 @@ extern "C" int sdxp_finish_rollout(sdxp_handle h, const float* last_states_dev, 
   hipStream_t st = (hipStream_t)stream;
   trunk_forward(h, 2, last_states_dev, h->D.N, st);
   sdxpk_value_head(&h->D, h->D.last_values, st);
-  sdxpk_gae(&h->D, h->D.last_values, last_dones_dev, st);
+  sdxpk_gae_only(&h->D, h->D.last_values, last_dones_dev, st);
+  sdxpk_adv_norm(&h->D, st);
   return plaunch_ok(h, "sdxp_finish_rollout");
 }
 
@@ -463,8 +376,6 @@ extern "C" int sdxp_get_values(sdxp_handle h, const float* states_dev, float* va
   sdxpk_value_head(&h->D, values_out_dev, st);
   return plaunch_ok(h, "sdxp_get_values");
 }
-extern "C" void sdxpk_gae_only(const SdxpDev*, const float*, const int64_t*, hipStream_t);
-extern "C" void sdxpk_adv_norm(const SdxpDev*, hipStream_t);
 extern "C" int sdxp_discount_values(sdxp_handle h, const float* last_values_dev, const int64_t* last_dones_dev, void* stream) {
   if (!h || !last_values_dev) return SDX_ERR_INVALID;
   sdxpk_gae_only(&h->D, last_values_dev, last_dones_dev, (hipStream_t)stream);
@@ -476,13 +387,25 @@ extern "C" int sdxp_prepare_dataset(sdxp_handle h, void* stream) {
   return plaunch_ok(h, "sdxp_prepare_dataset");
 }
 
+// Begin of an epoch's update phase, one helper per path: cursor and loss sums of the control block back to zero, then the central-value
+// inputs of every minibatch (and, on the multi-kernel rank-MB paths, the cursor move that clears the accumulators of the first step)
+static void begin_epoch_big(sdxp_agent* h, hipStream_t st) { sdxpk_begin_epoch(&h->D, st); sdxpk_big_prenorm(&h->D, &h->bigws, st); }
+static void begin_epoch_rank_mb(sdxp_agent* h, bool persistent, hipStream_t st) {
+  sdxpk_begin_epoch(&h->D, st);
+  if (persistent) sdxpk_prenorm(&h->D, h->cfg.minibatch, st); else sdxpk_update_begin(&h->D, h->cfg.minibatch, st);
+}
+static bool rank_mb_ok(sdxp_agent* h, const char* who) {
+  if (sdxp_rank_mb(h->cfg.minibatch)) return true;   // the rank-MB kernels come in minibatch sizes 2 / 4 / 8
+  h->err = std::string(who) + ": minibatch_size must be 2/4/8 (rank-MB paths) or > 8 (GEMM path)";
+  return false;
+}
+
 extern "C" int sdxp_update(sdxp_handle h, void* stream) {
   if (!h) return SDX_ERR_INVALID;
   hipStream_t st = (hipStream_t)stream;
   const int MB = h->cfg.minibatch;
   if (h->big) {   // minibatch_size > 8 (ppo_continuous_insert.yaml: 4096): GEMM-shaped step, explicit gradients, clip + Adam
-    hipLaunchKernelGGL(k_ctrl_begin_epoch, dim3(1), dim3(1), 0, st, h->D.ctrl);
-    sdxpk_big_prenorm(&h->D, &h->bigws, st);
+    begin_epoch_big(h, st);
     for (int me = 0; me < h->cfg.mini_epochs; ++me)
       for (int mb = 0; mb < h->D.num_minibatches; ++mb) {
         sdxpk_big_step(&h->D, &h->bigws, mb, me, st);
@@ -490,10 +413,7 @@ extern "C" int sdxp_update(sdxp_handle h, void* stream) {
       }
     return plaunch_ok(h, "sdxp_update(large minibatch)");
   }
-  if (MB != 2 && MB != 4 && MB != 8) {
-    h->err = "sdxp_update: minibatch_size must be 2/4/8 (rank-MB paths) or > 8 (GEMM path)";
-    return SDX_ERR_INVALID;
-  }
+  if (!rank_mb_ok(h, "sdxp_update")) return SDX_ERR_INVALID;
   long total = (long)h->cfg.mini_epochs * h->D.num_minibatches;
   // debug step limit (tests/test_gpu_fullsize_properties.py pins the N = 1024 persistent update to the oracle step for step): the
   // update phase stops after SDXP_MAX_STEPS optimiser steps, in minibatch order, on whichever path the handle uses
@@ -506,24 +426,16 @@ extern "C" int sdxp_update(sdxp_handle h, void* stream) {
              "this in time to repeat it); this handle now uses the hipGraph path";
     return SDX_ERR_STATE;
   }
+  if (h->use_persist)
+    for (const auto& b : h->backup) PCHK(h, hipMemcpyAsync(b.bak, b.live, b.bytes, hipMemcpyDeviceToDevice, st));
+  begin_epoch_rank_mb(h, h->use_persist, st);
   if (h->use_persist) {
-    const size_t ra = (size_t)h->D.N * h->D.horizon * h->D.act_dim * sizeof(float), sd = (size_t)h->D.state_dim * sizeof(double);
-    PCHK(h, hipMemcpyAsync(h->mus_bak, h->D.mb_mus, ra, hipMemcpyDeviceToDevice, st));
-    PCHK(h, hipMemcpyAsync(h->sig_bak, h->D.mb_sigmas, ra, hipMemcpyDeviceToDevice, st));
-    PCHK(h, hipMemcpyAsync(h->rms_bak, h->D.rms_mean, sd, hipMemcpyDeviceToDevice, st));
-    PCHK(h, hipMemcpyAsync(h->rms_bak + h->D.state_dim, h->D.rms_var, sd, hipMemcpyDeviceToDevice, st));
-    PCHK(h, hipMemcpyAsync(h->ctrl_bak, h->D.ctrl, sizeof(SdxpCtrl), hipMemcpyDeviceToDevice, st));
-  }
-  hipLaunchKernelGGL(k_ctrl_begin_epoch, dim3(1), dim3(1), 0, st, h->D.ctrl);
-  if (h->use_persist) {
-    sdxpk_prenorm(&h->D, MB, st);
     h->last_was_step = false;
     unsigned* fail = h->bar_dev + SDXP_BAR_PERSIST_FAIL;
     if (sdxpk_update_persistent(&h->D, (int)total, fail, h->opts.persist_stamps, persist_fault(), st) != 0) { h->err = "persistent update launch failed"; return SDX_ERR_HIP; }
     PCHK(h, hipMemcpyAsync(h->fail_host, fail, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     return plaunch_ok(h, "sdxp_update(persistent)");
   }
-  sdxpk_update_begin(&h->D, MB, st);
   // a chunk of optimiser steps is captured once into a hipGraph (no step-dependent kernel arguments: all state
   // lives in the device control block) and replayed; the remainder is launched eagerly
   const int chunk = 32;
@@ -537,7 +449,6 @@ extern "C" int sdxp_update(sdxp_handle h, void* stream) {
       PCHK(h, hipStreamEndCapture(cs, &h->graph));
       PCHK(h, hipGraphInstantiate(&h->graph_exec, h->graph, nullptr, nullptr, 0));
       PCHK(h, hipStreamDestroy(cs));
-      h->graph_chunk = chunk;
     }
     for (; done + chunk <= total; done += chunk) PCHK(h, hipGraphLaunch(h->graph_exec, st));
   }
@@ -556,8 +467,7 @@ extern "C" int sdxp_backward(sdxp_handle h, int32_t which, int32_t mb, void* str
   if (h->big) {
     if (which == 1) return SDX_OK;
     if (mb < 0) {
-      hipLaunchKernelGGL(k_ctrl_begin_epoch, dim3(1), dim3(1), 0, st, h->D.ctrl);
-      sdxpk_big_prenorm(&h->D, &h->bigws, st);
+      begin_epoch_big(h, st);
       h->big_me = 0; h->big_next = 0;
       return plaunch_ok(h, "sdxp_backward(begin, large minibatch)");
     }
@@ -567,11 +477,10 @@ extern "C" int sdxp_backward(sdxp_handle h, int32_t which, int32_t mb, void* str
     if (h->big_next >= h->D.num_minibatches) { h->big_next = 0; h->big_me += 1; }
     return plaunch_ok(h, "sdxp_backward(large minibatch)");
   }
-  if (MB != 2 && MB != 4 && MB != 8) { h->err = "sdxp_backward: minibatch_size must be 2/4/8"; return SDX_ERR_INVALID; }
+  if (!rank_mb_ok(h, "sdxp_backward")) return SDX_ERR_INVALID;
   if (which == 1) return SDX_OK;
   if (mb < 0) {
-    hipLaunchKernelGGL(k_ctrl_begin_epoch, dim3(1), dim3(1), 0, st, h->D.ctrl);
-    sdxpk_update_begin(&h->D, MB, st);
+    begin_epoch_rank_mb(h, false, st);
     return plaunch_ok(h, "sdxp_backward(begin)");
   }
   if (mb >= h->D.num_minibatches) { h->err = "sdxp_backward: minibatch index out of range"; return SDX_ERR_INVALID; }
@@ -586,7 +495,7 @@ extern "C" int sdxp_backward_factors(sdxp_handle h, int32_t mb, void* stream) {
   if (!h) return SDX_ERR_INVALID;
   hipStream_t st = (hipStream_t)stream;
   const int MB = h->cfg.minibatch;
-  if (MB != 2 && MB != 4 && MB != 8) { h->err = "sdxp_backward_factors: minibatch_size must be 2/4/8"; return SDX_ERR_INVALID; }
+  if (!rank_mb_ok(h, "sdxp_backward_factors")) return SDX_ERR_INVALID;
   if (mb < 0) return sdxp_backward(h, 0, -1, stream);
   if (mb >= h->D.num_minibatches) { h->err = "sdxp_backward_factors: minibatch index out of range"; return SDX_ERR_INVALID; }
   if (h->use_persist_step) {   // one launch: forward + backward on 256 CUs with tagged-word exchange, factors straight into D.fact
@@ -617,7 +526,7 @@ extern "C" int sdxp_apply_factors(sdxp_handle h, void* stream) {
 // all-reduced in place (SUM) through the SDXP_T_STATS view.
 extern "C" int sdxp_apply(sdxp_handle h, int32_t which, float kl, void* stream) {
   if (!h || which < 0 || which > 1) return SDX_ERR_INVALID;
-  sdxpk_apply_explicit(&h->D, which, kl, h->cfg.world_size > 0 ? h->cfg.world_size : 1, (hipStream_t)stream);
+  sdxpk_apply_explicit(&h->D, which, kl, h->D.world, (hipStream_t)stream);
   return plaunch_ok(h, "sdxp_apply");
 }
 // Blocks until the update launched by sdxp_update on `stream` has finished.  SDX_OK, or SDX_ERR_STATE if the persistent kernel gave
@@ -659,13 +568,8 @@ extern "C" int sdxp_update_status(sdxp_handle h, void* stream) {
   }
   *h->fail_host = 0;
   h->use_persist = false;
-  const size_t ra = (size_t)h->D.N * h->D.horizon * h->D.act_dim * sizeof(float), sd = (size_t)h->D.state_dim * sizeof(double);
   PCHK(h, hipMemsetAsync(h->bar_dev, 0, SDXP_BAR_CLEAR * sizeof(unsigned), st));
-  PCHK(h, hipMemcpyAsync(h->D.mb_mus, h->mus_bak, ra, hipMemcpyDeviceToDevice, st));
-  PCHK(h, hipMemcpyAsync(h->D.mb_sigmas, h->sig_bak, ra, hipMemcpyDeviceToDevice, st));
-  PCHK(h, hipMemcpyAsync(h->D.rms_mean, h->rms_bak, sd, hipMemcpyDeviceToDevice, st));
-  PCHK(h, hipMemcpyAsync(h->D.rms_var, h->rms_bak + h->D.state_dim, sd, hipMemcpyDeviceToDevice, st));
-  PCHK(h, hipMemcpyAsync(h->D.ctrl, h->ctrl_bak, sizeof(SdxpCtrl), hipMemcpyDeviceToDevice, st));
+  for (const auto& b : h->backup) PCHK(h, hipMemcpyAsync(b.live, b.bak, b.bytes, hipMemcpyDeviceToDevice, st));   // the list of sdxp_update, copied back
   PCHK(h, hipStreamSynchronize(st));
   {   // the restored block carries the tag from BEFORE the failed launch: move it past every word that launch may have written
     SdxpCtrl c;

@@ -23,6 +23,7 @@
 #include <cstdint>
 
 #include "sdx_common.h"
+#include "sdxp_launch.h"
 
 namespace {
 typedef unsigned long long u64;

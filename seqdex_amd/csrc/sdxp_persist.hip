@@ -18,13 +18,14 @@
 //   W2 columns   : CU g owns columns 2g, 2g+1: lanes l / l ^ 32 of wave w = row 32w + (l & 31) of the two columns (backward; duplicate copy)
 //   heads        : CU g runs Adam for 25 of the 6 400 head weights and publishes them; every CU reads the matrix back in phase D
 // Row and column copies receive the same gradient g[n][k] = sum_s dY_s[n] X_s[k] (same operands, same order), so they
-// stay bit-identical without communication.  The multi-kernel path (sdxp_kernels.hip) remains the fallback for other shapes
+// stay bit-identical without communication.  The multi-kernel path (sdxp_update.hip) remains the fallback for other shapes
 // and the explicit-gradient multi-rank path.
 #include <cstddef>
 #include <cstdlib>
 
 #include "sdx_common.h"
-#include "sdxp_types.h"
+#include "sdxp_device.h"   // elu, dpp_add, wave_sum
+#include "sdxp_launch.h"
 
 namespace {
 // OBS is the LARGEST actor/critic input width (GraspSim, 396); narrower inputs (Orient: 188) run with the tail columns masked off
@@ -37,18 +38,7 @@ constexpr int HR = 4;                  // head rows per wave (25 rows over 8 wav
 constexpr int HPC = (ACT + 2) * U2 / NWG;   // head weights whose Adam state one CU owns (25)
 static_assert(HPC * NWG == (ACT + 2) * U2 && U2 == 256, "head ownership split");
 
-__device__ __forceinline__ float elu(float x) { return x > 0.0f ? x : expm1f(x); }
 __device__ __forceinline__ float elu_g(float h) { return h > 0.0f ? 1.0f : h + 1.0f; }
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_add(float v) {
-  const int r = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xF, false);
-  return v + __builtin_bit_cast(float, r);
-}
-__device__ __forceinline__ float wave_sum(float v) {
-  v = dpp_add<0xB1, 0xF>(v); v = dpp_add<0x4E, 0xF>(v); v = dpp_add<0x141, 0xF>(v); v = dpp_add<0x140, 0xF>(v);
-  v = dpp_add<0x142, 0xA>(v); v = dpp_add<0x143, 0xC>(v);
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
 // v + (the value of lane ^ 32), in both lanes: v_permlane32_swap_b32 of v with itself leaves the lower half's values in one result and the
 // upper half's in the other
 __device__ __forceinline__ float pair_sum(float v) {

@@ -1,7 +1,7 @@
 // sdxp_ppo_terms.h — rl_games' PPO arithmetic of one minibatch, stated once: the loss terms per (row, action) and per row with
 // their gradients, the step rules (clip_grad_norm_ scale, Adam bias corrections, legacy adaptive learning rate), the Adam element
 // functions and the control block's bookkeeping.  Functions of scalars: no thread index, no LDS, no global memory; how a kernel
-// spreads rows and actions over its lanes and reduces the summands is the kernel's own (sdxp_kernels.hip, sdxp_bigmb.hip).
+// spreads rows and actions over its lanes and reduces the summands is the kernel's own (sdxp_update.hip, sdxp_bigmb.hip).
 // k_update_persistent (sdxp_persist.hip) restates the loss phase and the step rules in place: its schedule depends on the text.
 #pragma once
 #include "sdx_common.h"

@@ -1,4 +1,4 @@
-// sdxp_types.h — device-side tables of the PPO engine (shared by sdxp_kernels.hip and sdxp_capi.hip)
+// sdxp_types.h — device-side tables of the PPO engine (shared by sdxp_capi.hip and the units that hold its kernels)
 #pragma once
 #include <stdint.h>
 
@@ -36,6 +36,12 @@ struct SdxpCtrl {
 };
 
 #define SDXP_LL_WORDS 65536
+
+// SdxpDev::sqn_part (floats): block partials of the gradient-norm reductions ([2][512] of k_sqnorm2, [2][SDXP_SQN_STRIDE] per-workgroup shares of the factor path), then the 16-byte tagged words of the one-launch apply ([SDXP_SQN_STRIDE] workgroups, [64] groups)
+#define SDXP_SQN_STRIDE 2048
+#define SDXP_TW_OFF (2 * SDXP_SQN_STRIDE)
+#define SDXP_SQN_FLOATS (8 * SDXP_SQN_STRIDE)
+static_assert(SDXP_TW_OFF + 4 * (SDXP_SQN_STRIDE + 64) <= SDXP_SQN_FLOATS && SDXP_SQN_FLOATS * 4 == 65536, "the tagged words of the one-launch apply must fit behind the partials");
 
 // words of a handle's barrier block (unsigned[SDXP_BAR_WORDS] in HBM): fail flag of the persistent kernels, fail flag of the one-launch apply,
 // its launch counter (= tag of its exchange words); a failed persistent launch zeroes the words below the launch counter
@@ -84,13 +90,13 @@ struct SdxpDev {
   int32_t world;
   int32_t obs_cols;      // columns of the caller's observation rows (<= obs_dim); obs_pad [N, obs_dim] holds the zero-padded copy
   float* obs_pad;
-  float* sqn_part;       // [512] block partials of the deterministic gradient-norm reduction
+  float* sqn_part;       // [SDXP_SQN_FLOATS] block partials of the deterministic gradient-norm reductions, tagged words of the one-launch apply
   size_t g_tail;         // ALL_GRADS = [ac_g | pad | cv_g | pad | kl word | pad]: offset (floats, from ac_g) of the kl word
   int32_t bf16;          // large-minibatch path: trunk GEMMs on bf16 MFMA (fp32 sources, accumulation, weights and optimiser state)
   unsigned long long* ll; // [SDXP_LL_WORDS] (value, step tag) words exchanged between the CUs of the persistent update kernel
 };
 
-// workspace of the large-minibatch update path (sdxp_bigmb.hip), allocated by sdxp_capi.hip
+// workspace of the large-minibatch update path (sdxp_bigmb.hip: laid out by sdxpk_big_setup through the handle's allocator)
 struct SdxpBigWs {
   float* h[3][3];             // trunk outputs  [MB][units[l]] in fp32 (the heads read l = 2; bf16 NT runs do not write l = 0, 1: see hn)
   float* dy[3][3];            // dLoss/d(pre-activation) [MB][units[l]] (NT path: only l = 2, written by the head kernels)

@@ -1,5 +1,6 @@
 """Python binding of the sdxp_* C ABI (include/seqdex.h): the PPO inner loops of rl_games' A2CAgent on the GPU.
-torch is plumbing (pointers, streams); arithmetic is in libseqdex_hip.so (seqdex_amd/csrc/sdxp_kernels.hip)."""
+torch is plumbing (pointers, streams); arithmetic is in libseqdex_hip.so (seqdex_amd/csrc/sdxp_rollout.hip,
+sdxp_update.hip, sdxp_multirank.hip, sdxp_persist.hip, sdxp_bigmb.hip; host side sdxp_capi.hip)."""
 import ctypes as C
 
 import torch

@@ -104,7 +104,7 @@ def test_two_processes_step_together(tmp_path, minibatch):
         torch.cuda.synchronize()
         # Bit equality is NOT attainable on this forward / backward implementation: the multi-kernel step (SDXP_STEP_IMPL=kernels, the only
         # one two processes can run beside each other on one GPU) sums its split-N data gradients and Gram partials with float atomics
-        # (csrc/sdxp_kernels.hip: k_back, gram_sums), so each rank's FACTORS differ by an ulp from run to run; the replicas of one run still
+        # (csrc/sdxp_update.hip: k_back, gram_sums), so each rank's FACTORS differ by an ulp from run to run; the replicas of one run still
         # agree bit for bit (asserted above) because both rebuild the gradient from the same gathered factors.  What is asserted is that the
         # emulation lands within the noise those atomics can make over the run (measured: 2e-6 after 160 steps), with its own replicas identical.
         for k, tk in (("ac", "AC_PARAMS"), ("cv", "CV_PARAMS")):
