@@ -12,8 +12,6 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "seqdex_amd", "csrc")
 _SO = os.path.join(HERE, "libsdx_emu.so")
 _SRCS = [os.path.join(HERE, "hipemu.cpp"), os.path.join(HERE, "physics_driver.cpp"), os.path.join(CSRC, "sdx_physics.hip")]
-_DEPS = _SRCS + [os.path.abspath(__file__), os.path.join(HERE, "include", "hip", "hip_runtime.h"), os.path.join(CSRC, "sdx_common.h"),
-                 os.path.join(CSRC, "sdx_const_build.h"), os.path.join(ROOT, "include", "seqdex.h")]
 # extra g++ flags for every emulator build (e.g. "-DSDX_D_SORT": a compile-time variant of a kernel under test); rebuild with force=True after changing it
 _EXTRA = os.environ.get("SDX_EMU_CXXFLAGS", "").split()
 _lib = None
@@ -25,8 +23,23 @@ _SIM_SRCS = [os.path.join(HERE, "hipemu.cpp"), os.path.join(HERE, "sim_driver.cp
 _sim_lib = None
 
 
+def _headers():
+    """what any source of csrc may include: every csrc/*.h (sdx_physics.hip's private sdx_phys_*.h among them) and the C ABI"""
+    return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")] + [os.path.join(ROOT, "include", "seqdex.h")]
+
+
+def build_deps():
+    """the files build() compares libsdx_emu.so against (tests/test_hipemu_deps.py holds the list to the sources' #include lines)"""
+    return _SRCS + [os.path.abspath(__file__), os.path.join(HERE, "include", "hip", "hip_runtime.h")] + _headers()
+
+
+def build_sim_deps():
+    """the same for build_sim(); sdx_randomize.hip: sdx_capi.hip includes it under HIPEMU"""
+    return _SIM_SRCS + [os.path.abspath(__file__), os.path.join(HERE, "include", "hip", "hip_runtime.h")] + _headers() + [os.path.join(CSRC, "sdx_randomize.hip")]
+
+
 def build(force=False):
-    if not force and os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in _DEPS):
+    if not force and os.path.exists(_SO) and all(os.path.getmtime(_SO) >= os.path.getmtime(d) for d in build_deps()):
         return _SO
     objs = []
     for src in _SRCS:
@@ -40,9 +53,7 @@ def build(force=False):
 
 
 def build_sim(force=False):
-    deps = _SIM_SRCS + [os.path.abspath(__file__), os.path.join(HERE, "include", "hip", "hip_runtime.h"), os.path.join(ROOT, "include", "seqdex.h")] + \
-        [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(CSRC, "sdx_randomize.hip")]   # sdx_capi.hip includes it here
-    if not force and os.path.exists(_SIM_SO) and all(os.path.getmtime(_SIM_SO) >= os.path.getmtime(d) for d in deps):
+    if not force and os.path.exists(_SIM_SO) and all(os.path.getmtime(_SIM_SO) >= os.path.getmtime(d) for d in build_sim_deps()):
         return _SIM_SO
     objs = []
     for src in _SIM_SRCS:

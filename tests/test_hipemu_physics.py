@@ -1,4 +1,4 @@
-"""CPU (-m "not gpu"): the product's k_physics / k_kinematics SOURCE (seqdex_amd/csrc/sdx_physics.hip), compiled by g++ against the
+"""CPU (-m "not gpu"): the product's k_physics / k_kinematics SOURCE (seqdex_amd/csrc/sdx_physics.hip and the sdx_phys_*.h it includes), compiled by g++ against the
 SIMT emulator of tests/hipemu (one fiber per GPU thread, barriers and wave collectives emulated) and executed on the CPU, against
 oracle/physics_oracle.c.  This checks the kernel's LOGIC - indexing, barriers, scans, the contact order, the gather lists - without a
 GPU; the `-m gpu` parity tests remain the check of the compiled gfx950 code.  Tolerances are tighter than on the GPU because both

@@ -2,7 +2,7 @@
 """Where does k_physics' LAUNCH time go?  Timing ablations on an identical state (profiling build only: make -C seqdex_amd/csrc prof,
 SDX_LIB_PATH=.../libseqdex_prof.so).  The bench workload is stepped to a contact-rich state, every piece of state the kernel reads is
 snapshotted (root, dof, targets, warm-start cache), and each configuration is timed on launches that start from that snapshot with a set
-of ablation bits in SDX_T_DEBUG[63] (csrc/sdx_physics.hip: ABL).  launch(all) - launch(without X) = what X costs with both
+of ablation bits in SDX_T_DEBUG[63] (csrc/sdx_phys_lds.h: ABL).  launch(all) - launch(without X) = what X costs with both
 workgroups of a CU competing - which the single-env phase clock cannot say.
 usage: python tools/ablate_physics.py [N] [warm-steps]"""
 import json

@@ -1,5 +1,6 @@
 """Static check of k_physics<512>'s gfx950 code: registers, scratch bytes per lane, and the scratch / LDS / VALU instruction counts of the
-solver's iteration loop (the ISA between the source lines of the loop head and of its closing stamp, via -gline-tables-only).
+solver's iteration loop (the ISA between the source lines of the loop head and of its closing stamp, via -gline-tables-only).  The loop
+is looked for in sdx_physics.hip and the sdx_phys_*.h it includes; code inlined from other lines of those files is not part of the loop.
 usage: python tools/isa_check.py [--randomize] [extra hipcc flags...]      (cross-compiles; no GPU needed)
 --randomize: the same report for the domain-randomization variant k_physics<512 | SDX_PHYS_DR> (= k_physics<513>)"""
 import os
@@ -9,13 +10,17 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "seqdex_amd", "csrc", "sdx_physics.hip")
+CSRC = os.path.join(ROOT, "seqdex_amd", "csrc")
+SRC = os.path.join(CSRC, "sdx_physics.hip")
 RANDOMIZE = "--randomize" in sys.argv
 if RANDOMIZE:
     sys.argv.remove("--randomize")
 KERN = "_Z9k_physicsILi513EEvPK8SdxConst6SdxBuf" if RANDOMIZE else "_Z9k_physicsILi512EEvPK8SdxConst6SdxBuf"
 
-src = open(SRC).read().split("\n")
+# the unit's files: the .hip and the private headers it includes; the one with the loop markers is where the loop's lines are counted
+UNIT = ["sdx_physics.hip"] + re.findall(r'^#include "(sdx_phys_\w+\.h)"', open(SRC).read(), flags=re.M)
+LOOPFILE = next(f for f in UNIT if "for (int it = it0;" in open(os.path.join(CSRC, f)).read())
+src = open(os.path.join(CSRC, LOOPFILE)).read().split("\n")
 lo = next(i for i, l in enumerate(src) if "for (int it = it0;" in l) + 1
 hi = next(i for i, l in enumerate(src) if "SSTAMP(22);" in l and i > lo) + 1
 with tempfile.TemporaryDirectory() as td:
@@ -32,15 +37,17 @@ with tempfile.TemporaryDirectory() as td:
     loop = {"scratch": 0, "ds": 0, "valu": 0, "salu": 0, "barrier": 0, "total": 0}
     tot_scratch = 0
     seen_lo = False
-    fileno = None
+    fileno, unit_nos = None, set()
     for line in open(os.path.join(td, asm)):
         if line.startswith(KERN + ":"):
             inside = True
             continue
-        if not inside:
-            m = re.match(r'\s*\.file\s+(\d+)\s+"[^"]*"\s+"sdx_physics.hip"', line)
-            if m:
+        m = re.match(r'\s*\.file\s+(\d+)\s+"[^"]*"\s+"(?:[^"]*/)?(sdx_phys\w+\.h(?:ip)?)"', line)   # (a header's comes where its first line is used)
+        if m and m.group(2) in UNIT:
+            unit_nos.add(int(m.group(1)))
+            if m.group(2) == LOOPFILE:
                 fileno = int(m.group(1))
+        if not inside:
             continue
         if ".end_amdhsa_kernel" in line or line.startswith("\t.section"):
             break
@@ -48,6 +55,8 @@ with tempfile.TemporaryDirectory() as td:
         if m:
             if int(m.group(1)) == fileno:
                 cur = int(m.group(2))
+            elif int(m.group(1)) in unit_nos:   # another file of the unit: as far from the loop as another line of the loop's file
+                cur = None
             continue
         t = line.strip()
         if not t or t[0] in ";." or t.endswith(":"):
@@ -68,4 +77,4 @@ with tempfile.TemporaryDirectory() as td:
             elif op.startswith("s_"):
                 loop["salu"] += 1
     print("scratch instructions in the kernel:", tot_scratch)
-    print("iteration loop (source lines %d-%d):" % (lo, hi), loop)
+    print("iteration loop (%ssource lines %d-%d):" % ("" if LOOPFILE == "sdx_physics.hip" else LOOPFILE + ", ", lo, hi), loop)

@@ -5,9 +5,10 @@ the other lacks.  Kernels are matched by symbol across all files of a side: one 
 next to its verdict, not as dropped and added.  Comments, debug / .loc / .file lines, the function numbers inside local labels and the order of the symbols are ignored.
 
     git worktree add /tmp/parent HEAD~1      (a whole checkout: the sources include ../../include/seqdex.h)
-    python tools/kernel_identity.py /tmp/parent/seqdex_amd/csrc [--out profiles/kernel_identity.txt] [--work DIR] [--jobs 8]
+    python tools/kernel_identity.py /tmp/parent/seqdex_amd/csrc [--out profiles/kernel_identity.txt] [--work DIR] [--jobs 8] [--flags "-DSDX_PHASE_CLOCK"]
 
-Cross-compiles; no GPU needed.  --work keeps the assembly between runs (a side is recompiled when one of its sources is newer).  Exit 1 on a difference."""
+--flags: extra hipcc flags appended on both sides (the profiling builds: "-DSDX_PHASE_CLOCK", "-DSDX_PHASE_CLOCK -DSDX_LANE_CLOCK"); give
+each set of flags a --work of its own.  Cross-compiles; no GPU needed.  --work keeps the assembly between runs (a side is recompiled when one of its sources is newer).  Exit 1 on a difference."""
 import argparse
 import concurrent.futures
 import glob
@@ -30,12 +31,12 @@ def makefile_flags(csrc):
 FLAGS, EXTRA = makefile_flags(os.path.join(ROOT, "seqdex_amd", "csrc"))
 
 
-def compile_one(csrc, name, out):
+def compile_one(csrc, name, out, extra=()):
     os.makedirs(out, exist_ok=True)
     asm = glob.glob(os.path.join(out, name + "-hip-amdgcn-*gfx950*.s"))
     newest = max(os.path.getmtime(f) for f in glob.glob(os.path.join(csrc, "*.h*")))
     if not asm or os.path.getmtime(asm[0]) < newest:
-        cmd = ["/opt/rocm/bin/hipcc"] + FLAGS + EXTRA.get(name, []) + ["-save-temps=obj", "-c", os.path.join(csrc, name + ".hip"), "-o", os.path.join(out, name + ".o")]
+        cmd = ["/opt/rocm/bin/hipcc"] + FLAGS + EXTRA.get(name, []) + list(extra) + ["-save-temps=obj", "-c", os.path.join(csrc, name + ".hip"), "-o", os.path.join(out, name + ".o")]
         r = subprocess.run(cmd, capture_output=True, text=True, cwd=out)
         if r.returncode != 0:
             raise RuntimeError("%s: %s" % (name, r.stderr[-2000:]))
@@ -68,13 +69,18 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--work", default="")
     ap.add_argument("--jobs", type=int, default=8)
-    a = ap.parse_args()
+    ap.add_argument("--flags", default="", help="extra hipcc flags for every file of both sides")
+    argv = sys.argv[1:]
+    if "--flags" in argv[:-1]:   # (argparse takes a lone value that begins with "-" for an option: hand it over as --flags=VALUE)
+        i = argv.index("--flags")
+        argv[i:i + 2] = ["--flags=" + argv[i + 1]]
+    a = ap.parse_args(argv)
     mine = os.path.join(ROOT, "seqdex_amd", "csrc")
     work = a.work or tempfile.mkdtemp(prefix="kernel_identity_")
     sides = (("other", a.other), ("this", mine))
     files = {side: sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(d, "*.hip"))) for side, d in sides}
     with concurrent.futures.ThreadPoolExecutor(a.jobs) as ex:
-        fut = {(side, n): ex.submit(compile_one, d, n, os.path.join(work, side, n)) for side, d in sides for n in files[side]}
+        fut = {(side, n): ex.submit(compile_one, d, n, os.path.join(work, side, n), a.flags.split()) for side, d in sides for n in files[side]}
         asm = {k: f.result() for k, f in fut.items()}
     # {(file, symbol): text} per side; a kernel is matched in its own file first (two files may each have a static kernel of one name),
     # then by symbol across all files of a side when exactly one of that name is left over on either side: it moved
@@ -97,7 +103,7 @@ def main():
     sys.stdout.write(text)
     if a.out:
         with open(a.out, "w") as fh:
-            fh.write("# python tools/kernel_identity.py <csrc of the parent commit>: gfx950 instruction text + .amdhsa_* resources per kernel, parent vs this tree\n" + text)
+            fh.write("# python tools/kernel_identity.py <csrc of the parent commit>: gfx950 instruction text + .amdhsa_* resources per kernel, parent vs this tree%s\n" % (a.flags and "; extra flags on both sides: " + a.flags) + text)
     return 1 if bad else 0
 
 
