@@ -268,6 +268,34 @@ __device__ __forceinline__ void row_butterfly(const float (&v)[N], float (&u2)[(
     u2[j] = t;
   }
 }
+// N wave sums at once: the row butterfly, then the rows meet through v_permlane16_swap (partner lane ^ 16: rows 0 + 1, 2 + 3) and
+// v_permlane32_swap (lane ^ 32).  Every lane ends with u[j] = the whole wave's sum of value 4 j + (lane & 3).  The pairs of the six levels
+// are those of wave_sum's DPP tree (quad_perm, quad_perm, row_half_mirror, row_mirror, row_bcast15, row_bcast31) and IEEE addition
+// commutes, so u[j] equals wave_sum(v[4 j + (lane & 3)]) bit for bit - at N / 2, N / 4, N / 4, ... adds per level instead of N.
+template <int N>
+__device__ __forceinline__ void wave_sums(const float (&v)[N], float (&u)[(N + 3) / 4], int lane) {
+  // (opaque copies: the sums are those of the ROUNDED values - a value that is a bare product must not be contracted with the butterfly's first
+  // add into an fma, through the level's select.  wave_sum of a bare product IS contracted that way, per lane, which no butterfly reproduces:
+  // forward L2 therefore keeps its twelve trees.)
+  float t[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) { t[i] = v[i]; asm("" : "+v"(t[i])); }
+  row_butterfly<N>(t, u, lane);
+#pragma unroll
+  for (int j = 0; j < (N + 3) / 4; ++j) {
+    const unsigned x = __builtin_bit_cast(unsigned, u[j]);
+    const auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+    u[j] = pair_sum(__builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]));
+  }
+}
+// the forward passes' partial dot products, value net MB + s: lane s < MB holds u[net] = this wave's sum of (net, sample s)
+static_assert(MB == 4, "lane & 3 of wave_sums is the sample");
+__device__ __forceinline__ void fpart_store(PLds& S, const float (&u)[3], int wave, int lane) {
+  if (lane < MB) {
+#pragma unroll
+    for (int net = 0; net < 3; ++net) S.fpart[(net * MB + lane) * NWV + wave] = u[net];
+  }
+}
 template <int N4>
 __device__ __forceinline__ void rows_store(PLds& S, const float (&u2)[N4], int off, int wave, int lane) {
   if ((lane & 15) < 4) {
@@ -572,13 +600,14 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
           for (int s = 0; s < MB; ++s) pv[s] += w0v[i] * S.cvx[s][k];
         }
       }
-      // (all twelve wave reductions first - independent DPP chains the scheduler interleaves - then the stores: one reduction, one store
-      // at a time serialises the chains behind each other's LDS traffic; same sums, same order, bit-identical results)
+      // (the twelve wave sums as ONE halving butterfly, value net MB + s: lane s < 4 ends with sample s of the three networks and stores them;
+      // same pairs as twelve wave_sum trees, bit-identical results)
+      {
+        float v[3 * MB], u[3];
 #pragma unroll
-      for (int s = 0; s < MB; ++s) { pa[s] = wave_sum(pa[s]); pc[s] = wave_sum(pc[s]); pv[s] = wave_sum(pv[s]); }
-      if (lane == 0) {
-#pragma unroll
-        for (int s = 0; s < MB; ++s) { S.fpart[(0 * MB + s) * NWV + wave] = pa[s]; S.fpart[(1 * MB + s) * NWV + wave] = pc[s]; S.fpart[(2 * MB + s) * NWV + wave] = pv[s]; }
+        for (int s = 0; s < MB; ++s) { v[0 * MB + s] = pa[s]; v[1 * MB + s] = pc[s]; v[2 * MB + s] = pv[s]; }
+        wave_sums<3 * MB>(v, u, lane);
+        fpart_store(S, u, wave, lane);
       }
       __syncthreads();
       if (tid < MB * 4) {   // (sample s, owned row r): the three networks' outputs in one packed word
@@ -655,28 +684,20 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       TS(4)
       __syncthreads();
       {
-        float q[3][MB];
+        float q[3 * MB], u[3];   // value net MB + s
 #pragma unroll
         for (int net = 0; net < 3; ++net) {
 #pragma unroll
-          for (int s = 0; s < MB; ++s) q[net][s] = 0.0f;
+          for (int s = 0; s < MB; ++s) q[net * MB + s] = 0.0f;
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const int k = q1 * 256 + lane + 64 * i;
 #pragma unroll
-            for (int s = 0; s < MB; ++s) q[net][s] += w1[net][i] * S.x1[net][s][k];
+            for (int s = 0; s < MB; ++s) q[net * MB + s] += w1[net][i] * S.x1[net][s][k];
           }
         }
-#pragma unroll
-        for (int net = 0; net < 3; ++net)
-#pragma unroll
-          for (int s = 0; s < MB; ++s) q[net][s] = wave_sum(q[net][s]);
-        if (lane == 0) {
-#pragma unroll
-          for (int net = 0; net < 3; ++net)
-#pragma unroll
-            for (int s = 0; s < MB; ++s) S.fpart[(net * MB + s) * NWV + wave] = q[net][s];
-        }
+        wave_sums<3 * MB>(q, u, lane);
+        fpart_store(S, u, wave, lane);
       }
       __syncthreads();
       if (tid < MB * 2) {
@@ -786,6 +807,10 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       // (no barrier here: the one that stood between the S.x2 stores and their read-back also kept the S.fpart stores below behind forward L1's
       // readers of S.fpart - the barrier in front of phase C does that - and the S.x2 stores in front of their readers, which all sit behind
       // the barrier that follows the S.fpart stores)
+      // (twelve wave_sum trees, NOT the one butterfly of the other forward phases: a value here is a bare product, and the compiler contracts
+      // it with the tree's first add - lane l adds its EXACT w2 x2 to the rounded product of lane l ^ 1, one fma - so the two lanes of a pair hold
+      // different bits and the tree's result is the one that reaches lane 63.  A butterfly whose lane pairs each keep half of the values cannot
+      // form those bits: it was tried, x3 moved in its last place.  Same code as before, same bits.)
 #pragma unroll
       for (int net = 0; net < 3; ++net)
 #pragma unroll
@@ -912,7 +937,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     {
       // rows wave, wave + 8, wave + 16 (< 23: actor rows, except row 23 = the critic's value on wave 7) and wave + 24 (only wave 0: row 24,
       // the central value): the actor rows of a wave share ONE set of x3 loads
-      float q[HR][MB], xa[MB][4];
+      float q[HR * MB], u[HR], xa[MB][4];   // value MB j + s: lane s < 4 ends with sample s of the wave's rows
 #pragma unroll
       for (int s = 0; s < MB; ++s)
 #pragma unroll
@@ -924,7 +949,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
           float t = 0.0f;
 #pragma unroll
           for (int e = 0; e < 4; ++e) t += wh[j][e] * xa[s][e];
-          q[j][s] = t;
+          q[MB * j + s] = t;
         }
       if (wave == NWV - 1) {          // row 23: critic value (net 1)
 #pragma unroll
@@ -932,7 +957,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
           float t = 0.0f;
 #pragma unroll
           for (int e = 0; e < 4; ++e) t += wh[2][e] * S.x3[1][s][lane + 64 * e];
-          q[2][s] = t;
+          q[MB * 2 + s] = t;
         }
       } else {
 #pragma unroll
@@ -940,30 +965,32 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
           float t = 0.0f;
 #pragma unroll
           for (int e = 0; e < 4; ++e) t += wh[2][e] * xa[s][e];
-          q[2][s] = t;
+          q[MB * 2 + s] = t;
         }
       }
-#pragma unroll
-      for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int s = 0; s < MB; ++s) q[j][s] = wave_sum(q[j][s]);                       // 12 independent chains, then the stores
-      if (wave == 0) {                // row 24: central value (net 2)
+      if (wave == 0) {                // row 24: central value (net 2), the fourth quad of a 16-wide butterfly on this wave only
 #pragma unroll
         for (int s = 0; s < MB; ++s) {
           float t = 0.0f;
 #pragma unroll
           for (int e = 0; e < 4; ++e) t += wh[3][e] * S.x3[2][s][lane + 64 * e];
-          q[3][s] = wave_sum(t);
+          q[MB * 3 + s] = t;
         }
+        wave_sums<HR * MB>(q, u, lane);
+      } else {
+        float q3[3 * MB], u3[3];
+#pragma unroll
+        for (int i = 0; i < 3 * MB; ++i) q3[i] = q[i];
+        wave_sums<3 * MB>(q3, u3, lane);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) u[j] = u3[j];
+        u[3] = 0.0f;
       }
-      if (lane == 0) {
+      if (lane < MB) {                // sample s = lane: one bias per row
 #pragma unroll
         for (int j = 0; j < HR; ++j) {
           const int row = wave + 8 * j;
-          if (row < A + 2) {
-#pragma unroll
-            for (int s = 0; s < MB; ++s) { const float y = q[j][s] + S.bias[21 + row]; if (row < A) S.mu[s][row] = y; else S.val[row - A][s] = y; }
-          }
+          if (row < A + 2) { const float y = u[j] + S.bias[21 + row]; if (row < A) S.mu[lane][row] = y; else S.val[row - A][lane] = y; }
         }
       }
     }
@@ -992,23 +1019,16 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     const float invM = 1.0f / (float)MB;
     // (the loss phase restates sdxp_ppo_terms.h in place: calling its functions here changed this kernel's register allocation and schedule)
     {
-      float r_nlp = 0.0f, r_kl = 0.0f, r_bl = 0.0f, r_ent = 0.0f;
+      // (only what the gradients need: the KL, bounds and entropy terms of the statistics are formed in the dY1 shadow, on waves 5 and 7)
+      float r_nlp = 0.0f;
       if (tid < MB * 32) {
         const int s = tid / 32, a = tid % 32;
         // z of (sample s, action a): formed by the thread that uses it here; S.z is only for the dmu / dlogstd lanes after the barrier below
         const float zz = (a < A) ? (S.act[s][a] - S.mu[s][a]) / S.sgm[a] : 0.0f;
         S.z[s][a] = zz;
-        if (a < A) {
-          const float ls = S.ls[a], sg = S.sgm[a], mu = S.mu[s][a];
-          r_nlp = 0.5f * zz * zz + ls;
-          const float omu = S.omu[s][a], osg = S.osg[s][a];
-          r_kl = logf(osg / sg + 1e-5f) + (sg * sg + (omu - mu) * (omu - mu)) / (2.0f * (osg * osg + 1e-5f)) - 0.5f;
-          const float hi = fmaxf(mu - 1.1f, 0.0f), lo = fminf(mu + 1.1f, 0.0f);
-          r_bl = hi * hi + lo * lo;
-          r_ent = 0.5f + 0.5f * 1.8378770664093453f + ls;
-        }
+        if (a < A) r_nlp = 0.5f * zz * zz + S.ls[a];
       }
-      r_nlp = half_sum(r_nlp); r_kl = half_sum(r_kl); r_bl = half_sum(r_bl); r_ent = half_sum(r_ent);
+      r_nlp = half_sum(r_nlp);
       if (tid < MB * 32 && (tid % 32) == 31) {
         const int s = tid / 32;
         const float nlp = r_nlp + 0.5f * 1.8378770664093453f * (float)A;
@@ -1031,8 +1051,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
           } else { closs[j] = c1v; d = 2.0f * (v - R); }
           S.dv[j][s] = (j == 0 ? 0.5f * D.critic_coef : 1.0f) * d * invM;
         }
-        S.stat[s][1] = fmaxf(L1, L2); S.stat[s][2] = closs[0]; S.stat[s][3] = r_bl; S.stat[s][4] = r_kl;
-        S.stat[s][5] = closs[1]; S.stat[s][6] = r_ent;
+        S.stat[s][1] = fmaxf(L1, L2); S.stat[s][2] = closs[0]; S.stat[s][5] = closs[1];
       }
     }
     SDX_LDS_BARRIER();   // LDS traffic only: the column view's loads stay in flight (a __syncthreads() would wait for them)
@@ -1136,22 +1155,26 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     // waves: the x3 Gram's per-thread part only occupies threads 0..255, so the serial pieces - the statistics / LR rule, the products
     // dmu_a . dmu_b and the column sums of the head terms - run on waves 4..6 in front of the SAME block reduction instead of in two more
     // barrier-separated phases after it (3.1 -> about 2 us: this shadow was the longest overrun of its edge, section 4b of DESIGN.md).
-    if (tid == 384) {
-      PLds::Ctl& C = S.ctl;
-      float t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0, t6 = 0;
-      for (int s = 0; s < MB; ++s) { t1 += S.stat[s][1]; t2 += S.stat[s][2]; t3 += S.stat[s][3]; t4 += S.stat[s][4]; t5 += S.stat[s][5]; t6 += S.stat[s][6]; }
-      const float kl = t4 * invM;
-      C.sum_a += t1 * invM; C.sum_c += t2 * invM; C.sum_b += t3 * invM; C.sum_kl += kl; C.sum_cv += t5 * invM; C.sum_ent += t6 * invM;
-      C.last_kl = kl;
-      C.ac_lr_applied = C.ac_lr;   // the optimiser step of THIS minibatch uses the current lr; the schedule moves it afterwards
-      if (D.adaptive_lr) {         // legacy schedule: after every minibatch (PS:306-312)
-        // (the two thresholds are formed HERE from an opaque copy: hoisted out of the step loop they cost two registers for the whole launch,
-        // and with the first look at the norm words in flight one of them was spilled and reloaded - a scratch load and a vmcnt(0) - in this shadow)
-        float klt = D.kl_threshold;
-        SDX_OPAQUE(klt);
-        if (kl > 2.0f * klt) C.ac_lr = fmaxf(C.ac_lr / 1.5f, 1e-6f);
-        if (kl < 0.5f * klt) C.ac_lr = fminf(C.ac_lr * 1.5f, 1e-2f);
+    // The statistics-only terms of the loss phase (KL, bounds loss, entropy: a logf, two IEEE divisions and three half-wave sums per lane that
+    // no gradient uses) are formed HERE, on waves 5 and 7 as lane (sample, action) - S.mu / S.omu / S.osg / S.sgm / S.ls are those of the loss
+    // phase - in front of the reduction's first barrier; the statistics thread runs behind that barrier.
+    if (wave == 5 || wave == 7) {   // (wave 4 has the heads' 23-term products in front of the same barrier, wave 6 the statistics thread)
+      const int s = (wave - 5) + (lane >> 5), a = lane & 31;
+      float r_kl = 0.0f, r_bl = 0.0f, r_ent = 0.0f;
+      if (a < A) {
+        const float ls = S.ls[a], sg = S.sgm[a], mu = S.mu[s][a];
+        const float omu = S.omu[s][a], osg = S.osg[s][a];
+        r_kl = logf(osg / sg + 1e-5f) + (sg * sg + (omu - mu) * (omu - mu)) / (2.0f * (osg * osg + 1e-5f)) - 0.5f;
+        const float hi = fmaxf(mu - 1.1f, 0.0f), lo = fminf(mu + 1.1f, 0.0f);
+        r_bl = hi * hi + lo * lo;
+        r_ent = 0.5f + 0.5f * 1.8378770664093453f + ls;
       }
+      r_kl = half_sum(r_kl); r_bl = half_sum(r_bl); r_ent = half_sum(r_ent);
+      if (a == 31) { S.stat[s][3] = r_bl; S.stat[s][4] = r_kl; S.stat[s][6] = r_ent; }
+    }
+    if (tid == 384) {   // what does not wait for the KL stays in front of the barrier
+      PLds::Ctl& C = S.ctl;
+      C.ac_lr_applied = C.ac_lr;   // the optimiser step of THIS minibatch uses the current lr; the schedule moves it afterwards
       if constexpr (!SINGLE) {
         // Adam step counters / bias corrections of the optimiser step that applies THIS minibatch's gradient (phase A of the next
         // iteration): nothing here depends on the gradient, so it left the chain (round 6; the double-precision powers and the two
@@ -1163,6 +1186,25 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
         S.scal[4] = C.cv_lr / (float)(1.0 - C.cv_b1); S.scal[5] = 1.0f / sqrtf((float)(1.0 - C.cv_b2));
       }
     }
+    auto stats_and_lr = [&]() {
+    if (tid == 384) {
+      PLds::Ctl& C = S.ctl;
+      float t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0, t6 = 0;
+      for (int s = 0; s < MB; ++s) { t1 += S.stat[s][1]; t2 += S.stat[s][2]; t3 += S.stat[s][3]; t4 += S.stat[s][4]; t5 += S.stat[s][5]; t6 += S.stat[s][6]; }
+      const float kl = t4 * invM;
+      C.sum_a += t1 * invM; C.sum_c += t2 * invM; C.sum_b += t3 * invM; C.sum_kl += kl; C.sum_cv += t5 * invM; C.sum_ent += t6 * invM;
+      C.last_kl = kl;
+      if (D.adaptive_lr) {         // legacy schedule: after every minibatch (PS:306-312)
+        // (the two thresholds are formed HERE from an opaque copy: hoisted out of the step loop they cost two registers for the whole launch,
+        // and with the first look at the norm words in flight one of them was spilled and reloaded - a scratch load and a vmcnt(0) - in this shadow)
+        float klt = D.kl_threshold;
+        SDX_OPAQUE(klt);
+        if (kl > 2.0f * klt) C.ac_lr = fmaxf(C.ac_lr / 1.5f, 1e-6f);
+        if (kl < 0.5f * klt) C.ac_lr = fminf(C.ac_lr * 1.5f, 1e-2f);
+      }
+    }
+    };
+    if constexpr (SINGLE) { SDX_LDS_BARRIER(); stats_and_lr(); }   // (one minibatch: no reduction here whose barrier the statistics could share)
     if constexpr (!SINGLE) {
       // Round 6: the Gram of x3 (waves 0..3, unit = tid) and the Gram of dY2 (waves 4..7, unit = tid - 256; it used to wait for the dY0 shadow, whose
       // block reduction is on the chain since the norm edge shrank) go through ONE pass: columns 0..29 / 32..61, each summed over its 16 rows.
@@ -1197,7 +1239,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
         rows_store<8>(S, u, tid < U2 ? 0 : 32, wave, lane);
       }
       SDX_LDS_BARRIER();
-      if (tid < 64) {                                  // column tid: rows of waves 0..3 (x3) or 4..7 (dY2)
+      if (tid < 64) {                                 // column tid: rows of waves 0..3 (x3) or 4..7 (dY2)
         const int r0 = tid < 32 ? 0 : 2 * NWV;
         float t = 0.0f;
 #pragma unroll
@@ -1212,6 +1254,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       }
       // first look at this lane's dY1 words (the polling gather of phase E takes over if a producer is late)
       lq_peek<4>(LQ, LQ_DY1 + tid, NTH, pdy1); pdy1_issued = true;
+      stats_and_lr();                                  // thread 384, beside the column sums of threads 0..63 and behind its wave's first look; its readers sit behind the barrier below
       SDX_LDS_BARRIER();
     }
     TS(15)
@@ -1464,6 +1507,27 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
   }
 }
 
+// Test entry (tests/test_gpu_wave_sums.py): one workgroup of NTH threads, in / ref / got are [N][NTH].  ref[i][t] = wave_sum of value i in t's
+// wave, on every lane; got[i][t] = what wave_sums<N> left in lane t for value i - written by the lanes with (t & 3) == (i & 3), the others'
+// slots are not touched.
+template <int N>
+__global__ __launch_bounds__(NTH) void k_wave_sums_check(const float* in, float* ref, float* got) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  float v[N], u[(N + 3) / 4];
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = in[i * NTH + tid];
+#pragma unroll
+  for (int i = 0; i < N; ++i) ref[i * NTH + tid] = wave_sum(v[i]);
+  wave_sums<N>(v, u, lane);
+#pragma unroll
+  for (int j = 0; j < (N + 3) / 4; ++j) got[(4 * j + (lane & 3)) * NTH + tid] = u[j];
+}
+extern "C" int sdxpk_wave_sums_check(const float* in, float* ref, float* got, int n, hipStream_t st) {
+  if (n == 12) hipLaunchKernelGGL(k_wave_sums_check<12>, dim3(1), dim3(NTH), 0, st, in, ref, got);
+  else if (n == 16) hipLaunchKernelGGL(k_wave_sums_check<16>, dim3(1), dim3(NTH), 0, st, in, ref, got);
+  else return -1;
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 extern "C" size_t sdxpk_persist_lds_bytes() { return sizeof(PLds); }
 extern "C" int sdxpk_persist_supported(const SdxpDev* D, int minibatch, int n_cus) {
   return minibatch == MB && D->obs_dim <= OBS && D->obs_dim % 4 == 0 && D->state_dim == ST && D->units[0] == U0 && D->units[1] == U1 &&
