@@ -182,6 +182,8 @@ def load_library():
     lib.sdxtv_last_error.restype = C.c_char_p
     lib.sdxp_update.argtypes = [vp, vp]
     lib.sdxp_update_impl.argtypes = [vp]
+    lib.sdxpk_big_paths.argtypes = [vp]          # test hook outside include/seqdex.h (SdxPPO.gemm_paths)
+    lib.sdxpk_big_paths.restype = i32
     lib.sdxp_update_status.argtypes = [vp, vp]
     lib.sdxp_backward.argtypes = [vp, i32, i32, vp]
     lib.sdxp_apply.argtypes = [vp, i32, f32, vp]

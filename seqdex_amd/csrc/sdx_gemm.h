@@ -182,9 +182,10 @@ static __global__ __launch_bounds__(256) void k_reduce_parts3(ReduceBatch rb) {
   }
 }
 
-// 128 x 128 tiles (each wave 64 x 64: half the LDS and L2 traffic per flop) when they still give every CU a workgroup
+// 128 x 128 tiles (each wave 64 x 64: half the LDS and L2 traffic per flop) when they still give every CU a workgroup.
+// `tile` forces one shape (tests / timing: 1 = 64 x 64, 2 = 128 x 64, 3 = 128 x 128); 0: the automatic choice below
 template <int AT, int BT, int EPI>
-static void gemm(const GemmArgs* gs, int count, int splits, hipStream_t st, bool bf16 = false) {
+static void gemm(const GemmArgs* gs, int count, int splits, hipStream_t st, bool bf16 = false, int tile = 0) {
   GemmBatch gb;
   int Mx = 0, Nx = 0;
   for (int q = 0; q < 3; ++q) {
@@ -197,11 +198,12 @@ static void gemm(const GemmArgs* gs, int count, int splits, hipStream_t st, bool
   auto blocks = [&](int tm, int tn) { return (long)((Nx + tn - 1) / tn) * ((Mx + tm - 1) / tm) * splits * count; };
   auto waste = [&](long b) { const long rounds = (b + 255) / 256; return (double)(rounds * 256 - b) / (double)(rounds * 256); };
   const long b22 = blocks(128, 128), b21 = blocks(128, 64);
-  if (b22 >= 256 && waste(b22) <= 0.15) {
+  if (tile == 0) tile = (b22 >= 256 && waste(b22) <= 0.15) ? 3 : ((b21 >= 256 && waste(b21) <= 0.15) ? 2 : 1);
+  if (tile == 3) {
     dim3 grid((Nx + 127) / 128, (Mx + 127) / 128, splits * count);
     if (bf16) hipLaunchKernelGGL((k_gemm<AT, BT, EPI, 2, 2, 32, 1>), grid, dim3(256), 0, st, gb);
     else hipLaunchKernelGGL((k_gemm<AT, BT, EPI, 2, 2, 32>), grid, dim3(256), 0, st, gb);
-  } else if (b21 >= 256 && waste(b21) <= 0.15) {
+  } else if (tile == 2) {
     dim3 grid((Nx + 63) / 64, (Mx + 127) / 128, splits * count);
     if (bf16) hipLaunchKernelGGL((k_gemm<AT, BT, EPI, 2, 1, 32, 1>), grid, dim3(256), 0, st, gb);
     else hipLaunchKernelGGL((k_gemm<AT, BT, EPI, 2, 1, 32>), grid, dim3(256), 0, st, gb);

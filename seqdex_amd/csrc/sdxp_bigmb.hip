@@ -804,3 +804,21 @@ extern "C" int sdxpk_gemm_nt_launch(int bf, int epi, const NtArgs* gs, int count
   if (epi == EPI_TN) return (bf ? nt_prepare_and_launch<1, EPI_TN> : nt_prepare_and_launch<0, EPI_TN>)(gs, count, splits, tile, st) ? 0 : -1;
   return -1;
 }
+// ---- test hooks: one batched k_gemm_tt / k_gemm product on caller-owned operands (tests/test_gpu_gemm_products.py).  tile of
+// sdxpk_gemm_tt_launch as above; of sdxpk_gemm_launch as gemm<>() of sdx_gemm.h takes it.  Only the (AT, BT, EPI) products the step
+// and the T-value trainer instantiate exist: anything else is refused
+extern "C" int sdxpk_gemm_tt_launch(const NtArgs* gs, int count, int splits, const float* zeros, int tile, hipStream_t st) {
+  if (count < 1 || count > 3 || splits < 1 || !zeros || tile < 0 || tile > 2) return -1;
+  const bool ok = gemm_tt_prepare();
+  if (ok) gemm_tt(gs, count, splits, zeros, st, tile);
+  return hipGetLastError() == hipSuccess && ok ? 0 : -1;
+}
+extern "C" int sdxpk_gemm_launch(int at, int bt, int epi, int bf, const GemmArgs* gs, int count, int splits, int tile, hipStream_t st) {
+  if (count < 1 || count > 3 || splits < 1 || tile < 0 || tile > 3) return -1;
+  if (at == 0 && bt == 0 && epi == 1) gemm<0, 0, 1>(gs, count, splits, st, bf != 0, tile);
+  else if (at == 0 && bt == 0 && epi == 2) gemm<0, 0, 2>(gs, count, splits, st, bf != 0, tile);
+  else if (at == 0 && bt == 1 && epi == 3) gemm<0, 1, 3>(gs, count, splits, st, bf != 0, tile);
+  else if (at == 1 && bt == 1 && epi == 4) gemm<1, 1, 4>(gs, count, splits, st, bf != 0, tile);
+  else return -1;
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}

@@ -611,5 +611,12 @@ extern "C" int sdxp_set_state(sdxp_handle h, const sdxp_opt_state* in, void* str
   return SDX_OK;
 }
 extern "C" int sdxp_update_impl(sdxp_handle h) { return !h ? 0 : (h->big ? 2 : (h->use_persist ? 1 : 0)); }
+// test hook (not part of include/seqdex.h): what sdxpk_big_setup decided for this handle.  Bit 0 nt, bit 1 tt, bit 2 fused_heads,
+// bits 3-4 nt_tile (0 automatic, 1 = 128 x 64, 2 = 128 x 128), bit 5 bf16; -1: the handle is not on the large-minibatch path
+extern "C" int sdxpk_big_paths(sdxp_handle h) {
+  if (!h || !h->big) return -1;
+  const SdxpBigWs& w = h->bigws;
+  return (w.nt ? 1 : 0) | (w.tt ? 2 : 0) | (w.fused_heads ? 4 : 0) | ((w.nt_tile & 3) << 3) | (h->D.bf16 ? 32 : 0);
+}
 
 extern "C" const char* sdxp_last_error(sdxp_handle h) { return h ? h->err.c_str() : gp_create_err.c_str(); }

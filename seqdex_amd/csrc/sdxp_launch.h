@@ -7,6 +7,7 @@
 #include "sdx_kernels.h"
 #include "sdxp_types.h"
 struct NtArgs;   // sdx_gemm_nt.h
+struct GemmArgs; // sdx_gemm.h
 // device memory for a unit that sizes its own workspace: `bytes` zero-filled bytes owned by ctx (sdxp_create: the handle); SDX_OK or an error code
 typedef int (*SdxpAllocFn)(void* ctx, void** ptr, size_t bytes);
 extern "C" {
@@ -50,6 +51,8 @@ int sdxpk_big_setup(const SdxpDev* D, int MB, SdxpOpts* o, SdxpAllocFn alloc, vo
 void sdxpk_big_prenorm(const SdxpDev* D, const SdxpBigWs* ws, hipStream_t st);
 void sdxpk_big_step(const SdxpDev* D, const SdxpBigWs* ws, int mb, int me, hipStream_t st);
 int sdxpk_gemm_nt_launch(int bf, int epi, const NtArgs* gs, int count, int splits, int tile, hipStream_t st);
+int sdxpk_gemm_tt_launch(const NtArgs* gs, int count, int splits, const float* zeros, int tile, hipStream_t st);
+int sdxpk_gemm_launch(int at, int bt, int epi, int bf, const GemmArgs* gs, int count, int splits, int tile, hipStream_t st);
 // sdxp_exbench.hip
 int sdxpk_exchange_bench(void* ll, long long* out, int words, int rounds, int fmt, int src, int pattern, unsigned tag0, hipStream_t st);
 int sdxpk_pingpong_bench(void* ll, long long* out, int peer, int rounds, unsigned tag0, hipStream_t st);

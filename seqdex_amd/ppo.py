@@ -141,6 +141,14 @@ class SdxPPO:
         'gemm' (minibatch_size > 8: fp32-MFMA GEMM step with explicit gradients, sdxp_bigmb.hip)"""
         return {1: "persistent", 2: "gemm"}.get(self.lib.sdxp_update_impl(self.h), "graph")
 
+    def gemm_paths(self):
+        """what a 'gemm' handle settled on (sdxpk_big_paths): nt (trunk products on k_gemm_nt, else k_gemm), tt (fp32 weight gradients on
+        k_gemm_tt, else transposed copies), fused_heads, nt_tile (0 automatic, 1 = 128 x 64, 2 = 128 x 128), bf16; None on the other paths"""
+        bits = self.lib.sdxpk_big_paths(self.h)
+        if bits < 0:
+            return None
+        return dict(nt=bits & 1, tt=(bits >> 1) & 1, fused_heads=(bits >> 2) & 1, nt_tile=(bits >> 3) & 3, bf16=(bits >> 5) & 1)
+
     # ---- explicit-gradient path for world_size > 1 (gradients all-reduced by the caller between the two calls)
     def backward(self, which, mb):
         self._check(self.lib.sdxp_backward(self.h, which, mb, _stream_ptr(self.device)))

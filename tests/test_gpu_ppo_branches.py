@@ -1,5 +1,7 @@
 """-m gpu: the PPO update on every path (persistent kernel, hipGraph of the multi-kernel step, GEMM step with fused heads and with the
-13-launch head section) against oracle/ppo_oracle.py on data that takes every branch of the loss (tests/helpers/ppo_branch_data.py),
+13-launch head section, and the GEMM step on every trunk-product path: k_gemm by switch and by minibatch size, transposed copies instead of
+k_gemm_tt, the 128 x 128 tile, ragged minibatches; each handle says through gemm_paths() which it took) against oracle/ppo_oracle.py
+on data that takes every branch of the loss (tests/helpers/ppo_branch_data.py),
 at the defaults and with one configuration switch moved at a time; minibatch 2 and 8; the rollout's GAE, advantage normalisation and
 episode statistics at their edges.
 
@@ -23,11 +25,25 @@ from helpers import ppo_branch_data as BD  # noqa: E402
 from oracle.ppo_oracle import census_summary  # noqa: E402
 from test_gpu_ppo_parity import make_pair, rollout  # noqa: E402
 
-# path -> (envs, minibatch, variables around sdxp_create, update_impl()).  "persistent" sets nothing: the handle's own choice
-PATHS = {"persistent": (16, 4, None, "persistent"),
-         "graph": (16, 4, {"SDXP_UPDATE_IMPL": "graph"}, "graph"),
-         "gemm": (48, 48, None, "gemm"),
-         "gemm_13_launch_heads": (48, 48, {"SDXP_BIGMB_FUSED_HEADS": "0"}, "gemm")}
+# path -> (envs, minibatch, variables around sdxp_create, update_impl(), gemm_paths()).  "persistent" sets nothing: the handle's own choice.
+# update_impl() only says "gemm"; gemm_paths() shows that the handle honoured its switch: nt = 0 is k_gemm as the trunk (sdx_gemm.h),
+# tt = 0 the fp32 weight gradient from transposed copies (k_gemm_nt<0, EPI_TN>), nt_tile 2 the 128 x 128 tile of k_gemm_nt / k_gemm_tt.
+# 72 = 64 + 8 rows: ragged in both tile shapes.  A minibatch of 12 is no multiple of 8: the handle declines NT by itself
+NT = dict(nt=1, tt=1, fused_heads=1, nt_tile=0, bf16=0)
+PATHS = {"persistent": (16, 4, None, "persistent", None),
+         "graph": (16, 4, {"SDXP_UPDATE_IMPL": "graph"}, "graph", None),
+         "gemm": (48, 48, None, "gemm", NT),
+         "gemm_13_launch_heads": (48, 48, {"SDXP_BIGMB_FUSED_HEADS": "0"}, "gemm", dict(NT, fused_heads=0)),
+         "gemm_k_gemm_trunk": (48, 48, {"SDXP_BIGMB_NT": "0"}, "gemm", dict(NT, nt=0, tt=0)),
+         "gemm_k_gemm_by_size": (48, 12, None, "gemm", dict(NT, nt=0, tt=0)),
+         "gemm_nt_transposed_copies": (48, 48, {"SDXP_BIGMB_TT": "0"}, "gemm", dict(NT, tt=0)),
+         "gemm_wide_tile": (48, 48, {"SDXP_NT_TILE": "2"}, "gemm", dict(NT, nt_tile=2)),
+         "gemm_wide_tile_ragged": (72, 72, {"SDXP_NT_TILE": "2"}, "gemm", dict(NT, nt_tile=2)),
+         "gemm_ragged": (72, 72, None, "gemm", NT)}
+# the trunk-product paths run the two cases that reach the trunk differently (cv_normalize_input = 0 changes which staged input the central
+# value reads); the other switches live in the heads, which the first four paths cover in every case
+TRUNK_PATHS = [p for p in PATHS if p not in ("persistent", "graph", "gemm", "gemm_13_launch_heads")]
+TRUNK_CASES = ["defaults", "cv_normalize_input_0"]
 CASES = {"defaults": {}, "clip_value_0": dict(clip_value=0), "truncate_grads_0": dict(truncate_grads=0),
          "normalize_advantage_0": dict(normalize_advantage=0), "cv_normalize_input_0": dict(cv_normalize_input=0),
          "entropy_coef_0.02": dict(entropy_coef=0.02), "bounds_loss_coef_0.05": dict(bounds_loss_coef=0.05)}
@@ -44,7 +60,7 @@ def reference(n, minibatch, case):
 
 
 def run_case(path, case, n=None, minibatch=None, expect_impl="path"):
-    pn, pmb, env, impl = PATHS[path]
+    pn, pmb, env, impl, gemm_paths = PATHS[path]
     n, mb = n or pn, minibatch or pmb
     ref = reference(n, mb, case)
     over, st, orc, summary = ref["over"], ref["st"], ref["orc"], ref["summary"]
@@ -59,6 +75,8 @@ def run_case(path, case, n=None, minibatch=None, expect_impl="path"):
     try:
         if expect_impl is not None:
             assert agent.update_impl() == expect_impl, agent.update_impl()
+        if expect_impl == impl:
+            assert agent.gemm_paths() == gemm_paths, agent.gemm_paths()
         T = agent.t
         T["AC_PARAMS"].copy_(ref["orc0"].ac_flat().cuda())
         T["CV_PARAMS"].copy_(ref["orc0"].cv_flat().cuda())
@@ -107,10 +125,9 @@ def run_case(path, case, n=None, minibatch=None, expect_impl="path"):
         agent.close()
 
 
-@pytest.mark.parametrize("path", list(PATHS))
-@pytest.mark.parametrize("case", list(CASES))
+@pytest.mark.parametrize("case,path", [(c, p) for p in PATHS for c in (TRUNK_CASES if p in TRUNK_PATHS else CASES)])
 def test_update_on_branch_rich_data(case, path):
-    """one update phase (one mini-epoch: 32 minibatches of 4, or 8 of 48) against torch.autograd + Adam, one switch moved at a time.
+    """one update phase (one mini-epoch: 32 minibatches of 4 or of 12, 8 of 48 or of 72) against torch.autograd + Adam, one switch moved at a time.
     entropy_coef != 0 under "persistent": the handle must decline the persistent kernel (which has no entropy term) and say "graph".
     (While k_head and the persistent kernel dropped the term, this case gave on both small-minibatch paths sum_entropy / steps 32.6356
     against 32.7070 and max |d ac| 9.7e-3 against the bound 2e-4.)"""

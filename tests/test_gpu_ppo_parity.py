@@ -127,10 +127,9 @@ def test_update_matches_autograd_adam(adaptive):
         agent.close()
 
 
-def _large_minibatch_update_against_oracle(mbsize, critic_coef, env=None):
-    """one update phase of a large-minibatch agent checked against the oracle; `env`: variables set around sdxp_create only.  Returns the
-    parameters after the update."""
-    n = 48
+def _large_minibatch_update_against_oracle(mbsize, critic_coef, env=None, n=48, paths=None):
+    """one update phase of a large-minibatch agent of `n` envs checked against the oracle; `env`: variables set around sdxp_create only;
+    `paths`: what gemm_paths() must say of the handle.  Returns the parameters after the update."""
     old = {k: os.environ.get(k) for k in (env or {})}
     os.environ.update(env or {})
     try:
@@ -143,6 +142,9 @@ def _large_minibatch_update_against_oracle(mbsize, critic_coef, env=None):
                 os.environ[k] = v
     try:
         assert agent.update_impl() == "gemm"
+        if paths is not None:
+            got = agent.gemm_paths()
+            assert {k: got[k] for k in paths} == paths, got
         g = torch.Generator().manual_seed(7)
         ds = rollout(agent, orc, n, g)
         agent.update()
@@ -180,6 +182,15 @@ def test_large_minibatch_update_matches_autograd_adam(mbsize, critic_coef):
     _large_minibatch_update_against_oracle(mbsize, critic_coef)
 
 
+@pytest.mark.parametrize("env,paths", [(None, dict(nt=1, tt=1, nt_tile=0)), ({"SDXP_NT_TILE": "2"}, dict(nt=1, tt=1, nt_tile=2)),
+                                       ({"SDXP_BIGMB_NT": "0"}, dict(nt=0, tt=0))], ids=["nt", "nt_wide_tile", "k_gemm"])
+def test_large_minibatch_136_rows_match_autograd_adam(env, paths):
+    """51 envs x 8 steps = 3 minibatches of 136 = 128 + 8 rows, 15 optimiser steps: the second row of 128-row tiles holds eight rows, in
+    both tile shapes of k_gemm_nt / k_gemm_tt and in k_gemm as the trunk.  (tests/helpers/ppo_branch_data.py has no branch-rich data at
+    this size, so the shape is held here, on the common rollout.)  Bounds: those of test_large_minibatch_update_matches_autograd_adam."""
+    _large_minibatch_update_against_oracle(136, 1.0, env=env, n=51, paths=paths)
+
+
 def test_large_minibatch_switches_are_per_handle():
     """the SDXP_* switches are read by sdxp_create into the handle: within one process a second agent created under
     SDXP_BIGMB_FUSED_HEADS=0 takes the 13-launch head section although the first one has already run the fused head kernel.  Both meet the
@@ -190,15 +201,28 @@ def test_large_minibatch_switches_are_per_handle():
     assert not (np.array_equal(ac0, ac1) and np.array_equal(cv0, cv1))
 
 
-@pytest.mark.parametrize("mbsize", [64, 96, 384])
-def test_large_minibatch_bf16_gradients_against_fp32_path(mbsize):
+BF16_NT = dict(nt=1, tt=0, nt_tile=0, bf16=1)
+
+
+@pytest.mark.parametrize("mbsize,env,paths", [(64, None, BF16_NT), (96, None, BF16_NT), (384, None, BF16_NT),
+                                              (64, {"SDXP_NT_TILE": "2"}, dict(BF16_NT, nt_tile=2)),
+                                              (64, {"SDXP_BIGMB_NT": "0"}, dict(BF16_NT, nt=0)), (12, None, dict(BF16_NT, nt=0))],
+                         ids=["64", "96", "384", "64-wide_tile", "64-k_gemm", "12-k_gemm_by_size"])
+def test_large_minibatch_bf16_gradients_against_fp32_path(mbsize, env, paths):
     """one minibatch, same parameters and data: flat gradients of the bf16-MFMA step against the fp32-MFMA step of the same library
     (which the autograd oracle holds to 2e-4).  bf16 keeps 8 mantissa bits: the gradient of every network agrees to a few 1e-3 in
-    norm, layer by layer."""
+    norm, layer by layer.  `env` is set around the creation of the bf16 handle only: the 128 x 128 tile of k_gemm_nt (v_dot2c row sums
+    in both of its row blocks) and k_gemm with BF = 1, by switch and by a minibatch that is no multiple of 8.  The fp32 partner stays on
+    its default path (k_gemm for 12 rows), which the oracle holds."""
+    from helpers.ppo_branch_data import env_around_create
     n = 48
-    a, orc = make_pair(n, minibatch=mbsize, cv_minibatch=mbsize, adaptive_lr=0, mixed_precision=1)
+    with env_around_create(env):
+        a, orc = make_pair(n, minibatch=mbsize, cv_minibatch=mbsize, adaptive_lr=0, mixed_precision=1)
     b, _ = make_pair(n, minibatch=mbsize, cv_minibatch=mbsize, adaptive_lr=0)
     try:
+        got = a.gemm_paths()
+        assert {k: got[k] for k in paths} == paths, got
+        assert b.gemm_paths()["bf16"] == 0
         for ag in (a, b):
             rollout(ag, orc, n, torch.Generator().manual_seed(7))
             ag.backward(0, -1)

@@ -189,7 +189,7 @@ def test_census_counts_hand_made_rows():
 
 
 @pytest.mark.parametrize("n,minibatch,case", [(16, 4, "defaults"), (16, 2, "defaults"), (16, 8, "defaults"), (48, 48, "defaults"),
-                                               (16, 4, "clip_value_0"), (48, 48, "clip_value_0")])
+                                               (16, 4, "clip_value_0"), (48, 48, "clip_value_0"), (48, 12, "defaults"), (72, 72, "defaults")])
 def test_branch_rich_data_census_on_the_oracle_alone(n, minibatch, case):
     """the data of tests/test_gpu_ppo_branches.py (tests/helpers/ppo_branch_data.py) is decided on the CPU: its census has every class of
     decision often enough and none close to its boundary.  (The GPU tests assert the same for every case before they compare.)"""
