@@ -275,8 +275,8 @@ __device__ __forceinline__ void row_butterfly(const float (&v)[N], float (&u2)[(
 template <int N>
 __device__ __forceinline__ void wave_sums(const float (&v)[N], float (&u)[(N + 3) / 4], int lane) {
   // (opaque copies: the sums are those of the ROUNDED values - a value that is a bare product must not be contracted with the butterfly's first
-  // add into an fma, through the level's select.  wave_sum of a bare product IS contracted that way, per lane, which no butterfly reproduces:
-  // forward L2 therefore keeps its twelve trees.)
+  // add into an fma, through the level's select.  wave_sum of a bare product IS contracted that way, per lane: forward L2, whose values are
+  // bare products, has a butterfly of its own - fwd2_sums below.)
   float t[N];
 #pragma unroll
   for (int i = 0; i < N; ++i) { t[i] = v[i]; asm("" : "+v"(t[i])); }
@@ -288,12 +288,56 @@ __device__ __forceinline__ void wave_sums(const float (&v)[N], float (&u)[(N + 3
     u[j] = pair_sum(__builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]));
   }
 }
+// Forward L2: the wave sums of the twelve BARE products w[net] x[net][s], with the bits of twelve wave_sum trees.  wave_sum(w x) compiles to
+// v_mul (the rounded product) / v_mov_dpp quad_perm:[1,0,3,2] / v_fmac: lane l holds fma(w_l, x_l, rounded product of lane l ^ 1), so the two
+// lanes of a pair hold different bits, and of a DPP row only the lanes whose view the rest of the tree carries to lane 63 count - 15, 13, 8,
+// 10, 0, 2, 7, 5: row sum = ((v15 + v13) + (v8 + v10)) + ((v0 + v2) + (v7 + v5)), wave sum = (r3 + r2) + (r1 + r0).  Here the first level is
+// written out - on every lane, twelve independent fmas, the product through an opaque copy so that it stays rounded - and the other levels run
+// as a halving butterfly over exactly those pairs: partner l ^ 2 (the lanes with bit 0 == bit 1 keep samples 0 and 3, the others 1 and 2),
+// row_half_mirror (bit 2 == bit 3 keeps the first of the two), row_mirror, then the rows as in wave_sums.  Addition commutes, pairing does
+// not.  Lanes 0, 2, 5, 7 (and their mirrors 15, 13, 10, 8) of every row end with u[net] = the wave's sum of sample 0, 1, 2, 3: lanes 1 and 3
+// are not on the tree's path, so the storing lanes are not 0..3 (fwd2_sample, fwd2_store).
+__device__ __forceinline__ int fwd2_sample(int lane) {
+  const bool ka = (((lane >> 1) ^ lane) & 1) == 0, kf = (((lane >> 3) ^ (lane >> 2)) & 1) == 0;
+  return kf ? (ka ? 0 : 1) : (ka ? 3 : 2);
+}
+__device__ __forceinline__ void fwd2_sums(const float (&w)[3], const float (&x)[3][4], float (&u)[3], int lane) {
+  const bool ka = (((lane >> 1) ^ lane) & 1) == 0, kf = (((lane >> 3) ^ (lane >> 2)) & 1) == 0;
+  float v[3][4];
+#pragma unroll
+  for (int net = 0; net < 3; ++net)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      float t = w[net] * x[net][s];
+      asm("" : "+v"(t));
+      v[net][s] = __builtin_fmaf(w[net], x[net][s], dpp_mov<0xB1, 0xF>(0.0f, t));   // partner lane ^ 1
+    }
+#pragma unroll
+  for (int net = 0; net < 3; ++net) {
+    const float k0 = ka ? v[net][0] : v[net][1], s0 = ka ? v[net][1] : v[net][0];
+    const float k1 = ka ? v[net][3] : v[net][2], s1 = ka ? v[net][2] : v[net][3];
+    const float a = k0 + dpp_mov<0x4E, 0xF>(0.0f, s0), b = k1 + dpp_mov<0x4E, 0xF>(0.0f, s1);   // partner lane ^ 2
+    float t = (kf ? a : b) + dpp_mov<0x141, 0xF>(0.0f, kf ? b : a);                              // row_half_mirror: lane ^ 7
+    t += dpp_mov<0x140, 0xF>(0.0f, t);                                                           // row_mirror: lane ^ 15
+    const unsigned y = __builtin_bit_cast(unsigned, t);
+    const auto r = __builtin_amdgcn_permlane16_swap(y, y, false, false);
+    u[net] = pair_sum(__builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]));
+  }
+}
 // the forward passes' partial dot products, value net MB + s: lane s < MB holds u[net] = this wave's sum of (net, sample s)
 static_assert(MB == 4, "lane & 3 of wave_sums is the sample");
 __device__ __forceinline__ void fpart_store(PLds& S, const float (&u)[3], int wave, int lane) {
   if (lane < MB) {
 #pragma unroll
     for (int net = 0; net < 3; ++net) S.fpart[(net * MB + lane) * NWV + wave] = u[net];
+  }
+}
+// the same slots from fwd2_sums: lanes 0, 2, 5, 7 hold samples 0, 1, 2, 3
+__device__ __forceinline__ void fwd2_store(PLds& S, const float (&u)[3], int wave, int lane) {
+  if (lane < 8 && ((0xA5 >> lane) & 1)) {
+    const int s = fwd2_sample(lane);
+#pragma unroll
+    for (int net = 0; net < 3; ++net) S.fpart[(net * MB + s) * NWV + wave] = u[net];
   }
 }
 template <int N4>
@@ -794,33 +838,23 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       // forward L2 are formed from the gathered registers; the S.x2 image (Gram of x2, backward L2's elu', the next step's Adam of layer 2)
       // is stored behind them, under the DPP sums.
       static_assert(NTH == U1 && MB == 4, "word tid + NTH j of the x2 edge is (sample j, unit tid)");
-      float q[3][MB];
+      float x[3][MB], u[3];
       {
         float v0[4], v1[4], v2[4];
         if (!(px2_issued && lq_take<4>(px2, tag, v0, v1, v2)) && !lq_gather<4>(LQ, LQ_X2 + tid, NTH, tag, v0, v1, v2, failflag)) S.fail = 1;
         TS(7)
 #pragma unroll
-        for (int s = 0; s < MB; ++s) { q[0][s] = w2[0] * v0[s]; q[1][s] = w2[1] * v1[s]; q[2][s] = w2[2] * v2[s]; }
+        for (int s = 0; s < MB; ++s) { x[0][s] = v0[s]; x[1][s] = v1[s]; x[2][s] = v2[s]; }
 #pragma unroll
         for (int j = 0; j < 4; ++j) { (&S.x2[0][0][0])[tid + NTH * j] = v0[j]; (&S.x2[1][0][0])[tid + NTH * j] = v1[j]; (&S.x2[2][0][0])[tid + NTH * j] = v2[j]; }
       }
       // (no barrier here: the one that stood between the S.x2 stores and their read-back also kept the S.fpart stores below behind forward L1's
       // readers of S.fpart - the barrier in front of phase C does that - and the S.x2 stores in front of their readers, which all sit behind
       // the barrier that follows the S.fpart stores)
-      // (twelve wave_sum trees, NOT the one butterfly of the other forward phases: a value here is a bare product, and the compiler contracts
-      // it with the tree's first add - lane l adds its EXACT w2 x2 to the rounded product of lane l ^ 1, one fma - so the two lanes of a pair hold
-      // different bits and the tree's result is the one that reaches lane 63.  A butterfly whose lane pairs each keep half of the values cannot
-      // form those bits: it was tried, x3 moved in its last place.  Same code as before, same bits.)
-#pragma unroll
-      for (int net = 0; net < 3; ++net)
-#pragma unroll
-        for (int s = 0; s < MB; ++s) q[net][s] = wave_sum(q[net][s]);
-      if (lane == 0) {
-#pragma unroll
-        for (int net = 0; net < 3; ++net)
-#pragma unroll
-          for (int s = 0; s < MB; ++s) S.fpart[(net * MB + s) * NWV + wave] = q[net][s];
-      }
+      // (the twelve sums of bare products as one butterfly behind an explicit fma level: the bits of the twelve wave_sum trees that stood here,
+      // whose first add the compiler contracted with the product per lane - fwd2_sums above)
+      fwd2_sums(w2, x, u, lane);
+      fwd2_store(S, u, wave, lane);
     }
     __syncthreads();
     if (tid < MB) {
@@ -1128,25 +1162,30 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
         row_butterfly<12>(p, u2, lane);
         rows_store<3>(S, u2, 0, wave, lane);
       }
+      // dY1 leaves from the reducing lanes, in front of the closing barrier: lane (net MB + s) 2 + c < 24 of wave 0 applies elu' to its own sum
+      // and stores dyown; lanes l + 8 (the same DPP row) and l + 16 (the next row: v_permlane16_swap) hand networks 1 and 2 of (s, c) to lane
+      // l < 8, which publishes the word.  (S.part is not written: the read-back it served is gone.)
+      const int bi = tid >> 1, bc = tid & 1, bnet = min(tid >> 3, 2), bs = bi & 3;
+      const float eg = tid < 24 ? elu_g(S.x2[bnet][bs][2 * g + bc]) : 0.0f;   // (requested in front of the barrier: it does not wait for the sums)
       SDX_LDS_BARRIER();
-      if (tid < 24) {   // (net MB + s, c)
-        const int i = tid >> 1, c = tid & 1;
-        float t = 0.0f;
+      if (wave == 0) {
+        float v = 0.0f;
+        if (tid < 24) {   // (net MB + s, c)
+          float t = 0.0f;
 #pragma unroll
-        for (int w = 0; w < NWV; ++w) { t += S.red[4 * w + 2 * c][i]; t += S.red[4 * w + 2 * c + 1][i]; }   // rows 16 j .. 16 j + 15 of the column, j ascending
-        S.part[tid] = t;
-      }
-      SDX_LDS_BARRIER();
-      if (tid < MB * 2) {   // S.part: [(net MB + s) 2 + c]
-        const int s = tid / 2, c = tid % 2;
-        float v[3];
-#pragma unroll
-        for (int net = 0; net < 3; ++net) {
-          v[net] = S.part[(net * MB + s) * 2 + c] * elu_g(S.x2[net][s][2 * g + c]);
-          S.dyown[net][s][4 + c] = v[net];
+          for (int w = 0; w < NWV; ++w) { t += S.red[4 * w + 2 * bc][bi]; t += S.red[4 * w + 2 * bc + 1][bi]; }   // rows 16 j .. 16 j + 15 of the column, j ascending
+          v = t * eg;
+          S.dyown[bnet][bs][4 + bc] = v;
         }
-        lq_store(LQ, LQ_DY1 + (unsigned)s * U1 + 2 * g + c, v[0], v[1], v[2], tag);
+        const float v1 = dpp_mov<0x108, 0xF>(0.0f, v);                                        // row_shl:8: lane l + 8
+        const unsigned y = __builtin_bit_cast(unsigned, v);
+        const auto r = __builtin_amdgcn_permlane16_swap(y, y, false, false);                  // r[1]: rows 1, 1, 3, 3 - lane l + 16 for l < 16
+        const float v2 = __builtin_bit_cast(float, (unsigned)r[1]);
+        if (tid < MB * 2) lq_store(LQ, LQ_DY1 + (unsigned)(tid >> 1) * U1 + 2 * g + (tid & 1), v, v1, v2, tag);
       }
+      // (the reduction's closing barrier - S.red read out before its next writer, S.dyown[.][.][4..5] published - stands in the dY1 shadow, in front
+      // of that shadow's rows_store: the other waves form their parts of the shadow while wave 0 adds and publishes.  One minibatch: the barrier in
+      // front of its statistics thread.)
     }
     TS(14)
     u32x4 pdy1[4];
@@ -1236,6 +1275,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       {
         float u[8];
         row_butterfly<30>(p, u, lane);
+        SDX_LDS_BARRIER();   // backward L2's closing barrier: wave 0 has read S.red out
         rows_store<8>(S, u, tid < U2 ? 0 : 32, wave, lane);
       }
       SDX_LDS_BARRIER();
@@ -1281,20 +1321,38 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       // S.red / S.part behind the dY1 shadow's readers of both - the LDS barrier that closes that shadow does that - and the S.dy1 stores in
       // front of the Gram of dY1, which sits behind block_sum's barriers.  The one-minibatch instantiation has no such shadow: it keeps it.)
       if constexpr (SINGLE) __syncthreads();
-      block_sum<48>(S, p, S.part, tid, wave, lane);
-      if (tid < MB * 4) {   // S.part: [(net MB + s) 4 + c]
-        const int s = tid / 4, c = tid % 4;
-        float v[3];
+      // block_sum<48>, opened up: the 48 reducing lanes (net MB + s) 4 + c = 16 net + 4 s + c of wave 0 - network net is DPP row net - apply
+      // elu' to their own 32-term sum and store dyown; what leaves the CU (the norm word; in the one-minibatch instantiation the dY0 words,
+      // rows 1 and 2 reaching row 0 through v_permlane16_swap / v_permlane32_swap) goes out in FRONT of the reduction's second barrier, which
+      // the shadow's rows_store still needs.  (S.part is not written: the read-back it served is gone.)
+      {
+        float u2[12];
+        row_butterfly<48>(p, u2, lane);
+        rows_store<12>(S, u2, 0, wave, lane);
+      }
+      const int es = (tid >> 2) & 3, ec = tid & 3, enet = min(tid >> 4, 2);
+      const float eg = tid < 48 ? elu_g(S.x1[enet][es][4 * g + ec]) : 0.0f;   // (requested in front of the barrier: it does not wait for the sums)
+      SDX_LDS_BARRIER();
+      if (wave == 0) {
+        float v = 0.0f;
+        if (tid < 48) {
+          float t = 0.0f;
 #pragma unroll
-        for (int net = 0; net < 3; ++net) {
-          v[net] = S.part[(net * MB + s) * 4 + c] * elu_g(S.x1[net][s][4 * g + c]);
-          S.dyown[net][s][c] = v[net];
+          for (int w = 0; w < 4 * NWV; ++w) t += S.red[w][tid];
+          v = t * eg;
+          S.dyown[enet][es][ec] = v;
         }
-        if constexpr (SINGLE) lq_store(LQ, LQ_DY0 + (unsigned)s * U0 + 4 * g + c, v[0], v[1], v[2], tag);
+        if constexpr (SINGLE) {
+          const unsigned y = __builtin_bit_cast(unsigned, v);
+          const auto r16 = __builtin_amdgcn_permlane16_swap(y, y, false, false);   // r16[1]: rows 1, 1, 3, 3 - lane l + 16 for l < 16
+          const auto r32 = __builtin_amdgcn_permlane32_swap(y, y, false, false);   // r32[1]: the upper half in both halves - lane l + 32 for l < 32
+          if (tid < MB * 4)
+            lq_store(LQ, LQ_DY0 + (unsigned)es * U0 + 4 * g + ec, v, __builtin_bit_cast(float, (unsigned)r16[1]), __builtin_bit_cast(float, (unsigned)r32[1]), tag);
+        }
       }
       if constexpr (!SINGLE) {
         // the other CUs need dY0 only for the gradient norm: publish this CU's share of the Gram dY0 dY0^T (its four columns).
-        // Lanes 0..15 of wave 0 wrote dyown above; the same wave reads it back (LDS keeps program order within a wave)
+        // Lanes 0..47 of wave 0 wrote dyown above; the same wave reads it back (LDS keeps program order within a wave)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1320,6 +1378,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
           }
           if (lane == 0) lq_store(LQ, LQ_G0 + g, t[0], t[1], t[2], tag);
         }
+        // (the reduction's second barrier stands in the dY0 shadow, in front of its rows_store: the other waves form their Gram terms meanwhile)
       }
     }
     TS(17)
@@ -1376,6 +1435,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
 #pragma unroll
         for (int net = 0; net < 3; ++net) gram_acc10(&p[net * 10], S.dy1[net][0][tid], S.dy1[net][1][tid], S.dy1[net][2][tid], S.dy1[net][3][tid]);
         row_butterfly<30>(p, ua, lane);
+        SDX_LDS_BARRIER();   // backward L1's second barrier: wave 0 has read S.red out and published, S.dyown[.][.][0..3] is there for what follows
         rows_store<8>(S, ua, 0, wave, lane);
       }
       SDX_LDS_BARRIER();          // (rows_reduce, opened up: the stage between its two barriers occupies 32 threads ...)
@@ -1526,6 +1586,40 @@ extern "C" int sdxpk_wave_sums_check(const float* in, float* ref, float* got, in
   if (n == 12) hipLaunchKernelGGL(k_wave_sums_check<12>, dim3(1), dim3(NTH), 0, st, in, ref, got);
   else if (n == 16) hipLaunchKernelGGL(k_wave_sums_check<16>, dim3(1), dim3(NTH), 0, st, in, ref, got);
   else return -1;
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// Test entry (tests/test_gpu_fwd2_sums.py): one workgroup of NTH threads, w is [3][NTH], x [3][MB][NTH], ref / got [3 MB][NTH], value
+// net MB + s.  ref[i][t] = the tree forward L2 used to run for value i in t's wave, written serially: the explicit fma first level, the
+// five dpp_add levels of wave_sum, lane 63.  got[i][t] = what fwd2_sums left in lane t for value i - written by the 32 lanes of a wave that hold
+// sample i % MB (fwd2_sample, the eight useful lanes of every DPP row), the others' slots are not touched.
+__global__ __launch_bounds__(NTH) void k_fwd2_sums_check(const float* w, const float* x, float* ref, float* got) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  float wv[3], xv[3][MB], u[3];
+#pragma unroll
+  for (int net = 0; net < 3; ++net) {
+    wv[net] = w[net * NTH + tid];
+#pragma unroll
+    for (int s = 0; s < MB; ++s) xv[net][s] = x[(net * MB + s) * NTH + tid];
+  }
+#pragma unroll
+  for (int net = 0; net < 3; ++net)
+#pragma unroll
+    for (int s = 0; s < MB; ++s) {
+      float t = wv[net] * xv[net][s];
+      asm volatile("" : "+v"(t));
+      float v = __builtin_fmaf(wv[net], xv[net][s], dpp_mov<0xB1, 0xF>(0.0f, t));
+      v = dpp_add<0x4E, 0xF>(v); v = dpp_add<0x141, 0xF>(v); v = dpp_add<0x140, 0xF>(v); v = dpp_add<0x142, 0xA>(v); v = dpp_add<0x143, 0xC>(v);
+      ref[(net * MB + s) * NTH + tid] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+    }
+  fwd2_sums(wv, xv, u, lane);
+  if ((0xA5A5 >> (lane & 15)) & 1) {
+    const int s = fwd2_sample(lane);
+#pragma unroll
+    for (int net = 0; net < 3; ++net) got[(net * MB + s) * NTH + tid] = u[net];
+  }
+}
+extern "C" int sdxpk_fwd2_sums_check(const float* w, const float* x, float* ref, float* got, hipStream_t st) {
+  hipLaunchKernelGGL(k_fwd2_sums_check, dim3(1), dim3(NTH), 0, st, w, x, ref, got);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 extern "C" size_t sdxpk_persist_lds_bytes() { return sizeof(PLds); }
