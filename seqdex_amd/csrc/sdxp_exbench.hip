@@ -24,10 +24,9 @@
 
 #include "sdx_common.h"
 #include "sdxp_launch.h"
+#include "sdxp_persist_exchange.h"   // u64, u32x4, load16 / store16: the words and the 16-byte access of the update kernel
 
 namespace {
-typedef unsigned long long u64;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr int XNWG = 256, XNTH = 512;
 
 __device__ __forceinline__ float payload(unsigned tag, unsigned idx) {   // what word `idx` of round `tag` must carry
@@ -42,14 +41,11 @@ struct ExArgs {
 };
 
 // Batches of B words per thread, all requested before the first tag is looked at, re-requested as a whole (wave-uniform retry) until
-// every lane of the wave has its B tags: the shape of ll_gather<12> in sdxp_persist.hip.  Elements a thread is not interested in
-// (idx < 0) are not loaded.
+// every lane of the wave has its B tags: the shape of lq_gather<N> / ll_gather<N> in sdxp_persist_exchange.h, with bare tags (the payload
+// check is this benchmark's point).  Elements a thread is not interested in (idx < 0) are not loaded.
 constexpr int XB = 6;
-// one buffer_load / buffer_store_dwordx4 ... sc1 per lane (device scope, as the 8-byte agent-scope atomics lower to): the compiler
-// counts these in its s_waitcnt bookkeeping, unlike inline asm
+// (a resource of its own: the benchmark's buffer is sized by its caller, not by SDXP_LL_WORDS as lq_rsrc's)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(void* base) { return __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x00020000); }
-__device__ __forceinline__ u32x4 load16(__amdgpu_buffer_rsrc_t r, unsigned q) { return __builtin_amdgcn_raw_buffer_load_b128(r, q * 16u, 0, 16); }
-__device__ __forceinline__ void store16(__amdgpu_buffer_rsrc_t r, unsigned q, u32x4 v) { __builtin_amdgcn_raw_buffer_store_b128(v, r, q * 16u, 0, 16); }
 }  // namespace
 
 __global__ __launch_bounds__(XNTH, 2) void k_exchange_bench(ExArgs a) {

@@ -44,6 +44,7 @@ int sdxpk_persist_supported(const SdxpDev* D, int minibatch, int n_cus);
 int sdxpk_persist_prepare(int dev);
 int sdxpk_update_persistent(const SdxpDev* D, int total_steps, unsigned* failflag, int stamps, int fault, hipStream_t st);
 int sdxpk_fwd_bwd_persistent(const SdxpDev* D, unsigned* failflag, hipStream_t st);
+// sdxp_persist_checks.hip
 int sdxpk_wave_sums_check(const float* in, float* ref, float* got, int n, hipStream_t st);   // test entry: wave_sums<n> beside n wave_sum trees, n = 12 or 16
 int sdxpk_fwd2_sums_check(const float* w, const float* x, float* ref, float* got, hipStream_t st);   // test entry: fwd2_sums beside the twelve trees it replaces
 // sdxp_bigmb.hip.  sdxpk_big_setup lowers the large-minibatch options of `o` to what shapes and device allow, sets the LDS attributes of

@@ -26,350 +26,10 @@
 #include "sdx_common.h"
 #include "sdxp_device.h"   // elu, dpp_add, wave_sum
 #include "sdxp_launch.h"
-
-namespace {
-// OBS is the LARGEST actor/critic input width (GraspSim, 396); narrower inputs (Orient: 188) run with the tail columns masked off
-constexpr int MB = 4, OBS = 396, ST = 564, U0 = 1024, U1 = 512, U2 = 256, ACT = 23;
-constexpr int NWG = 256, NTH = 512, NWV = NTH / 64;
-constexpr int H0A = OBS / 2, H0V = ST / 2;   // a layer-0 row is split over two waves: 198 / 282 elements each
-constexpr int I0A = (H0A + 63) / 64;   // 4 elements per lane of half an actor/critic layer-0 row
-constexpr int I0V = (H0V + 63) / 64;   // 5 for half a central-value layer-0 row
-constexpr int HR = 4;                  // head rows per wave (25 rows over 8 waves)
-constexpr int HPC = (ACT + 2) * U2 / NWG;   // head weights whose Adam state one CU owns (25)
-static_assert(HPC * NWG == (ACT + 2) * U2 && U2 == 256, "head ownership split");
-
-__device__ __forceinline__ float elu_g(float h) { return h > 0.0f ? 1.0f : h + 1.0f; }
-// v + (the value of lane ^ 32), in both lanes: v_permlane32_swap_b32 of v with itself leaves the lower half's values in one result and the
-// upper half's in the other
-__device__ __forceinline__ float pair_sum(float v) {
-  const unsigned u = __builtin_bit_cast(unsigned, v);
-  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
-}
-// Opaque copy of an index.  volatile asm statements keep their program order relative to each other and to sched_barrier,
-// and an LDS load whose address depends on the result cannot be floated above it: this is what keeps the operand loads of
-// Adam element i+1 below the arithmetic of element i.
-// Passing the weight updated by element i as a (fake) input orders element i+1's loads after element i's arithmetic too.
-__device__ __forceinline__ int opaque(int x, float after) { asm volatile("" : "+v"(x) : "v"(after)); return x; }
-__device__ __forceinline__ void adam1(float& w, float g, float& m, float& v, float lr_bc1, float isq_bc2) {
-  m = 0.9f * m + 0.1f * g;
-  v = 0.999f * v + 0.001f * g * g;
-  // v_sqrt_f32 / v_rcp_f32 (1 ulp each) instead of the IEEE sequences: the Adam arithmetic of ~45 elements per lane is VALU bound
-  w -= lr_bc1 * m * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(v) * isq_bc2 + 1e-8f);
-  // one element at a time: without this the scheduler forms all ~45 gradients of the lane first and holds them (and the
-  // half-updated moments) in registers while it interleaves the long sqrt/div chains
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-struct PLds {
-  float obs[MB][OBS];        // layer-0 input of actor/critic (dataset rows)
-  float cvx[MB][ST];         // layer-0 input of the central value (pre-normalised rows)
-  float x1[3][MB][U0];
-  float x2[3][MB][U1];
-  float x3[3][MB][U2];
-  float dy2[3][MB][U2];
-  float dy1[3][MB][U1];
-  // Gram matrices (MB x MB) of the factors of the minibatch currently held: inputs gx[net][layer 0..3], gradients gd[net][layer 0..2]
-  // (round 6: the gradient factors' Grams never leave the reduction that forms them - layer 0's meets G_x0 on the producing CU, layers 1 / 2
-  // meet theirs at the end of the dY0 shadow - so only the inputs' Grams and one partial squared norm per network are kept)
-  float gx[3][4][16];
-  float gd2[3][16];          // Gram of dY2 (formed in the dY1 shadow beside the Gram of x3, used at the end of the dY0 shadow)
-  float n2rest[4];           // per network: sum over trunk layers 1, 2 of <G_dY, G_x> + their bias terms + the heads' terms (n2h): everything but layer 0
-  float part[64 * 4];        // block_sum results
-  float fpart[3 * MB * NWV];  // cross-wave partial dot products of the forward passes
-  float red[4 * NWV][64];    // block_sum: one row per (wave, DPP row)
-  float mu[MB][32], dmu[MB][32], z[MB][32], act[MB][32], omu[MB][32], osg[MB][32];
-  float val[2][MB], dv[2][MB], gnlp[MB], ls[32], sgm[32], dls[32], stat[MB][8];   // sgm = exp(ls): formed with ls in the x3 shadow (round 6), not three times in the loss phase
-  // biases of the owned rows and their Adam moments, one thread per slot: [0..11] L0 (net*4 + row), [12..17] L1 (12 + net*2 + row),
-  // [18..20] L2 (18 + net), [21..45] heads (21 + row, replicated on every CU); logstd lives in the static bank s_b2
-  float bias[64], bias_m[64], bias_v[64];
-  float dyown[3][MB][8];     // dY of the owned rows: [net][s][0..3] L0 rows (per wave), [4..5] L1 rows, [6] L2 row
-  float scal[16];            // broadcast scalars of the step: 0 ac_gscale 1 cv_gscale 2 ac_lr_bc1 3 ac_isq 4 cv_lr_bc1 5 cv_isq
-  // control state machine, owned by thread 0 of every CU (every CU runs it on identical inputs, so the copies stay identical)
-  struct Ctl {
-    double ac_b1, ac_b2, cv_b1, cv_b2;
-    float ac_lr, ac_lr_applied, cv_lr, sum_a, sum_c, sum_b, sum_kl, sum_cv, sum_ent, last_kl, ac_gn, cv_gn;
-    int ac_t, cv_t;
-  } ctl;
-  int fail;
-  long long tacc[32], tlast;   // phase clock accumulators of CU 0 (SDXP_PERSIST_STAMPS=1)
-};
-
-// ---- (value, tag) exchange words ("LL" protocol): one relaxed 8-byte store at agent scope carries the float and the tag of the
-// optimiser step that produced it; a consumer re-reads until the tag it expects shows up.  No fences, no barriers, no reset:
-// tags only grow, and the data dependencies of the step (x1 -> x2 -> x3 -> dY1 -> dY0 -> next x1) guarantee that a word is not
-// overwritten before every CU has consumed it ("persistent update kernel").
-typedef unsigned long long u64;
-// Round 4: the five edges on the step's dependency chain (x1, x2, x3, dY1 and the dY0 Gram) travel as 16-BYTE words (v0, v1, v2, tag):
-// the same (sample, unit) of the THREE networks in one word, written and read by one dwordx4 access per lane (device scope, sc1).  The
-// all-gather alone, measured (tools/bench_exchange.py, profiles/r4_exchange_edge_floor.txt): x1 (12 288 floats) 6.0 us as 8-byte
-// words, 3.6 us packed; x2 / dY1 3.3 -> 2.1; the Gram 4.7 -> 2.5; x3 (3 072 floats) 2.0 either way; no torn word in ~1e10 checked
-// gathers (a 16-byte access of one lane is not architecturally single-copy atomic: the tag sits in the LAST dword, and the benchmark
-// verifies every payload against its tag; RCCL's LL128 protocol relies on the same hardware behaviour).  Since round 5 the last dword
-// carries tag ^ fold(payload) (lq_fold below): a torn word is rejected and polled again instead of being trusted to never occur.  The head matrix (LL_HW:
-// published a phase ahead, gathered row- and column-wise by different consumers) keeps its 8-byte words.
-// Layout of D.ll: 16-byte words LQ_* first, then the 8-byte head words at LL_HW (u64 index).
-constexpr unsigned LQ_X1 = 0, LQ_X2 = LQ_X1 + MB * U0, LQ_X3 = LQ_X2 + MB * U1, LQ_DY1 = LQ_X3 + MB * U2, LQ_DY0 = LQ_DY1 + MB * U1,
-                   LQ_G0 = LQ_DY0 + MB * U0, LQ_END = LQ_G0 + 16 * NWG;   // LQ_G0: [CU]: the CU's share of layer 0's squared gradient norm, the 3 nets per word (round 6; rounds 4-5: 10 Gram entries per CU)
-constexpr size_t LL_HW = 2 * (size_t)LQ_END, LL_END = LL_HW + (ACT + 2) * U2;
-static_assert(LL_END <= SDXP_LL_WORDS, "exchange buffer too small");
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t lq_rsrc(void* ll) { return __builtin_amdgcn_make_buffer_rsrc(ll, 0, SDXP_LL_WORDS * 8, 0x00020000); }
-// Tearing is DETECTABLE: the last dword is not the bare tag but tag ^ fold(payload); a consumer accepts a word only when
-// last ^ fold(the payload it read) equals the tag it waits for.  A word whose dwords come from two different stores (new tag over a
-// stale payload or the reverse) fails the test unless the mixed payload folds to the same value (2^-32, or the stale dwords equal the new
-// ones - then nothing is lost) and is simply polled again, like a word that has not arrived.
-// (fold = x ^ y ^ z: one v_xor3_b32.  With rotations of y and z in it - to decorrelate equal values of two networks - the checks cost the
-// step 0.6 us on its dependent chain, 31.4 instead of 30.8; two networks' values that are equal before AND after a step are unchanged ones)
-// Tags advance by 1 per step, so the XOR of two consecutive bare tags is 1, 3, 7, ...: a torn word (new payload over a stale last dword) whose
-// payload fold moved by exactly that - one network's value changing by an ulp - would pass.  The tag is therefore spread over all
-// 32 bits before it meets the fold (lq_tag: one scalar multiply per gather, off the dependent chain): consecutive tags now differ in ~16
-// pseudo-random bit positions, which a slowly varying payload does not reproduce.
-__device__ __forceinline__ unsigned lq_fold(unsigned x, unsigned y, unsigned z) { return x ^ y ^ z; }
-__device__ __forceinline__ unsigned lq_tag(unsigned tag) { return tag * 0x9E3779B1u; }
-__device__ __forceinline__ bool lq_ok(const u32x4& w, unsigned tag) { return (w.w ^ lq_fold(w.x, w.y, w.z)) == lq_tag(tag); }
-__device__ __forceinline__ void lq_store(__amdgpu_buffer_rsrc_t q, unsigned idx, float a, float b, float c, unsigned tag) {
-  u32x4 w;
-  w.x = __float_as_uint(a); w.y = __float_as_uint(b); w.z = __float_as_uint(c); w.w = lq_tag(tag) ^ lq_fold(w.x, w.y, w.z);
-  __builtin_amdgcn_raw_buffer_store_b128(w, q, idx * 16u, 0, 16);   // buffer_store_dwordx4 ... sc1
-}
-// gather N packed words idx0 + i * stride carrying `tag` -> the three networks' values; wave-uniform retry as ll_gather
-template <int N>
-__device__ __forceinline__ bool lq_gather(__amdgpu_buffer_rsrc_t q, unsigned idx0, unsigned stride, unsigned tag, float (&o0)[N], float (&o1)[N], float (&o2)[N],
-                                          unsigned* failflag) {
-  unsigned spins = 0;
-  for (;;) {
-    u32x4 w[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) w[i] = __builtin_amdgcn_raw_buffer_load_b128(q, (idx0 + i * stride) * 16u, 0, 16);   // buffer_load_dwordx4 ... sc1
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < N; ++i) ok = ok && lq_ok(w[i], tag);
-#pragma unroll
-    for (int i = 0; i < N; ++i) { o0[i] = __uint_as_float(w[i].x); o1[i] = __uint_as_float(w[i].y); o2[i] = __uint_as_float(w[i].z); }
-    if (__builtin_amdgcn_ballot_w64(!ok) == 0) return true;
-    __builtin_amdgcn_s_sleep(1);
-    if ((++spins & 255u) == 0) {
-      const unsigned f = __hip_atomic_load(failflag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (spins > (1u << 20) || __builtin_amdgcn_readfirstlane(f) != 0) {
-        __hip_atomic_store(failflag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return false;
-      }
-    }
-  }
-}
-// first look at N packed words, issued some work ahead of where they are needed (lq_peek), and the test whether all of them already
-// carried `tag` (lq_take): when a shadow phase outlasts its exchange edge the words are there, and the round trip of the gather
-// (about 0.6 us) runs under the shadow's last piece of work instead of after it.  A miss falls back to the polling lq_gather.
-template <int N>
-__device__ __forceinline__ void lq_peek(__amdgpu_buffer_rsrc_t q, unsigned idx0, unsigned stride, u32x4 (&w)[N]) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) w[i] = __builtin_amdgcn_raw_buffer_load_b128(q, (idx0 + i * stride) * 16u, 0, 16);
-}
-template <int N>
-__device__ __forceinline__ bool lq_take(const u32x4 (&w)[N], unsigned tag, float (&o0)[N], float (&o1)[N], float (&o2)[N]) {
-  bool ok = true;
-#pragma unroll
-  for (int i = 0; i < N; ++i) ok = ok && lq_ok(w[i], tag);
-#pragma unroll
-  for (int i = 0; i < N; ++i) { o0[i] = __uint_as_float(w[i].x); o1[i] = __uint_as_float(w[i].y); o2[i] = __uint_as_float(w[i].z); }
-  return __builtin_amdgcn_ballot_w64(!ok) == 0;
-}
-__device__ __forceinline__ void ll_store(u64* p, float v, unsigned tag) {
-  __hip_atomic_store(p, ((u64)tag << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// gather N words p[i * stride] carrying `tag`; false (and *failflag set) if they do not arrive.  The retry loop is wave-uniform
-// (all lanes reload until every lane has its words), which keeps the loaded values out of divergent-loop phis.
-template <int N>
-__device__ __forceinline__ bool ll_gather(const u64* p, size_t stride, unsigned tag, float (&out)[N], unsigned* failflag) {
-  unsigned spins = 0;
-  for (;;) {
-    u64 w[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) w[i] = __hip_atomic_load(p + i * stride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < N; ++i) ok = ok && (unsigned)(w[i] >> 32) == tag;
-#pragma unroll
-    for (int i = 0; i < N; ++i) out[i] = __uint_as_float((unsigned)w[i]);
-    if (__builtin_amdgcn_ballot_w64(!ok) == 0) return true;
-    __builtin_amdgcn_s_sleep(1);
-    if ((++spins & 255u) == 0) {
-      const unsigned f = __hip_atomic_load(failflag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (spins > (1u << 20) || __builtin_amdgcn_readfirstlane(f) != 0) {
-        __hip_atomic_store(failflag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return false;
-      }
-    }
-  }
-}
-// the same without the scheduling fence (elements whose gradients already sit in registers: the sqrt / rcp chains of neighbours may interleave)
-__device__ __forceinline__ void adam1f(float& w, float g, float& m, float& v, float lr_bc1, float isq_bc2) {
-  m = 0.9f * m + 0.1f * g;
-  v = 0.999f * v + 0.001f * g * g;
-  w -= lr_bc1 * m * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(v) * isq_bc2 + 1e-8f);
-}
-#define SDX_PIN4X(a, b, c, d) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
-#define SDX_PIN3X(a, b, c) asm volatile("" : "+v"(a), "+v"(b), "+v"(c))
-// layer 0 (the only Adam on the step's dependent chain): the moments arrive PRE-SCALED by 0.9 / 0.999 - done in the dY0 shadow, where the
-// element's gradient is formed - so that behind the clip scale an element is 7 VALU + sqrt + rcp instead of 11 (round 6)
-__device__ __forceinline__ void adam1p(float& w, float g, float& m9, float& v999, float lr_bc1, float isq_bc2) {
-  m9 = __builtin_fmaf(0.1f, g, m9);
-  v999 = __builtin_fmaf(0.001f * g, g, v999);
-  w -= lr_bc1 * m9 * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(v999) * isq_bc2 + 1e-8f);
-  __builtin_amdgcn_sched_barrier(0);
-}
-#define ADAM0 adam1p
-// accumulate the 4x4 Gram (lower triangle, 10 terms) and |sum|^2 of (a, b, c, d)
-__device__ __forceinline__ void gram_acc(float* p, float a, float b, float c, float d) {
-  p[0] += a * a; p[1] += b * a; p[2] += b * b; p[3] += c * a; p[4] += c * b; p[5] += c * c;
-  p[6] += d * a; p[7] += d * b; p[8] += d * c; p[9] += d * d;
-  const float sb = a + b + c + d;
-  p[10] += sb * sb;
-}
-__device__ __forceinline__ void gram_acc10(float* p, float a, float b, float c, float d) {   // the 10 entries only (inputs: no bias term)
-  p[0] += a * a; p[1] += b * a; p[2] += b * b; p[3] += c * a; p[4] += c * b; p[5] += c * c;
-  p[6] += d * a; p[7] += d * b; p[8] += d * c; p[9] += d * d;
-}
-__device__ __forceinline__ int tri16(int i) { const int a = i >> 2, b = i & 3, hi = a > b ? a : b, lo = a > b ? b : a; return hi * (hi + 1) / 2 + lo; }
-// sums over each 32-lane half of the wave; valid in lanes 16..31 and 48..63
-__device__ __forceinline__ float half_sum(float v) {
-  v = dpp_add<0xB1, 0xF>(v); v = dpp_add<0x4E, 0xF>(v); v = dpp_add<0x141, 0xF>(v); v = dpp_add<0x140, 0xF>(v);
-  return dpp_add<0x142, 0xA>(v);
-}
-
-// block-wide sums of N per-thread values (N <= 64); result in out[0..N).  Two "halving" butterfly levels (lane pairs keep the even /
-// odd half of the values, so level L costs N / 2^L exchanges instead of N), two more within the 16-lane DPP row, and the 4 rows x 8
-// waves meet in LDS: ~3.5 N VALU ops + N/4 LDS writes per wave instead of 7 N + N masked writes for N independent wave sums.
-template <int CTRL, int BANK>
-__device__ __forceinline__ float dpp_mov(float old, float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v), CTRL, 0xF, BANK, false));
-}
-// the two halving levels + the two levels inside the 16-lane DPP row: u2[j] = sum over the row's lanes of value 4 j + (lane & 3)
-template <int N>
-__device__ __forceinline__ void row_butterfly(const float (&v)[N], float (&u2)[(N + 3) / 4], int lane) {
-  constexpr int N4 = (N + 3) / 4;
-  const bool b0 = lane & 1, b1 = lane & 2;
-  float u1[2 * N4];
-#pragma unroll
-  for (int j = 0; j < 2 * N4; ++j) {
-    const float e = 2 * j < N ? v[2 * j] : 0.0f, o = 2 * j + 1 < N ? v[2 * j + 1] : 0.0f;
-    const float keep = b0 ? o : e, send = b0 ? e : o;
-    u1[j] = keep + dpp_mov<0xB1, 0xF>(0.0f, send);           // partner lane ^ 1
-  }
-#pragma unroll
-  for (int j = 0; j < N4; ++j) {
-    const float keep = b1 ? u1[2 * j + 1] : u1[2 * j], send = b1 ? u1[2 * j] : u1[2 * j + 1];
-    float t = keep + dpp_mov<0x4E, 0xF>(0.0f, send);         // partner lane ^ 2: t = quad sum of value 4 j + (lane & 3)
-    float x = dpp_mov<0x114, 0xA>(0.0f, t);                  // lane ^ 4: row_shr:4 into banks 1,3 ...
-    x = dpp_mov<0x104, 0x5>(x, t);                           // ... row_shl:4 into banks 0,2
-    t += x;
-    t += dpp_mov<0x128, 0xF>(0.0f, t);                       // lane ^ 8 (row_ror:8): sum over the 16-lane row
-    u2[j] = t;
-  }
-}
-// N wave sums at once: the row butterfly, then the rows meet through v_permlane16_swap (partner lane ^ 16: rows 0 + 1, 2 + 3) and
-// v_permlane32_swap (lane ^ 32).  Every lane ends with u[j] = the whole wave's sum of value 4 j + (lane & 3).  The pairs of the six levels
-// are those of wave_sum's DPP tree (quad_perm, quad_perm, row_half_mirror, row_mirror, row_bcast15, row_bcast31) and IEEE addition
-// commutes, so u[j] equals wave_sum(v[4 j + (lane & 3)]) bit for bit - at N / 2, N / 4, N / 4, ... adds per level instead of N.
-template <int N>
-__device__ __forceinline__ void wave_sums(const float (&v)[N], float (&u)[(N + 3) / 4], int lane) {
-  // (opaque copies: the sums are those of the ROUNDED values - a value that is a bare product must not be contracted with the butterfly's first
-  // add into an fma, through the level's select.  wave_sum of a bare product IS contracted that way, per lane: forward L2, whose values are
-  // bare products, has a butterfly of its own - fwd2_sums below.)
-  float t[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i) { t[i] = v[i]; asm("" : "+v"(t[i])); }
-  row_butterfly<N>(t, u, lane);
-#pragma unroll
-  for (int j = 0; j < (N + 3) / 4; ++j) {
-    const unsigned x = __builtin_bit_cast(unsigned, u[j]);
-    const auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
-    u[j] = pair_sum(__builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]));
-  }
-}
-// Forward L2: the wave sums of the twelve BARE products w[net] x[net][s], with the bits of twelve wave_sum trees.  wave_sum(w x) compiles to
-// v_mul (the rounded product) / v_mov_dpp quad_perm:[1,0,3,2] / v_fmac: lane l holds fma(w_l, x_l, rounded product of lane l ^ 1), so the two
-// lanes of a pair hold different bits, and of a DPP row only the lanes whose view the rest of the tree carries to lane 63 count - 15, 13, 8,
-// 10, 0, 2, 7, 5: row sum = ((v15 + v13) + (v8 + v10)) + ((v0 + v2) + (v7 + v5)), wave sum = (r3 + r2) + (r1 + r0).  Here the first level is
-// written out - on every lane, twelve independent fmas, the product through an opaque copy so that it stays rounded - and the other levels run
-// as a halving butterfly over exactly those pairs: partner l ^ 2 (the lanes with bit 0 == bit 1 keep samples 0 and 3, the others 1 and 2),
-// row_half_mirror (bit 2 == bit 3 keeps the first of the two), row_mirror, then the rows as in wave_sums.  Addition commutes, pairing does
-// not.  Lanes 0, 2, 5, 7 (and their mirrors 15, 13, 10, 8) of every row end with u[net] = the wave's sum of sample 0, 1, 2, 3: lanes 1 and 3
-// are not on the tree's path, so the storing lanes are not 0..3 (fwd2_sample, fwd2_store).
-__device__ __forceinline__ int fwd2_sample(int lane) {
-  const bool ka = (((lane >> 1) ^ lane) & 1) == 0, kf = (((lane >> 3) ^ (lane >> 2)) & 1) == 0;
-  return kf ? (ka ? 0 : 1) : (ka ? 3 : 2);
-}
-__device__ __forceinline__ void fwd2_sums(const float (&w)[3], const float (&x)[3][4], float (&u)[3], int lane) {
-  const bool ka = (((lane >> 1) ^ lane) & 1) == 0, kf = (((lane >> 3) ^ (lane >> 2)) & 1) == 0;
-  float v[3][4];
-#pragma unroll
-  for (int net = 0; net < 3; ++net)
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      float t = w[net] * x[net][s];
-      asm("" : "+v"(t));
-      v[net][s] = __builtin_fmaf(w[net], x[net][s], dpp_mov<0xB1, 0xF>(0.0f, t));   // partner lane ^ 1
-    }
-#pragma unroll
-  for (int net = 0; net < 3; ++net) {
-    const float k0 = ka ? v[net][0] : v[net][1], s0 = ka ? v[net][1] : v[net][0];
-    const float k1 = ka ? v[net][3] : v[net][2], s1 = ka ? v[net][2] : v[net][3];
-    const float a = k0 + dpp_mov<0x4E, 0xF>(0.0f, s0), b = k1 + dpp_mov<0x4E, 0xF>(0.0f, s1);   // partner lane ^ 2
-    float t = (kf ? a : b) + dpp_mov<0x141, 0xF>(0.0f, kf ? b : a);                              // row_half_mirror: lane ^ 7
-    t += dpp_mov<0x140, 0xF>(0.0f, t);                                                           // row_mirror: lane ^ 15
-    const unsigned y = __builtin_bit_cast(unsigned, t);
-    const auto r = __builtin_amdgcn_permlane16_swap(y, y, false, false);
-    u[net] = pair_sum(__builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]));
-  }
-}
-// the forward passes' partial dot products, value net MB + s: lane s < MB holds u[net] = this wave's sum of (net, sample s)
-static_assert(MB == 4, "lane & 3 of wave_sums is the sample");
-__device__ __forceinline__ void fpart_store(PLds& S, const float (&u)[3], int wave, int lane) {
-  if (lane < MB) {
-#pragma unroll
-    for (int net = 0; net < 3; ++net) S.fpart[(net * MB + lane) * NWV + wave] = u[net];
-  }
-}
-// the same slots from fwd2_sums: lanes 0, 2, 5, 7 hold samples 0, 1, 2, 3
-__device__ __forceinline__ void fwd2_store(PLds& S, const float (&u)[3], int wave, int lane) {
-  if (lane < 8 && ((0xA5 >> lane) & 1)) {
-    const int s = fwd2_sample(lane);
-#pragma unroll
-    for (int net = 0; net < 3; ++net) S.fpart[(net * MB + s) * NWV + wave] = u[net];
-  }
-}
-template <int N4>
-__device__ __forceinline__ void rows_store(PLds& S, const float (&u2)[N4], int off, int wave, int lane) {
-  if ((lane & 15) < 4) {
-    float* r = S.red[wave * 4 + (lane >> 4)] + off;
-#pragma unroll
-    for (int j = 0; j < N4; ++j) r[4 * j + (lane & 3)] = u2[j];
-  }
-}
-// LDS-only barriers (sdx_common.h): __syncthreads() also waits for the wave's outstanding global accesses - in the shadows that is the
-// acknowledgement of the exchange words just published and the next minibatch's prefetched rows; nothing here is ordered through HBM
-__device__ __forceinline__ void rows_reduce(PLds& S, int n, float* out, int tid) {
-  SDX_LDS_BARRIER();
-  if (tid < n) {
-    float t = 0.0f;
-#pragma unroll
-    for (int w = 0; w < 4 * NWV; ++w) t += S.red[w][tid];
-    out[tid] = t;
-  }
-  SDX_LDS_BARRIER();
-}
-template <int N>
-__device__ __forceinline__ void block_sum(PLds& S, const float (&v)[N], float* out, int tid, int wave, int lane) {
-  float u2[(N + 3) / 4];
-  row_butterfly<N>(v, u2, lane);
-  rows_store<(N + 3) / 4>(S, u2, 0, wave, lane);
-  rows_reduce(S, N, out, tid);
-}
-
-static_assert(sizeof(PLds) + 512 <= 160 * 1024, "PLds (+ the static logstd bank) must fit the 160 KiB LDS of a gfx950 CU");
-}  // namespace
+#include "sdxp_persist_lds.h"        // shape constants, PLds, names of its slots and of the recurring thread windows
+#include "sdxp_persist_exchange.h"   // lq_* / ll_* tagged words between the CUs
+#include "sdxp_persist_sums.h"       // row / wave / block sums, Gram accumulators
+#include "sdxp_persist_adam.h"       // adam1, adam1p, opaque, SDX_PIN*
 
 // dataset-row helpers
 __device__ __forceinline__ const float* obs_rows(const SdxpDev& D, int mb) { return D.mb_obs + (size_t)mb * MB * D.obs_dim; }
@@ -432,12 +92,19 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
   auto head_woff = [&](int row) -> size_t { return row < A ? D.off.mu_w + (size_t)row * U2 : (row == A ? D.off.v_w : D.coff.v_w); };
   auto head_boff = [&](int row) -> size_t { return row < A ? D.off.mu_b + row : (row == A ? D.off.v_b : D.coff.v_b); };
   auto head_net = [&](int row) -> int { return row < A ? 0 : (row == A ? 1 : 2); };
+  // column of element i of this lane's layer-1 row quarter (o_w1 and forward L1; the Adam shadow forms its own through opaque())
+  auto k_w1 = [&](int i) -> int { return q1 * 256 + lane + 64 * i; };
+  // flat offset, in the network's parameter and moment arrays, of elements this lane owns: prologue and epilogue use the same names.  (The central
+  // value's layer-0 half row and the layer-2 row eighth stay spelled out in both: named, the one-minibatch prologue forms its addresses differently.)
+  auto o_w0 = [&](int net, int k) -> size_t { return woff(net, 0) + (size_t)n0 * D.obs_dim + k; };   // actor / critic (net 0 / 1)
+  auto o_w1 = [&](int net, int i) -> size_t { return woff(net, 1) + (size_t)r1 * U0 + q1 * 256 + lane + 64 * i; };   // (k_w1(i), added term by term in 64 bits)
+  auto o_hw = [&]() -> size_t { return head_woff(hrow) + hk; };
 
 #pragma unroll
   for (int i = 0; i < I0A; ++i) {
     const int kk = lane + 64 * i, k = h0 * H0A + kk;
     const bool ok = kk < H0A && k < D.obs_dim;
-    const size_t oa = woff(0, 0) + (size_t)n0 * D.obs_dim + k, oc = woff(1, 0) + (size_t)n0 * D.obs_dim + k;
+    const size_t oa = o_w0(0, k), oc = o_w0(1, k);
     w0a[i] = ok ? D.ac[oa] : 0.0f; m0a[i] = ok ? ldm(D.ac_m, oa) : 0.0f; v0a[i] = ok ? ldm(D.ac_v, oa) : 0.0f;
     w0c[i] = ok ? D.ac[oc] : 0.0f; m0c[i] = ok ? ldm(D.ac_m, oc) : 0.0f; v0c[i] = ok ? ldm(D.ac_v, oc) : 0.0f;
   }
@@ -452,7 +119,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
   for (int net = 0; net < 3; ++net) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const size_t o = woff(net, 1) + (size_t)r1 * U0 + q1 * 256 + lane + 64 * i;
+      const size_t o = o_w1(net, i);
       w1[net][i] = P_of(net)[o]; m1[net][i] = ldm(M_of(net), o); v1[net][i] = ldm(V_of(net), o);
     }
 #pragma unroll
@@ -471,29 +138,19 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
   }
   if (tid < HPC) {
     const int net = head_net(hrow);
-    const size_t o = head_woff(hrow) + hk;
+    const size_t o = o_hw();
     hw = P_of(net)[o]; hm = ldm(M_of(net), o); hv = ldm(V_of(net), o);
   }
   // biases + logstd (LDS, one thread each)
   __shared__ float s_b2[3][32];     // logstd value, m, v
-  if (tid < 12) {   // bias slot map: L0 net*4 + row (12), L1 12 + net*2 + row (6), L2 18 + net (3), heads 21 + row (25)
-    const int net = tid / 4, w = tid % 4;
-    const size_t o = boff(net, 0) + 4 * g + w;
-    S.bias[tid] = P_of(net)[o]; S.bias_m[tid] = ldm(M_of(net), o); S.bias_v[tid] = ldm(V_of(net), o);
-  } else if (tid < 18) {
-    const int net = (tid - 12) / 2, r = (tid - 12) % 2;
-    const size_t o = boff(net, 1) + 2 * g + r;
-    S.bias[tid] = P_of(net)[o]; S.bias_m[tid] = ldm(M_of(net), o); S.bias_v[tid] = ldm(V_of(net), o);
-  } else if (tid < 21) {
-    const int net = tid - 18;
-    const size_t o = boff(net, 2) + g;
-    S.bias[tid] = P_of(net)[o]; S.bias_m[tid] = ldm(M_of(net), o); S.bias_v[tid] = ldm(V_of(net), o);
-  } else if (tid < 21 + A + 2) {
-    const int row = tid - 21, net = head_net(row);
-    const size_t o = head_boff(row);
-    S.bias[tid] = P_of(net)[o]; S.bias_m[tid] = ldm(M_of(net), o); S.bias_v[tid] = ldm(V_of(net), o);
-  } else if (tid >= 64 && tid < 64 + A) {
-    const int a = tid - 64;
+  auto bias_load = [&](int net, size_t o) { S.bias[tid] = P_of(net)[o]; S.bias_m[tid] = ldm(M_of(net), o); S.bias_v[tid] = ldm(V_of(net), o); };
+  // (the slot map of S.bias, BIAS_*; the epilogue walks the same ladder: stated once for both, it changes thousands of lines of both instantiations)
+  if (tid < BIAS_L1) { const int net = (tid - BIAS_L0) / 4, w = (tid - BIAS_L0) % 4; bias_load(net, boff(net, 0) + 4 * g + w); }
+  else if (tid < BIAS_L2) { const int net = (tid - BIAS_L1) / 2, r = (tid - BIAS_L1) % 2; bias_load(net, boff(net, 1) + 2 * g + r); }
+  else if (tid < BIAS_HEAD) { const int net = tid - BIAS_L2; bias_load(net, boff(net, 2) + g); }
+  else if (tid < BIAS_HEAD + A + 2) { const int row = tid - BIAS_HEAD; bias_load(head_net(row), head_boff(row)); }
+  else if (tid >= T_LOGSTD && tid < T_LOGSTD + A) {
+    const int a = tid - T_LOGSTD;
     const size_t o = D.off.logstd + a;
     s_b2[0][a] = D.ac[o]; s_b2[1][a] = ldm(D.ac_m, o); s_b2[2][a] = ldm(D.ac_v, o);
   }
@@ -577,19 +234,17 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     const unsigned tag = tag_base + (unsigned)step + 1u, tag_prev = tag_base + (unsigned)step;
     // ================================================================== phase A: gradient norm, Adam of layer 0, forward L0
     if (pending) {
-      // Squared gradient norm -> clip scale, WITHOUT a workgroup barrier or an LDS pass on the step's dependent chain (round 6).  Every CU
-      // published ONE word at the end of the previous step: its four columns' share of <G_dY0, G_x0> + |sum_s dY0_s|^2 for the three
-      // networks (rounds 4-5: the 10 entries of its Gram; 320 threads gathered 2 560 words, reduced them through LDS and wave 0 ran the
-      // control block between two barriers: 2.2 us from the top of the step to the first Adam instruction).  Every WAVE now gathers the
-      // 256 words itself - CUs lane, lane + 64, ... - and adds them in one fixed order (pair sums, then the DPP tree of wave_sum), so all
-      // waves of all CUs hold bit-identical scalars and walk into Adam of layer 0 as their own words arrive.  What does not depend on dY0
-      // - the other layers' and the heads' terms (S.n2rest), the bias corrections and the learning-rate scalars (S.scal[2..5]) - was
-      // prepared in the shadows of the previous step.
+      // Squared gradient norm -> clip scale, WITHOUT a workgroup barrier or an LDS pass on the step's dependent chain.  Every CU published
+      // ONE word at the end of the previous step: its four columns' share of <G_dY0, G_x0> + |sum_s dY0_s|^2 for the three networks.  Every
+      // WAVE gathers the 256 words itself - CUs lane, lane + 64, ... - and adds them in one fixed order (pair sums, then the DPP tree of
+      // wave_sum), so all waves of all CUs hold bit-identical scalars and walk into Adam of layer 0 as their own words arrive.  What does not
+      // depend on dY0 - the other layers' and the heads' terms (S.n2rest), the bias corrections and the learning-rate scalars
+      // (S.scal[SC_AC_LR_BC1 ..]) - was prepared in the shadows of the previous step.
       // (what the scalars below need from LDS is requested in front of the norm words' take: one LDS round trip less behind the DPP sums)
       float nr0 = S.n2rest[0], nr1 = S.n2rest[1], nr2 = S.n2rest[2];
-      float ac_lr_bc1 = S.scal[2], ac_isq = S.scal[3], cv_lr_bc1 = S.scal[4], cv_isq = S.scal[5];
+      float ac_lr_bc1 = S.scal[SC_AC_LR_BC1], ac_isq = S.scal[SC_AC_ISQ], cv_lr_bc1 = S.scal[SC_CV_LR_BC1], cv_isq = S.scal[SC_CV_ISQ];
       float w0[4], w1[4], w2[4];
-      if (!(pg0_issued && lq_take<4>(pg0, tag_prev, w0, w1, w2)) && !lq_gather<4>(LQ, LQ_G0 + lane, 64, tag_prev, w0, w1, w2, failflag)) S.fail = 1;
+      lq_take_or_gather<4>(pg0_issued, pg0, LQ, LQ_G0 + lane, 64, tag_prev, w0, w1, w2, failflag, S.fail);
       float n2[3];
       n2[0] = (w0[0] + w0[1]) + (w0[2] + w0[3]); n2[1] = (w1[0] + w1[1]) + (w1[2] + w1[3]); n2[2] = (w2[0] + w2[1]) + (w2[2] + w2[3]);
 #pragma unroll
@@ -601,23 +256,21 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       const float ac_gn = __builtin_amdgcn_sqrtf(n2[0] + n2[1]), cv_gn = __builtin_amdgcn_sqrtf(n2[2]);
       const float gs_ac = D.truncate_grads ? fminf(1.0f, D.grad_norm * __builtin_amdgcn_rcpf(ac_gn + 1e-6f)) : 1.0f;
       const float gs_cv = D.truncate_grads ? fminf(1.0f, D.grad_norm * __builtin_amdgcn_rcpf(cv_gn + 1e-6f)) : 1.0f;
-      if (tid == 0) { S.ctl.ac_gn = ac_gn; S.ctl.cv_gn = cv_gn; S.scal[0] = gs_ac; S.scal[1] = gs_cv; }   // for the shadows' Adam phases (behind the next barrier)
+      if (tid == 0) { S.ctl.ac_gn = ac_gn; S.ctl.cv_gn = cv_gn; S.scal[SC_AC_GSCALE] = gs_ac; S.scal[SC_CV_GSCALE] = gs_cv; }   // for the shadows' Adam phases (behind the next barrier)
       TS(0)
       // ---- layer 0 rows: gradient elements from registers (g0a / g0c / g0v, dY0 shadow of the previous iteration), scaled by the clip factor
 #pragma unroll
       for (int i = 0; i < I0A; ++i) {
-        ADAM0(w0a[i], g0a[i] * gs_ac, m0a[i], v0a[i], ac_lr_bc1, ac_isq);
-        ADAM0(w0c[i], g0c[i] * gs_ac, m0c[i], v0c[i], ac_lr_bc1, ac_isq);
+        adam1p(w0a[i], g0a[i] * gs_ac, m0a[i], v0a[i], ac_lr_bc1, ac_isq);
+        adam1p(w0c[i], g0c[i] * gs_ac, m0c[i], v0c[i], ac_lr_bc1, ac_isq);
       }
 #pragma unroll
-      for (int i = 0; i < I0V; ++i) ADAM0(w0v[i], g0v[i] * gs_cv, m0v[i], v0v[i], cv_lr_bc1, cv_isq);
-      if (tid < 12) {   // layer-0 biases (bias gradient = sum_s dY_s[row])
-        const int net = tid / 4;
+      for (int i = 0; i < I0V; ++i) adam1p(w0v[i], g0v[i] * gs_cv, m0v[i], v0v[i], cv_lr_bc1, cv_isq);
+      if (tid < BIAS_L1) {   // layer-0 biases (bias gradient = sum_s dY_s[row])
+        const int net = (tid - BIAS_L0) / 4;
         float gg = 0.0f;
-        for (int s = 0; s < MB; ++s) gg += S.dyown[net][s][tid % 4];
-        float b = S.bias[tid], bm = S.bias_m[tid], bv = S.bias_v[tid];
-        adam1(b, gg * (net == 2 ? gs_cv : gs_ac), bm, bv, net == 2 ? cv_lr_bc1 : ac_lr_bc1, net == 2 ? cv_isq : ac_isq);
-        S.bias[tid] = b; S.bias_m[tid] = bm; S.bias_v[tid] = bv;
+        for (int s = 0; s < MB; ++s) gg += S.dyown[net][s][DY_L0 + (tid - BIAS_L0) % 4];
+        adam_bias(S, StepScal{gs_ac, gs_cv, ac_lr_bc1, ac_isq, cv_lr_bc1, cv_isq}, tid, net, gg);
       }
       TS(1)
     }
@@ -659,7 +312,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
         float y[3];
 #pragma unroll
         for (int net = 0; net < 3; ++net)
-          y[net] = elu(S.fpart[(net * MB + s) * NWV + 2 * r] + S.fpart[(net * MB + s) * NWV + 2 * r + 1] + S.bias[net * 4 + r]);
+          y[net] = elu(S.fpart[(net * MB + s) * NWV + 2 * r] + S.fpart[(net * MB + s) * NWV + 2 * r + 1] + S.bias[BIAS_L0 + net * 4 + r]);
         lq_store(LQ, LQ_X1 + (unsigned)s * U0 + 4 * g + r, y[0], y[1], y[2], tag);
       }
       TS(2)
@@ -679,16 +332,15 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     refresh();
     if (pending) {
       // ---- (shadow of x1) Adam of layer 1: row copy and column copy, operands are last step's S.x1 / S.dy1
-      const float gs_ac = S.scal[0], gs_cv = S.scal[1];
-      const float ac_lr_bc1 = S.scal[2], ac_isq = S.scal[3], cv_lr_bc1 = S.scal[4], cv_isq = S.scal[5];
+      const StepScal sc = step_scal(S);
       float dep = 0.0f;
 #pragma unroll
       for (int net = 0; net < 3; ++net) {
-        const float gs = net == 2 ? gs_cv : gs_ac, lrb = net == 2 ? cv_lr_bc1 : ac_lr_bc1, isq = net == 2 ? cv_isq : ac_isq;
+        const float gs = sc.gs(net), lrb = sc.lrb(net), isq = sc.isq(net);
         float d1r[MB], dn1[MB];
         const int o_r = opaque(r1w, dep), o_t = opaque(tid, dep);
 #pragma unroll
-        for (int s = 0; s < MB; ++s) { d1r[s] = S.dyown[net][s][4 + o_r] * gs; dn1[s] = S.dy1[net][s][o_t] * gs; }
+        for (int s = 0; s < MB; ++s) { d1r[s] = S.dyown[net][s][DY_L1 + o_r] * gs; dn1[s] = S.dy1[net][s][o_t] * gs; }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int k = opaque(q1 * 256 + lane + 64 * i, dep);
@@ -706,13 +358,11 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
           adam1(c1[net][c], gg, cm1[net][c], cv1[net][c], lrb, isq); dep = c1[net][c];
         }
       }
-      if (tid >= 12 && tid < 18) {   // layer-1 biases
-        const int net = (tid - 12) / 2;
+      if (tid >= BIAS_L1 && tid < BIAS_L2) {   // layer-1 biases
+        const int net = (tid - BIAS_L1) / 2;
         float gg = 0.0f;
-        for (int s = 0; s < MB; ++s) gg += S.dyown[net][s][4 + (tid - 12) % 2];
-        float b = S.bias[tid], bm = S.bias_m[tid], bv = S.bias_v[tid];
-        adam1(b, gg * (net == 2 ? gs_cv : gs_ac), bm, bv, net == 2 ? cv_lr_bc1 : ac_lr_bc1, net == 2 ? cv_isq : ac_isq);
-        S.bias[tid] = b; S.bias_m[tid] = bm; S.bias_v[tid] = bv;
+        for (int s = 0; s < MB; ++s) gg += S.dyown[net][s][DY_L1 + (tid - BIAS_L1) % 2];
+        adam_bias(S, sc, tid, net, gg);
       }
     }
     TS(3)
@@ -722,8 +372,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       {
         float v0[8], v1[8], v2[8];   // word tid + NTH j = (sample, unit) s U0 + unit: S.x1[net] is [MB][U0], i.e. the same flat index
         if (!lq_gather<8>(LQ, LQ_X1 + tid, NTH, tag, v0, v1, v2, failflag)) S.fail = 1;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { (&S.x1[0][0][0])[tid + NTH * j] = v0[j]; (&S.x1[1][0][0])[tid + NTH * j] = v1[j]; (&S.x1[2][0][0])[tid + NTH * j] = v2[j]; }
+        image_store(S.x1, v0, v1, v2, tid);
       }
       TS(4)
       __syncthreads();
@@ -735,7 +384,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
           for (int s = 0; s < MB; ++s) q[net * MB + s] = 0.0f;
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
-            const int k = q1 * 256 + lane + 64 * i;
+            const int k = k_w1(i);
 #pragma unroll
             for (int s = 0; s < MB; ++s) q[net * MB + s] += w1[net][i] * S.x1[net][s][k];
           }
@@ -750,7 +399,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
 #pragma unroll
         for (int net = 0; net < 3; ++net) {
           const float* q = &S.fpart[(net * MB + s) * NWV + 4 * r];
-          y[net] = elu(q[0] + q[1] + q[2] + q[3] + S.bias[12 + net * 2 + r]);
+          y[net] = elu(q[0] + q[1] + q[2] + q[3] + S.bias[BIAS_L1 + net * 2 + r]);
         }
         lq_store(LQ, LQ_X2 + (unsigned)s * U1 + 2 * g + r, y[0], y[1], y[2], tag);
       }
@@ -763,19 +412,18 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     bool px2_issued = false;
     if (pending) {
       // ---- (shadow of x2) Adam of layer 2 (row and column copies), of this CU's head elements, of the remaining biases and logstd
-      const float gs_ac = S.scal[0], gs_cv = S.scal[1];
-      const float ac_lr_bc1 = S.scal[2], ac_isq = S.scal[3], cv_lr_bc1 = S.scal[4], cv_isq = S.scal[5];
+      const StepScal sc = step_scal(S);
       float dep = 0.0f;
 #pragma unroll
       for (int net = 0; net < 3; ++net) {
         // first look at this lane's x2 words before the last network's update: the shadow has outlasted the edge by then (2.2 us of
         // its 2.8 against an edge of 2.1), what follows hides the round trip
         if (net == 2 && !last) { lq_peek<4>(LQ, LQ_X2 + tid, NTH, px2); px2_issued = true; }
-        const float gs = net == 2 ? gs_cv : gs_ac, lrb = net == 2 ? cv_lr_bc1 : ac_lr_bc1, isq = net == 2 ? cv_isq : ac_isq;
+        const float gs = sc.gs(net), lrb = sc.lrb(net), isq = sc.isq(net);
         float d2r[MB], dn2[MB];
         const int o_n = opaque(c2n, dep);
 #pragma unroll
-        for (int s = 0; s < MB; ++s) { d2r[s] = S.dyown[net][s][6] * gs; dn2[s] = S.dy2[net][s][o_n] * gs; }
+        for (int s = 0; s < MB; ++s) { d2r[s] = S.dyown[net][s][DY_L2] * gs; dn2[s] = S.dy2[net][s][o_n] * gs; }
         {
           const int k = opaque(wave * 64 + lane, dep);
           float gg = 0.0f;
@@ -794,24 +442,22 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       // heads: this CU's HPC elements; the new weight is published for phase D of every CU (tag == step)
       if (tid < HPC) {
         const int net = head_net(hrow);
-        const float gs = net == 2 ? gs_cv : gs_ac, lrb = net == 2 ? cv_lr_bc1 : ac_lr_bc1, isq = net == 2 ? cv_isq : ac_isq;
+        const float gs = sc.gs(net), lrb = sc.lrb(net), isq = sc.isq(net);
         float gg = 0.0f;
 #pragma unroll
         for (int s = 0; s < MB; ++s) gg += (hrow < A ? S.dmu[s][hrow] : S.dv[hrow - A][s]) * gs * S.x3[net][s][hk];
         adam1(hw, gg, hm, hv, lrb, isq);
         ll_store(LL + LL_HW + he, hw, tag_prev);
       }
-      if (tid >= 18 && tid < 21 + A + 2) {   // layer-2 and head biases
+      if (tid >= BIAS_L2 && tid < BIAS_HEAD + A + 2) {   // layer-2 and head biases
         int net; float gg = 0.0f;
-        if (tid < 21) { net = tid - 18; for (int s = 0; s < MB; ++s) gg += S.dyown[net][s][6]; }
-        else { const int row = tid - 21; net = head_net(row); for (int s = 0; s < MB; ++s) gg += row < A ? S.dmu[s][row] : S.dv[row - A][s]; }
-        float b = S.bias[tid], bm = S.bias_m[tid], bv = S.bias_v[tid];
-        adam1(b, gg * (net == 2 ? gs_cv : gs_ac), bm, bv, net == 2 ? cv_lr_bc1 : ac_lr_bc1, net == 2 ? cv_isq : ac_isq);
-        S.bias[tid] = b; S.bias_m[tid] = bm; S.bias_v[tid] = bv;
-      } else if (tid >= 64 && tid < 64 + A) {   // logstd
-        const int a = tid - 64;
+        if (tid < BIAS_HEAD) { net = tid - BIAS_L2; for (int s = 0; s < MB; ++s) gg += S.dyown[net][s][DY_L2]; }
+        else { const int row = tid - BIAS_HEAD; net = head_net(row); for (int s = 0; s < MB; ++s) gg += row < A ? S.dmu[s][row] : S.dv[row - A][s]; }
+        adam_bias(S, sc, tid, net, gg);
+      } else if (tid >= T_LOGSTD && tid < T_LOGSTD + A) {   // logstd
+        const int a = tid - T_LOGSTD;
         float b = s_b2[0][a], bm = s_b2[1][a], bv = s_b2[2][a];
-        adam1(b, S.dls[a] * gs_ac, bm, bv, ac_lr_bc1, ac_isq);
+        adam1(b, S.dls[a] * sc.gs(0), bm, bv, sc.lrb(0), sc.isq(0));
         s_b2[0][a] = b; s_b2[1][a] = bm; s_b2[2][a] = bv;
       }
     }
@@ -841,12 +487,11 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       float x[3][MB], u[3];
       {
         float v0[4], v1[4], v2[4];
-        if (!(px2_issued && lq_take<4>(px2, tag, v0, v1, v2)) && !lq_gather<4>(LQ, LQ_X2 + tid, NTH, tag, v0, v1, v2, failflag)) S.fail = 1;
+        lq_take_or_gather<4>(px2_issued, px2, LQ, LQ_X2 + tid, NTH, tag, v0, v1, v2, failflag, S.fail);
         TS(7)
 #pragma unroll
         for (int s = 0; s < MB; ++s) { x[0][s] = v0[s]; x[1][s] = v1[s]; x[2][s] = v2[s]; }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { (&S.x2[0][0][0])[tid + NTH * j] = v0[j]; (&S.x2[1][0][0])[tid + NTH * j] = v1[j]; (&S.x2[2][0][0])[tid + NTH * j] = v2[j]; }
+        image_store(S.x2, v0, v1, v2, tid);
       }
       // (no barrier here: the one that stood between the S.x2 stores and their read-back also kept the S.fpart stores below behind forward L1's
       // readers of S.fpart - the barrier in front of phase C does that - and the S.x2 stores in front of their readers, which all sit behind
@@ -863,7 +508,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
 #pragma unroll
       for (int net = 0; net < 3; ++net) {
         const float* q = &S.fpart[(net * MB + s) * NWV];
-        float t = S.bias[18 + net];
+        float t = S.bias[BIAS_L2 + net];
 #pragma unroll
         for (int w = 0; w < NWV; ++w) t += q[w];
         y[net] = elu(t);
@@ -873,7 +518,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     TS(8)
     // (this minibatch's actions and old (mu, sigma) go to LDS before the Grams: three registers fewer across the 60-value reduction)
     if (tid < MB * 32) { S.act[tid / 32][tid % 32] = pf_act; S.omu[tid / 32][tid % 32] = pf_omu; S.osg[tid / 32][tid % 32] = pf_osg; }
-    if (tid >= 128 && tid < 128 + 32) { const float l_ = (tid - 128 < A) ? s_b2[0][tid - 128] : 0.0f; S.ls[tid - 128] = l_; S.sgm[tid - 128] = expf(l_); }
+    if (tid >= T_LS && tid < T_LS + 32) { const float l_ = (tid - T_LS < A) ? s_b2[0][tid - T_LS] : 0.0f; S.ls[tid - T_LS] = l_; S.sgm[tid - T_LS] = expf(l_); }
     if constexpr (!SINGLE)
     {   // ---- (shadow of x3) Grams of x2 and x1 (S.x1 stays valid until the next step's gather).  Two butterflies, ONE pass through LDS
         // and its two barriers: out[0..29] = [x2: net][10], out[32..61] = [x1: net][10]
@@ -917,7 +562,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       // producer are not there yet, the polling gather below continues after the head words have been taken
       u32x4 w3[2];
 #pragma unroll
-      for (int i = 0; i < 2; ++i) w3[i] = __builtin_amdgcn_raw_buffer_load_b128(LQ, (LQ_X3 + tid + i * NTH) * 16u, 0, 16);
+      for (int i = 0; i < 2; ++i) w3[i] = load16(LQ, LQ_X3 + tid + i * NTH);
       if (step != 0) {
         u64 ww[HR][4];
         const u64 absent = (u64)tag_prev << 32;        // rows past the 25 head rows: value 0 with the expected tag
@@ -947,8 +592,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       if (__builtin_amdgcn_ballot_w64(!(lq_ok(w3[0], tag) && lq_ok(w3[1], tag))) != 0) {
         if (!lq_gather<2>(LQ, LQ_X3 + tid, NTH, tag, v0, v1, v2, failflag)) S.fail = 1;
       }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) { (&S.x3[0][0][0])[tid + NTH * j] = v0[j]; (&S.x3[1][0][0])[tid + NTH * j] = v1[j]; (&S.x3[2][0][0])[tid + NTH * j] = v2[j]; }
+      image_store(S.x3, v0, v1, v2, tid);
     }
     if (!row_done) {
 #pragma unroll
@@ -1024,7 +668,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
 #pragma unroll
         for (int j = 0; j < HR; ++j) {
           const int row = wave + 8 * j;
-          if (row < A + 2) { const float y = u[j] + S.bias[21 + row]; if (row < A) S.mu[lane][row] = y; else S.val[row - A][lane] = y; }
+          if (row < A + 2) { const float y = u[j] + S.bias[BIAS_HEAD + row]; if (row < A) S.mu[lane][row] = y; else S.val[row - A][lane] = y; }
         }
       }
     }
@@ -1085,7 +729,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
           } else { closs[j] = c1v; d = 2.0f * (v - R); }
           S.dv[j][s] = (j == 0 ? 0.5f * D.critic_coef : 1.0f) * d * invM;
         }
-        S.stat[s][1] = fmaxf(L1, L2); S.stat[s][2] = closs[0]; S.stat[s][5] = closs[1];
+        S.stat[s][STAT_ACTOR] = fmaxf(L1, L2); S.stat[s][STAT_CRITIC] = closs[0]; S.stat[s][STAT_CV] = closs[1];
       }
     }
     SDX_LDS_BARRIER();   // LDS traffic only: the column view's loads stay in flight (a __syncthreads() would wait for them)
@@ -1100,8 +744,8 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       }
       S.dmu[s][a] = dmu;
     }
-    if (tid >= 128 && tid < 128 + 32) {
-      const int a = tid - 128;
+    if (tid >= T_LS && tid < T_LS + 32) {
+      const int a = tid - T_LS;
       float dls = 0.0f;
       if (a < A) for (int s = 0; s < MB; ++s) dls += S.gnlp[s] * (1.0f - S.z[s][a] * S.z[s][a]) * invM;
       S.dls[a] = dls;
@@ -1116,7 +760,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     // would run both sides of.
     // (no barriers here: the two that let the halves meet in S.dy2 ordered nothing else - S.dmu / S.dv / S.x3 were published by the barriers
     // of the loss phase, and the last readers of S.red / S.part, in the x3 shadow, are behind the barriers of the head forward.  The S.dy2
-    // stores below sit in front of block_sum's barriers, their readers - the Gram of dY2, dyown[.][.][6], the next step's Adam of layer 2 -
+    // stores below sit in front of block_sum's barriers, their readers - the Gram of dY2, dyown[.][.][DY_L2], the next step's Adam of layer 2 -
     // behind them.)
     float d2[3][MB];
     {
@@ -1175,7 +819,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
 #pragma unroll
           for (int w = 0; w < NWV; ++w) { t += S.red[4 * w + 2 * bc][bi]; t += S.red[4 * w + 2 * bc + 1][bi]; }   // rows 16 j .. 16 j + 15 of the column, j ascending
           v = t * eg;
-          S.dyown[bnet][bs][4 + bc] = v;
+          S.dyown[bnet][bs][DY_L1 + bc] = v;
         }
         const float v1 = dpp_mov<0x108, 0xF>(0.0f, v);                                        // row_shl:8: lane l + 8
         const unsigned y = __builtin_bit_cast(unsigned, v);
@@ -1183,7 +827,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
         const float v2 = __builtin_bit_cast(float, (unsigned)r[1]);
         if (tid < MB * 2) lq_store(LQ, LQ_DY1 + (unsigned)(tid >> 1) * U1 + 2 * g + (tid & 1), v, v1, v2, tag);
       }
-      // (the reduction's closing barrier - S.red read out before its next writer, S.dyown[.][.][4..5] published - stands in the dY1 shadow, in front
+      // (the reduction's closing barrier - S.red read out before its next writer, S.dyown[.][.][DY_L1 ..] published - stands in the dY1 shadow, in front
       // of that shadow's rows_store: the other waves form their parts of the shadow while wave 0 adds and publishes.  One minibatch: the barrier in
       // front of its statistics thread.)
     }
@@ -1209,27 +853,27 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
         r_ent = 0.5f + 0.5f * 1.8378770664093453f + ls;
       }
       r_kl = half_sum(r_kl); r_bl = half_sum(r_bl); r_ent = half_sum(r_ent);
-      if (a == 31) { S.stat[s][3] = r_bl; S.stat[s][4] = r_kl; S.stat[s][6] = r_ent; }
+      if (a == 31) { S.stat[s][STAT_BOUNDS] = r_bl; S.stat[s][STAT_KL] = r_kl; S.stat[s][STAT_ENTROPY] = r_ent; }
     }
-    if (tid == 384) {   // what does not wait for the KL stays in front of the barrier
+    if (tid == T_STATS) {   // what does not wait for the KL stays in front of the barrier
       PLds::Ctl& C = S.ctl;
       C.ac_lr_applied = C.ac_lr;   // the optimiser step of THIS minibatch uses the current lr; the schedule moves it afterwards
       if constexpr (!SINGLE) {
         // Adam step counters / bias corrections of the optimiser step that applies THIS minibatch's gradient (phase A of the next
         // iteration): nothing here depends on the gradient, so it left the chain (round 6; the double-precision powers and the two
-        // divisions sat between the norm and the first Adam instruction).  S.scal[2..5] were last read by the Adam shadows of this
+        // divisions sat between the norm and the first Adam instruction).  S.scal[SC_AC_LR_BC1 ..] were last read by the Adam shadows of this
         // iteration, which every wave finished before the barrier in front of phase C
         C.ac_t += 1; C.cv_t += 1;
         C.ac_b1 *= 0.9; C.ac_b2 *= 0.999; C.cv_b1 *= 0.9; C.cv_b2 *= 0.999;
-        S.scal[2] = C.ac_lr_applied / (float)(1.0 - C.ac_b1); S.scal[3] = 1.0f / sqrtf((float)(1.0 - C.ac_b2));
-        S.scal[4] = C.cv_lr / (float)(1.0 - C.cv_b1); S.scal[5] = 1.0f / sqrtf((float)(1.0 - C.cv_b2));
+        S.scal[SC_AC_LR_BC1] = C.ac_lr_applied / (float)(1.0 - C.ac_b1); S.scal[SC_AC_ISQ] = 1.0f / sqrtf((float)(1.0 - C.ac_b2));
+        S.scal[SC_CV_LR_BC1] = C.cv_lr / (float)(1.0 - C.cv_b1); S.scal[SC_CV_ISQ] = 1.0f / sqrtf((float)(1.0 - C.cv_b2));
       }
     }
     auto stats_and_lr = [&]() {
-    if (tid == 384) {
+    if (tid == T_STATS) {
       PLds::Ctl& C = S.ctl;
       float t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0, t6 = 0;
-      for (int s = 0; s < MB; ++s) { t1 += S.stat[s][1]; t2 += S.stat[s][2]; t3 += S.stat[s][3]; t4 += S.stat[s][4]; t5 += S.stat[s][5]; t6 += S.stat[s][6]; }
+      for (int s = 0; s < MB; ++s) { t1 += S.stat[s][STAT_ACTOR]; t2 += S.stat[s][STAT_CRITIC]; t3 += S.stat[s][STAT_BOUNDS]; t4 += S.stat[s][STAT_KL]; t5 += S.stat[s][STAT_CV]; t6 += S.stat[s][STAT_ENTROPY]; }
       const float kl = t4 * invM;
       C.sum_a += t1 * invM; C.sum_c += t2 * invM; C.sum_b += t3 * invM; C.sum_kl += kl; C.sum_cv += t5 * invM; C.sum_ent += t6 * invM;
       C.last_kl = kl;
@@ -1247,22 +891,22 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     if constexpr (!SINGLE) {
       // Round 6: the Gram of x3 (waves 0..3, unit = tid) and the Gram of dY2 (waves 4..7, unit = tid - 256; it used to wait for the dY0 shadow, whose
       // block reduction is on the chain since the norm edge shrank) go through ONE pass: columns 0..29 / 32..61, each summed over its 16 rows.
-      // The heads' terms are only STORED here (S.part[128..], [192..]); the serial sums that closed this shadow (16 + 23 dependent LDS reads on
+      // The heads' terms are only STORED here (S.part[PART_HEAD_G ..], [PART_HEAD_B ..]); the serial sums that closed this shadow (16 + 23 dependent LDS reads on
       // three threads, about 1 us after the reduction) are lanes of the DPP sum at the end of the dY0 shadow now.
       float p[30];
 #pragma unroll
       for (int i = 0; i < 30; ++i) p[i] = 0.0f;
-      if (tid >= 256 && tid < 256 + 48) {              // thread (net, a, b): the heads' gradient product that multiplies G_x3[a][b]
-        const int t = tid - 256, net = t / 16, a = (t / 4) % 4, b = t % 4;
+      if (tid >= T_HEAD_G && tid < T_HEAD_G + 48) {    // thread (net, a, b): the heads' gradient product that multiplies G_x3[a][b]
+        const int t = tid - T_HEAD_G, net = t / 16, a = (t / 4) % 4, b = t % 4;
         float dd = 0.0f;
         if (net == 0) { for (int j = 0; j < A; ++j) dd += S.dmu[a][j] * S.dmu[b][j]; }
         else dd = S.dv[net - 1][a] * S.dv[net - 1][b];
-        S.part[128 + t] = dd;
-      } else if (tid >= 320 && tid < 320 + 32) {       // bias of the policy head and logstd: |sum_s dmu_s[j]|^2 + dlogstd[j]^2
-        const int j = tid - 320;
+        S.part[PART_HEAD_G + t] = dd;
+      } else if (tid >= T_HEAD_B && tid < T_HEAD_B + 32) {   // bias of the policy head and logstd: |sum_s dmu_s[j]|^2 + dlogstd[j]^2
+        const int j = tid - T_HEAD_B;
         float t = 0.0f;
         if (j < A) { float sb = 0; for (int a = 0; a < MB; ++a) sb += S.dmu[a][j]; t = sb * sb + S.dls[j] * S.dls[j]; }
-        S.part[192 + j] = t;
+        S.part[PART_HEAD_B + j] = t;
       }
       if (tid < U2) {
 #pragma unroll
@@ -1294,7 +938,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       }
       // first look at this lane's dY1 words (the polling gather of phase E takes over if a producer is late)
       lq_peek<4>(LQ, LQ_DY1 + tid, NTH, pdy1); pdy1_issued = true;
-      stats_and_lr();                                  // thread 384, beside the column sums of threads 0..63 and behind its wave's first look; its readers sit behind the barrier below
+      stats_and_lr();                                  // thread T_STATS, beside the column sums of threads 0..63 and behind its wave's first look; its readers sit behind the barrier below
       SDX_LDS_BARRIER();
     }
     TS(15)
@@ -1306,7 +950,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       float p[48];
       {
         float v0[4], v1[4], v2[4];
-        if (!(pdy1_issued && lq_take<4>(pdy1, tag, v0, v1, v2)) && !lq_gather<4>(LQ, LQ_DY1 + tid, NTH, tag, v0, v1, v2, failflag)) S.fail = 1;
+        lq_take_or_gather<4>(pdy1_issued, pdy1, LQ, LQ_DY1 + tid, NTH, tag, v0, v1, v2, failflag, S.fail);
         TS(16)
 #pragma unroll
         for (int s = 0; s < MB; ++s)
@@ -1314,8 +958,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
           for (int c = 0; c < 4; ++c) {
             p[(0 * MB + s) * 4 + c] = v0[s] * c1[0][c]; p[(1 * MB + s) * 4 + c] = v1[s] * c1[1][c]; p[(2 * MB + s) * 4 + c] = v2[s] * c1[2][c];
           }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { (&S.dy1[0][0][0])[tid + NTH * j] = v0[j]; (&S.dy1[1][0][0])[tid + NTH * j] = v1[j]; (&S.dy1[2][0][0])[tid + NTH * j] = v2[j]; }
+        image_store(S.dy1, v0, v1, v2, tid);
       }
       // (no barrier here on the epoch's chain: the one that stood between the S.dy1 stores and their read-back also kept block_sum's stores to
       // S.red / S.part behind the dY1 shadow's readers of both - the LDS barrier that closes that shadow does that - and the S.dy1 stores in
@@ -1340,7 +983,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
 #pragma unroll
           for (int w = 0; w < 4 * NWV; ++w) t += S.red[w][tid];
           v = t * eg;
-          S.dyown[enet][es][ec] = v;
+          S.dyown[enet][es][DY_L0 + ec] = v;
         }
         if constexpr (SINGLE) {
           const unsigned y = __builtin_bit_cast(unsigned, v);
@@ -1366,16 +1009,12 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
             for (int net = 0; net < 3; ++net) {
               float gg = 0.0f;
 #pragma unroll
-              for (int c = 0; c < 4; ++c) gg += S.dyown[net][hi][c] * S.dyown[net][lo][c];
+              for (int c = 0; c < 4; ++c) gg += S.dyown[net][hi][DY_L0 + c] * S.dyown[net][lo][DY_L0 + c];
               t[net] = gg * S.gx[net][0][lane] + gg;
             }
           }
 #pragma unroll
-          for (int net = 0; net < 3; ++net) {
-            float x = t[net];
-            x = dpp_add<0xB1, 0xF>(x); x = dpp_add<0x4E, 0xF>(x); x = dpp_add<0x141, 0xF>(x); x = dpp_add<0x140, 0xF>(x);   // 16-lane row sums
-            t[net] = x;
-          }
+          for (int net = 0; net < 3; ++net) t[net] = row_sum16(t[net]);
           if (lane == 0) lq_store(LQ, LQ_G0 + g, t[0], t[1], t[2], tag);
         }
         // (the reduction's second barrier stands in the dY0 shadow, in front of its rows_store: the other waves form their Gram terms meanwhile)
@@ -1435,7 +1074,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
 #pragma unroll
         for (int net = 0; net < 3; ++net) gram_acc10(&p[net * 10], S.dy1[net][0][tid], S.dy1[net][1][tid], S.dy1[net][2][tid], S.dy1[net][3][tid]);
         row_butterfly<30>(p, ua, lane);
-        SDX_LDS_BARRIER();   // backward L1's second barrier: wave 0 has read S.red out and published, S.dyown[.][.][0..3] is there for what follows
+        SDX_LDS_BARRIER();   // backward L1's second barrier: wave 0 has read S.red out and published, S.dyown[.][.][DY_L0 ..] is there for what follows
         rows_store<8>(S, ua, 0, wave, lane);
       }
       SDX_LDS_BARRIER();          // (rows_reduce, opened up: the stage between its two barriers occupies 32 threads ...)
@@ -1446,12 +1085,12 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
         for (int w = 0; w < 4 * NWV; ++w) t += S.red[w][tid];
         S.part[tid] = t;
       }
-      // ... so this lane's layer-0 gradient elements are formed here, by every wave (dyown[.][.][0..3] were published by the barrier above;
+      // ... so this lane's layer-0 gradient elements are formed here, by every wave (dyown[.][.][DY_L0 ..] were published by the barrier above;
       // S.obs / S.cvx still hold this minibatch): 4 + 5 batches of four independent LDS loads instead of 13 dependent round trips on the chain
       {
         float da[MB], dc[MB], dvv[MB];
 #pragma unroll
-        for (int s = 0; s < MB; ++s) { da[s] = S.dyown[0][s][r0w]; dc[s] = S.dyown[1][s][r0w]; dvv[s] = S.dyown[2][s][r0w]; }
+        for (int s = 0; s < MB; ++s) { da[s] = S.dyown[0][s][DY_L0 + r0w]; dc[s] = S.dyown[1][s][DY_L0 + r0w]; dvv[s] = S.dyown[2][s][DY_L0 + r0w]; }
 #pragma unroll
         for (int i = 0; i < I0A; ++i) {
           const int kk = lane + 64 * i, k = h0 * H0A + kk;
@@ -1479,18 +1118,18 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       if (step + 1 < total_steps) { const bool wrap = mbi + 1 >= D.num_minibatches; load_rows(wrap ? 0 : mbi + 1, mini_epoch + (wrap ? 1 : 0)); }
       if (wave == 1) {
         // lane (net, i) < 48: entry i of the Grams of dY1 / dY2 against (G_x1 / G_x2 + 1) - weight and bias gradients of trunk layers 1, 2 -, of the
-        // Gram of x3 against the heads' gradient products (S.part[128..], dY1 shadow), + the head-bias / logstd terms (32 entries over the 16 lanes
+        // Gram of x3 against the heads' gradient products (S.part[PART_HEAD_G ..], dY1 shadow), + the head-bias / logstd terms (32 entries over the 16 lanes
         // of net 0; |sum_s dV_s|^2 on lane 0 of nets 1, 2); a DPP row sum per network
         float t = 0.0f;
         if (lane < 48) {
           const int net = lane >> 4, i = lane & 15;
-          t = S.part[net * 10 + tri16(i)] * (S.gx[net][1][i] + 1.0f) + S.gd2[net][i] * (S.gx[net][2][i] + 1.0f) + S.gx[net][3][i] * S.part[128 + net * 16 + i];
-          if (net == 0) t += S.part[192 + i] + S.part[208 + i];
+          t = S.part[net * 10 + tri16(i)] * (S.gx[net][1][i] + 1.0f) + S.gd2[net][i] * (S.gx[net][2][i] + 1.0f) + S.gx[net][3][i] * S.part[PART_HEAD_G + net * 16 + i];
+          if (net == 0) t += S.part[PART_HEAD_B + i] + S.part[PART_HEAD_B + 16 + i];
           else if (i == 0) { float sb = 0.0f; for (int a = 0; a < MB; ++a) sb += S.dv[net - 1][a]; t += sb * sb; }
         }
-        t = dpp_add<0xB1, 0xF>(t); t = dpp_add<0x4E, 0xF>(t); t = dpp_add<0x141, 0xF>(t); t = dpp_add<0x140, 0xF>(t);   // 16-lane row sums
+        t = row_sum16(t);
         if (lane < 48 && (lane & 15) == 0) S.n2rest[lane >> 4] = t;
-      } else if (tid >= 128 && tid < 128 + 3 * MB) { const int net = (tid - 128) / MB, s = (tid - 128) % MB; S.dyown[net][s][6] = S.dy2[net][s][g]; }
+      } else if (tid >= 128 && tid < 128 + 3 * MB) { const int net = (tid - 128) / MB, s = (tid - 128) % MB; S.dyown[net][s][DY_L2] = S.dy2[net][s][g]; }
     }
     TS(18)
     pending = true;
@@ -1503,7 +1142,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
   for (int i = 0; i < I0A; ++i) {
     const int kk = lane + 64 * i, k = h0 * H0A + kk;
     if (kk < H0A && k < D.obs_dim) {
-      const size_t oa = woff(0, 0) + (size_t)n0 * D.obs_dim + k, oc = woff(1, 0) + (size_t)n0 * D.obs_dim + k;
+      const size_t oa = o_w0(0, k), oc = o_w0(1, k);
       D.ac[oa] = w0a[i]; D.ac_m[oa] = m0a[i]; D.ac_v[oa] = v0a[i];
       D.ac[oc] = w0c[i]; D.ac_m[oc] = m0c[i]; D.ac_v[oc] = v0c[i];
     }
@@ -1517,7 +1156,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
   for (int net = 0; net < 3; ++net) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const size_t o = woff(net, 1) + (size_t)r1 * U0 + q1 * 256 + lane + 64 * i;
+      const size_t o = o_w1(net, i);
       P_of(net)[o] = w1[net][i]; M_of(net)[o] = m1[net][i]; V_of(net)[o] = v1[net][i];
     }
     {
@@ -1527,17 +1166,17 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
   }
   if (tid < HPC) {
     const int net = head_net(hrow);
-    const size_t o = head_woff(hrow) + hk;
+    const size_t o = o_hw();
     P_of(net)[o] = hw; M_of(net)[o] = hm; V_of(net)[o] = hv;
   }
-  if (g == 0) {
-    if (tid >= 21 && tid < 21 + A + 2) {
-      const int row = tid - 21, net = head_net(row);
-      const size_t o = head_boff(row);
-      P_of(net)[o] = S.bias[tid]; M_of(net)[o] = S.bias_m[tid]; V_of(net)[o] = S.bias_v[tid];
+  auto bias_store = [&](int net, size_t o) { P_of(net)[o] = S.bias[tid]; M_of(net)[o] = S.bias_m[tid]; V_of(net)[o] = S.bias_v[tid]; };
+  if (g == 0) {   // head biases and logstd are replicated on every CU: CU 0 writes them
+    if (tid >= BIAS_HEAD && tid < BIAS_HEAD + A + 2) {
+      const int row = tid - BIAS_HEAD;
+      bias_store(head_net(row), head_boff(row));
     }
-    if (tid >= 64 && tid < 64 + A) {
-      const int a = tid - 64;
+    if (tid >= T_LOGSTD && tid < T_LOGSTD + A) {
+      const int a = tid - T_LOGSTD;
       const size_t o = D.off.logstd + a;
       D.ac[o] = s_b2[0][a]; D.ac_m[o] = s_b2[1][a]; D.ac_v[o] = s_b2[2][a];
     }
@@ -1552,76 +1191,11 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       gctl->ll_tag = tag_base + (unsigned)total_steps + 2u;
     }
   }
-  if (tid < 12) {
-    const int net = tid / 4, w = tid % 4;
-    const size_t o = boff(net, 0) + 4 * g + w;
-    P_of(net)[o] = S.bias[tid]; M_of(net)[o] = S.bias_m[tid]; V_of(net)[o] = S.bias_v[tid];
-  } else if (tid < 18) {
-    const int net = (tid - 12) / 2, r = (tid - 12) % 2;
-    const size_t o = boff(net, 1) + 2 * g + r;
-    P_of(net)[o] = S.bias[tid]; M_of(net)[o] = S.bias_m[tid]; V_of(net)[o] = S.bias_v[tid];
-  } else if (tid < 21) {
-    const int net = tid - 18;
-    const size_t o = boff(net, 2) + g;
-    P_of(net)[o] = S.bias[tid]; M_of(net)[o] = S.bias_m[tid]; V_of(net)[o] = S.bias_v[tid];
-  }
+  if (tid < BIAS_L1) { const int net = (tid - BIAS_L0) / 4, w = (tid - BIAS_L0) % 4; bias_store(net, boff(net, 0) + 4 * g + w); }
+  else if (tid < BIAS_L2) { const int net = (tid - BIAS_L1) / 2, r = (tid - BIAS_L1) % 2; bias_store(net, boff(net, 1) + 2 * g + r); }
+  else if (tid < BIAS_HEAD) { const int net = tid - BIAS_L2; bias_store(net, boff(net, 2) + g); }
 }
 
-// Test entry (tests/test_gpu_wave_sums.py): one workgroup of NTH threads, in / ref / got are [N][NTH].  ref[i][t] = wave_sum of value i in t's
-// wave, on every lane; got[i][t] = what wave_sums<N> left in lane t for value i - written by the lanes with (t & 3) == (i & 3), the others'
-// slots are not touched.
-template <int N>
-__global__ __launch_bounds__(NTH) void k_wave_sums_check(const float* in, float* ref, float* got) {
-  const int tid = threadIdx.x, lane = tid & 63;
-  float v[N], u[(N + 3) / 4];
-#pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = in[i * NTH + tid];
-#pragma unroll
-  for (int i = 0; i < N; ++i) ref[i * NTH + tid] = wave_sum(v[i]);
-  wave_sums<N>(v, u, lane);
-#pragma unroll
-  for (int j = 0; j < (N + 3) / 4; ++j) got[(4 * j + (lane & 3)) * NTH + tid] = u[j];
-}
-extern "C" int sdxpk_wave_sums_check(const float* in, float* ref, float* got, int n, hipStream_t st) {
-  if (n == 12) hipLaunchKernelGGL(k_wave_sums_check<12>, dim3(1), dim3(NTH), 0, st, in, ref, got);
-  else if (n == 16) hipLaunchKernelGGL(k_wave_sums_check<16>, dim3(1), dim3(NTH), 0, st, in, ref, got);
-  else return -1;
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-// Test entry (tests/test_gpu_fwd2_sums.py): one workgroup of NTH threads, w is [3][NTH], x [3][MB][NTH], ref / got [3 MB][NTH], value
-// net MB + s.  ref[i][t] = the tree forward L2 used to run for value i in t's wave, written serially: the explicit fma first level, the
-// five dpp_add levels of wave_sum, lane 63.  got[i][t] = what fwd2_sums left in lane t for value i - written by the 32 lanes of a wave that hold
-// sample i % MB (fwd2_sample, the eight useful lanes of every DPP row), the others' slots are not touched.
-__global__ __launch_bounds__(NTH) void k_fwd2_sums_check(const float* w, const float* x, float* ref, float* got) {
-  const int tid = threadIdx.x, lane = tid & 63;
-  float wv[3], xv[3][MB], u[3];
-#pragma unroll
-  for (int net = 0; net < 3; ++net) {
-    wv[net] = w[net * NTH + tid];
-#pragma unroll
-    for (int s = 0; s < MB; ++s) xv[net][s] = x[(net * MB + s) * NTH + tid];
-  }
-#pragma unroll
-  for (int net = 0; net < 3; ++net)
-#pragma unroll
-    for (int s = 0; s < MB; ++s) {
-      float t = wv[net] * xv[net][s];
-      asm volatile("" : "+v"(t));
-      float v = __builtin_fmaf(wv[net], xv[net][s], dpp_mov<0xB1, 0xF>(0.0f, t));
-      v = dpp_add<0x4E, 0xF>(v); v = dpp_add<0x141, 0xF>(v); v = dpp_add<0x140, 0xF>(v); v = dpp_add<0x142, 0xA>(v); v = dpp_add<0x143, 0xC>(v);
-      ref[(net * MB + s) * NTH + tid] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-    }
-  fwd2_sums(wv, xv, u, lane);
-  if ((0xA5A5 >> (lane & 15)) & 1) {
-    const int s = fwd2_sample(lane);
-#pragma unroll
-    for (int net = 0; net < 3; ++net) got[(net * MB + s) * NTH + tid] = u[net];
-  }
-}
-extern "C" int sdxpk_fwd2_sums_check(const float* w, const float* x, float* ref, float* got, hipStream_t st) {
-  hipLaunchKernelGGL(k_fwd2_sums_check, dim3(1), dim3(NTH), 0, st, w, x, ref, got);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
-}
 extern "C" size_t sdxpk_persist_lds_bytes() { return sizeof(PLds); }
 extern "C" int sdxpk_persist_supported(const SdxpDev* D, int minibatch, int n_cus) {
   return minibatch == MB && D->obs_dim <= OBS && D->obs_dim % 4 == 0 && D->state_dim == ST && D->units[0] == U0 && D->units[1] == U1 &&

@@ -1,0 +1,164 @@
+// sdxp_persist_sums.h - private to the persistent PPO update (included by sdxp_persist.hip and sdxp_persist_checks.hip only): the cross-lane and
+// cross-wave sums of k_update_persistent - DPP row sums, the halving butterflies that form N wave sums at once with the bits of N wave_sum
+// trees, the workgroup reduction through PLds::red, and the 4x4 Gram accumulators
+#pragma once
+#include "sdxp_device.h"   // sdx_common.h, dpp_add, wave_sum
+#include "sdxp_persist_lds.h"
+
+namespace {
+// v + (the value of lane ^ 32), in both lanes: v_permlane32_swap_b32 of v with itself leaves the lower half's values in one result and the
+// upper half's in the other
+__device__ __forceinline__ float pair_sum(float v) {
+  const unsigned u = __builtin_bit_cast(unsigned, v);
+  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+  return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
+}
+// accumulate the 4x4 Gram (lower triangle, 10 terms) of (a, b, c, d) ...
+__device__ __forceinline__ void gram_acc10(float* p, float a, float b, float c, float d) {
+  p[0] += a * a; p[1] += b * a; p[2] += b * b; p[3] += c * a; p[4] += c * b; p[5] += c * c;
+  p[6] += d * a; p[7] += d * b; p[8] += d * c; p[9] += d * d;
+}
+// ... and |sum|^2 (the bias term)
+__device__ __forceinline__ void gram_acc(float* p, float a, float b, float c, float d) {
+  gram_acc10(p, a, b, c, d);
+  const float sb = a + b + c + d;
+  p[10] += sb * sb;
+}
+__device__ __forceinline__ int tri16(int i) { const int a = i >> 2, b = i & 3, hi = a > b ? a : b, lo = a > b ? b : a; return hi * (hi + 1) / 2 + lo; }
+// sums over each 16-lane DPP row, in every lane of the row: the first four levels of wave_sum (quad_perm, quad_perm, row_half_mirror, row_mirror)
+__device__ __forceinline__ float row_sum16(float v) {
+  v = dpp_add<0xB1, 0xF>(v); v = dpp_add<0x4E, 0xF>(v); v = dpp_add<0x141, 0xF>(v); v = dpp_add<0x140, 0xF>(v);
+  return v;
+}
+// sums over each 32-lane half of the wave; valid in lanes 16..31 and 48..63
+__device__ __forceinline__ float half_sum(float v) { return dpp_add<0x142, 0xA>(row_sum16(v)); }
+template <int CTRL, int BANK>
+__device__ __forceinline__ float dpp_mov(float old, float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v), CTRL, 0xF, BANK, false));
+}
+// the two halving levels + the two levels inside the 16-lane DPP row: u2[j] = sum over the row's lanes of value 4 j + (lane & 3)
+template <int N>
+__device__ __forceinline__ void row_butterfly(const float (&v)[N], float (&u2)[(N + 3) / 4], int lane) {
+  constexpr int N4 = (N + 3) / 4;
+  const bool b0 = lane & 1, b1 = lane & 2;
+  float u1[2 * N4];
+#pragma unroll
+  for (int j = 0; j < 2 * N4; ++j) {
+    const float e = 2 * j < N ? v[2 * j] : 0.0f, o = 2 * j + 1 < N ? v[2 * j + 1] : 0.0f;
+    const float keep = b0 ? o : e, send = b0 ? e : o;
+    u1[j] = keep + dpp_mov<0xB1, 0xF>(0.0f, send);           // partner lane ^ 1
+  }
+#pragma unroll
+  for (int j = 0; j < N4; ++j) {
+    const float keep = b1 ? u1[2 * j + 1] : u1[2 * j], send = b1 ? u1[2 * j] : u1[2 * j + 1];
+    float t = keep + dpp_mov<0x4E, 0xF>(0.0f, send);         // partner lane ^ 2: t = quad sum of value 4 j + (lane & 3)
+    float x = dpp_mov<0x114, 0xA>(0.0f, t);                  // lane ^ 4: row_shr:4 into banks 1,3 ...
+    x = dpp_mov<0x104, 0x5>(x, t);                           // ... row_shl:4 into banks 0,2
+    t += x;
+    t += dpp_mov<0x128, 0xF>(0.0f, t);                       // lane ^ 8 (row_ror:8): sum over the 16-lane row
+    u2[j] = t;
+  }
+}
+// N wave sums at once: the row butterfly, then the rows meet through v_permlane16_swap (partner lane ^ 16: rows 0 + 1, 2 + 3) and
+// v_permlane32_swap (lane ^ 32).  Every lane ends with u[j] = the whole wave's sum of value 4 j + (lane & 3).  The pairs of the six levels
+// are those of wave_sum's DPP tree (quad_perm, quad_perm, row_half_mirror, row_mirror, row_bcast15, row_bcast31) and IEEE addition
+// commutes, so u[j] equals wave_sum(v[4 j + (lane & 3)]) bit for bit - at N / 2, N / 4, N / 4, ... adds per level instead of N.
+template <int N>
+__device__ __forceinline__ void wave_sums(const float (&v)[N], float (&u)[(N + 3) / 4], int lane) {
+  // (opaque copies: the sums are those of the ROUNDED values - a value that is a bare product must not be contracted with the butterfly's first
+  // add into an fma, through the level's select.  wave_sum of a bare product IS contracted that way, per lane: forward L2, whose values are
+  // bare products, has a butterfly of its own - fwd2_sums below.)
+  float t[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) { t[i] = v[i]; asm("" : "+v"(t[i])); }
+  row_butterfly<N>(t, u, lane);
+#pragma unroll
+  for (int j = 0; j < (N + 3) / 4; ++j) {
+    const unsigned x = __builtin_bit_cast(unsigned, u[j]);
+    const auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+    u[j] = pair_sum(__builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]));
+  }
+}
+// Forward L2: the wave sums of the twelve BARE products w[net] x[net][s], with the bits of twelve wave_sum trees.  wave_sum(w x) compiles to
+// v_mul (the rounded product) / v_mov_dpp quad_perm:[1,0,3,2] / v_fmac: lane l holds fma(w_l, x_l, rounded product of lane l ^ 1), so the two
+// lanes of a pair hold different bits, and of a DPP row only the lanes whose view the rest of the tree carries to lane 63 count - 15, 13, 8,
+// 10, 0, 2, 7, 5: row sum = ((v15 + v13) + (v8 + v10)) + ((v0 + v2) + (v7 + v5)), wave sum = (r3 + r2) + (r1 + r0).  Here the first level is
+// written out - on every lane, twelve independent fmas, the product through an opaque copy so that it stays rounded - and the other levels run
+// as a halving butterfly over exactly those pairs: partner l ^ 2 (the lanes with bit 0 == bit 1 keep samples 0 and 3, the others 1 and 2),
+// row_half_mirror (bit 2 == bit 3 keeps the first of the two), row_mirror, then the rows as in wave_sums.  Addition commutes, pairing does
+// not.  Lanes 0, 2, 5, 7 (and their mirrors 15, 13, 10, 8) of every row end with u[net] = the wave's sum of sample 0, 1, 2, 3: lanes 1 and 3
+// are not on the tree's path, so the storing lanes are not 0..3 (fwd2_sample, fwd2_store).
+__device__ __forceinline__ int fwd2_sample(int lane) {
+  const bool ka = (((lane >> 1) ^ lane) & 1) == 0, kf = (((lane >> 3) ^ (lane >> 2)) & 1) == 0;
+  return kf ? (ka ? 0 : 1) : (ka ? 3 : 2);
+}
+__device__ __forceinline__ void fwd2_sums(const float (&w)[3], const float (&x)[3][4], float (&u)[3], int lane) {
+  const bool ka = (((lane >> 1) ^ lane) & 1) == 0, kf = (((lane >> 3) ^ (lane >> 2)) & 1) == 0;
+  float v[3][4];
+#pragma unroll
+  for (int net = 0; net < 3; ++net)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      float t = w[net] * x[net][s];
+      asm("" : "+v"(t));
+      v[net][s] = __builtin_fmaf(w[net], x[net][s], dpp_mov<0xB1, 0xF>(0.0f, t));   // partner lane ^ 1
+    }
+#pragma unroll
+  for (int net = 0; net < 3; ++net) {
+    const float k0 = ka ? v[net][0] : v[net][1], s0 = ka ? v[net][1] : v[net][0];
+    const float k1 = ka ? v[net][3] : v[net][2], s1 = ka ? v[net][2] : v[net][3];
+    const float a = k0 + dpp_mov<0x4E, 0xF>(0.0f, s0), b = k1 + dpp_mov<0x4E, 0xF>(0.0f, s1);   // partner lane ^ 2
+    float t = (kf ? a : b) + dpp_mov<0x141, 0xF>(0.0f, kf ? b : a);                              // row_half_mirror: lane ^ 7
+    t += dpp_mov<0x140, 0xF>(0.0f, t);                                                           // row_mirror: lane ^ 15
+    const unsigned y = __builtin_bit_cast(unsigned, t);
+    const auto r = __builtin_amdgcn_permlane16_swap(y, y, false, false);
+    u[net] = pair_sum(__builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]));
+  }
+}
+// the forward passes' partial dot products, value net MB + s: lane s < MB holds u[net] = this wave's sum of (net, sample s)
+static_assert(MB == 4, "lane & 3 of wave_sums is the sample");
+__device__ __forceinline__ void fpart_store(PLds& S, const float (&u)[3], int wave, int lane) {
+  if (lane < MB) {
+#pragma unroll
+    for (int net = 0; net < 3; ++net) S.fpart[(net * MB + lane) * NWV + wave] = u[net];
+  }
+}
+// the same slots from fwd2_sums: lanes 0, 2, 5, 7 hold samples 0, 1, 2, 3
+__device__ __forceinline__ void fwd2_store(PLds& S, const float (&u)[3], int wave, int lane) {
+  if (lane < 8 && ((0xA5 >> lane) & 1)) {
+    const int s = fwd2_sample(lane);
+#pragma unroll
+    for (int net = 0; net < 3; ++net) S.fpart[(net * MB + s) * NWV + wave] = u[net];
+  }
+}
+template <int N4>
+__device__ __forceinline__ void rows_store(PLds& S, const float (&u2)[N4], int off, int wave, int lane) {
+  if ((lane & 15) < 4) {
+    float* r = S.red[wave * 4 + (lane >> 4)] + off;
+#pragma unroll
+    for (int j = 0; j < N4; ++j) r[4 * j + (lane & 3)] = u2[j];
+  }
+}
+// LDS-only barriers (sdx_common.h): __syncthreads() also waits for the wave's outstanding global accesses - in the shadows that is the
+// acknowledgement of the exchange words just published and the next minibatch's prefetched rows; nothing here is ordered through HBM
+__device__ __forceinline__ void rows_reduce(PLds& S, int n, float* out, int tid) {
+  SDX_LDS_BARRIER();
+  if (tid < n) {
+    float t = 0.0f;
+#pragma unroll
+    for (int w = 0; w < 4 * NWV; ++w) t += S.red[w][tid];
+    out[tid] = t;
+  }
+  SDX_LDS_BARRIER();
+}
+// block-wide sums of N per-thread values (N <= 64); result in out[0..N).  Two "halving" butterfly levels (lane pairs keep the even /
+// odd half of the values, so level L costs N / 2^L exchanges instead of N), two more within the 16-lane DPP row, and the 4 rows x 8
+// waves meet in LDS: ~3.5 N VALU ops + N/4 LDS writes per wave instead of 7 N + N masked writes for N independent wave sums.
+template <int N>
+__device__ __forceinline__ void block_sum(PLds& S, const float (&v)[N], float* out, int tid, int wave, int lane) {
+  float u2[(N + 3) / 4];
+  row_butterfly<N>(v, u2, lane);
+  rows_store<(N + 3) / 4>(S, u2, 0, wave, lane);
+  rows_reduce(S, N, out, tid);
+}
+}  // namespace

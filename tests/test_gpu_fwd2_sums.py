@@ -1,4 +1,4 @@
-"""-m gpu: fwd2_sums (csrc/sdxp_persist.hip) - the twelve wave sums of forward L2's bare products w2 * x2 as ONE butterfly behind an explicit
+"""-m gpu: fwd2_sums (csrc/sdxp_persist_sums.h) - the twelve wave sums of forward L2's bare products w2 * x2 as ONE butterfly behind an explicit
 fma level - against the twelve trees it replaces, bit for bit, through the test entry sdxpk_fwd2_sums_check of the loaded library: one
 workgroup of 512 threads (8 waves), w [3][512], x [3][4][512], value net * 4 + s.
 

@@ -10,6 +10,7 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+from helpers.persist_float64 import persistent_or_skip as _require_persistent  # noqa: E402
 from test_gpu_fullsize_properties import _filled_agent  # noqa: E402
 from test_gpu_ppo_parity import make_pair, rollout  # noqa: E402
 
@@ -23,11 +24,6 @@ BOUND_AC, BOUND_CV = 2e-4, 5e-4
 # each).  This change keeps every sum's order: it measures the same figures.
 PARENT_AC_320, PARENT_CV_320 = 1.3550e-04, 1.2156e-04
 BOUND_AC_320, BOUND_CV_320 = 2.0 * PARENT_AC_320, 2.0 * PARENT_CV_320
-
-
-def _require_persistent(agent):
-    if agent.update_impl() != "persistent":
-        pytest.skip("persistent update kernel not selected on this device (needs >= 256 CUs)")
 
 
 def test_three_launches_bit_identical_on_two_handles():

@@ -1,4 +1,4 @@
-"""-m gpu: wave_sums<N> (csrc/sdxp_persist.hip) - N wave sums as one halving butterfly plus two permlane swaps - against N independent
+"""-m gpu: wave_sums<N> (csrc/sdxp_persist_sums.h) - N wave sums as one halving butterfly plus two permlane swaps - against N independent
 wave_sum trees (csrc/sdxp_device.h), bit for bit, through the test entry sdxpk_wave_sums_check of the loaded library: one workgroup of 512
 threads (8 waves), N = 12 (the forward phases) and N = 16 (the head forward on wave 0).  The inputs are chosen so that the ORDER of a sum
 shows in its bits: the host sums every wave in plain lane order and in the tree's order and requires that the two differ somewhere - a

@@ -1,4 +1,4 @@
-// layout probe of v_mfma_f32_4x4x1_16b_f32 (used by gram_mfma in csrc/sdxp_persist.hip): lane l supplies A = l + 1 and B = 1000 + l;
+// layout probe of v_mfma_f32_4x4x1_16b_f32: lane l supplies A = l + 1 and B = 1000 + l;
 // expected: lane 4 b + j, register i holds A(lane 4 b + i) * B(lane 4 b + j)
 #include <hip/hip_runtime.h>
 #include <cstdio>
