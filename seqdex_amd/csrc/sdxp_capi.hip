@@ -24,6 +24,7 @@ struct sdxp_agent {
   hipGraphExec_t graph_exec = nullptr;
   bool use_persist = false;      // persistent register-resident update kernel (sdxp_persist.hip)
   SdxpOpts opts;                 // the SDXP_* switches as sdxp_create found them, lowered to what this device can run (prepare_device)
+  float* gx0_tab = nullptr;      // persistent update: Grams of every minibatch's layer-0 inputs, rebuilt by each epoch's pre-pass (sdxpk_input_grams); scratch
   unsigned* bar_dev = nullptr;   // [SDXP_BAR_WORDS] grid-barrier counter, fail flags and launch counter (sdxp_types.h)
   bool last_was_step = false;    // the most recent persistent launch was a single forward/backward (no restore possible on failure)
   bool use_persist_step = false; // multi-rank path: forward/backward of one minibatch as one persistent-style launch
@@ -194,6 +195,7 @@ extern "C" int sdxp_create(const sdxp_config* cfg, int32_t device, uint64_t seed
   PAL(D.cvx0, R * cfg->state_dim); PAL(D.cvx1, R * cfg->state_dim);
   PAL(D.dbg, 64); PAL(D.dhead, (size_t)2 * MB * 34); PAL(D.dlogstd, 64); PAL(D.ctrl, 1); PAL(h->stats_dev, 16);
   PAL(h->bar_dev, SDXP_BAR_WORDS); PAL(D.ll, SDXP_LL_WORDS);
+  if (h->use_persist) PAL(h->gx0_tab, sdxpk_input_grams_floats(D.num_minibatches));
   D.obs_cols = cfg->obs_cols > 0 ? cfg->obs_cols : cfg->obs_dim;
   PAL(D.obs_pad, (size_t)N * cfg->obs_dim);
   {   // the persistent update's backup list: sdxp_update copies live -> backup, sdxp_update_status backup -> live
@@ -392,7 +394,10 @@ extern "C" int sdxp_prepare_dataset(sdxp_handle h, void* stream) {
 static void begin_epoch_big(sdxp_agent* h, hipStream_t st) { sdxpk_begin_epoch(&h->D, st); sdxpk_big_prenorm(&h->D, &h->bigws, st); }
 static void begin_epoch_rank_mb(sdxp_agent* h, bool persistent, hipStream_t st) {
   sdxpk_begin_epoch(&h->D, st);
-  if (persistent) sdxpk_prenorm(&h->D, h->cfg.minibatch, st); else sdxpk_update_begin(&h->D, h->cfg.minibatch, st);
+  if (persistent) {   // the epoch kernel fetches the Grams of its dataset rows with the rows: formed once, behind the images they are formed from
+    sdxpk_prenorm(&h->D, h->cfg.minibatch, st);
+    sdxpk_input_grams(h->D.mb_obs, h->D.obs_dim, h->D.cvx0, h->D.cvx1, h->D.num_minibatches, h->gx0_tab, st);
+  } else sdxpk_update_begin(&h->D, h->cfg.minibatch, st);
 }
 static bool rank_mb_ok(sdxp_agent* h, const char* who) {
   if (sdxp_rank_mb(h->cfg.minibatch)) return true;   // the rank-MB kernels come in minibatch sizes 2 / 4 / 8
@@ -432,7 +437,7 @@ extern "C" int sdxp_update(sdxp_handle h, void* stream) {
   if (h->use_persist) {
     h->last_was_step = false;
     unsigned* fail = h->bar_dev + SDXP_BAR_PERSIST_FAIL;
-    if (sdxpk_update_persistent(&h->D, (int)total, fail, h->opts.persist_stamps, persist_fault(), st) != 0) { h->err = "persistent update launch failed"; return SDX_ERR_HIP; }
+    if (sdxpk_update_persistent(&h->D, h->gx0_tab, (int)total, fail, h->opts.persist_stamps, persist_fault(), st) != 0) { h->err = "persistent update launch failed"; return SDX_ERR_HIP; }
     PCHK(h, hipMemcpyAsync(h->fail_host, fail, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     return plaunch_ok(h, "sdxp_update(persistent)");
   }

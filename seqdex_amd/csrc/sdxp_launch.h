@@ -42,11 +42,15 @@ void sdxpk_apply_explicit(const SdxpDev* D, int which, float kl, int world, hipS
 size_t sdxpk_persist_lds_bytes();
 int sdxpk_persist_supported(const SdxpDev* D, int minibatch, int n_cus);
 int sdxpk_persist_prepare(int dev);
-int sdxpk_update_persistent(const SdxpDev* D, int total_steps, unsigned* failflag, int stamps, int fault, hipStream_t st);
+// the 4x4 Grams of the layer-0 inputs of n_mb minibatches of 4 rows (obs [4 n_mb][obs_dim], cvx0 / cvx1 [4 n_mb][564]) -> tab, sdxpk_input_grams_floats(n_mb) floats
+int sdxpk_input_grams(const float* obs, int obs_dim, const float* cvx0, const float* cvx1, int n_mb, float* tab, hipStream_t st);
+size_t sdxpk_input_grams_floats(int n_mb);
+int sdxpk_update_persistent(const SdxpDev* D, const float* gx0_tab, int total_steps, unsigned* failflag, int stamps, int fault, hipStream_t st);
 int sdxpk_fwd_bwd_persistent(const SdxpDev* D, unsigned* failflag, hipStream_t st);
 // sdxp_persist_checks.hip
 int sdxpk_wave_sums_check(const float* in, float* ref, float* got, int n, hipStream_t st);   // test entry: wave_sums<n> beside n wave_sum trees, n = 12 or 16
 int sdxpk_fwd2_sums_check(const float* w, const float* x, float* ref, float* got, hipStream_t st);   // test entry: fwd2_sums beside the twelve trees it replaces
+int sdxpk_input_grams_reference(const float* obs, int obs_dim, const float* cvx, int n_mb, float* out, hipStream_t st);   // test entry: the input Grams as the epoch kernel formed them in its x1 shadow
 // sdxp_bigmb.hip.  sdxpk_big_setup lowers the large-minibatch options of `o` to what shapes and device allow, sets the LDS attributes of
 // the kernels that stay and lays out the workspace of one minibatch of MB rows in `ws`, every buffer through `alloc`
 int sdxpk_big_setup(const SdxpDev* D, int MB, SdxpOpts* o, SdxpAllocFn alloc, void* ctx, SdxpBigWs* ws);

@@ -9,6 +9,9 @@
 //   C  gather x2, forward L2 of own row                                                                  -> x3  | shadow: Gram x2
 //   D  gather x3 + heads, PPO losses (replicated on every CU, bit-identical), backward heads and L2      -> dY1 | shadow: stats, LR rule, Gram x3, head norms
 //   E  gather dY1, backward L1 (column copy)                                                             -> dY0 | shadow: Grams dY1, dY2
+// (Phase A's shadow holds Adam of layer 1 alone.  The Gram of the layer-0 inputs, which stood in it, does not depend on the step - the
+// inputs are dataset rows: k_input_grams at the end of this file forms every minibatch's once per epoch, behind the pre-normalisation,
+// and the step fetches its 32 floats with its rows.)
 //
 // Ownership (shipped network 396/564 -> 1024 -> 512 -> 256 -> 23/1, minibatch 4):
 //   W0 rows      : CU g, wave w owns half (w&1) of row 4g+(w>>1) of actor, critic and central value
@@ -41,7 +44,7 @@ __device__ __forceinline__ const float* cvx_rows(const SdxpDev& D, int mb, int m
 // device cursor SdxpCtrl.mb_index points at) with the current parameters; no optimiser state is touched, the rank-MB factors
 // are written to D.fact for the multi-rank exchange and the cursor / loss statistics advance as k_ctrl does in explicit mode.
 template <bool SINGLE>
-__global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int total_steps, unsigned* bar, unsigned* failflag, int stamps, int fault) {
+__global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int total_steps, const float* gx0_tab, unsigned* failflag, int stamps, int fault) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   PLds& S = *reinterpret_cast<PLds*>(smem_raw);
   // Thread coordinates are re-derived from an opaque copy of threadIdx/blockIdx at the start of every phase (refresh()):
@@ -190,6 +193,14 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     const float* o = uni(obs_rows(D, mb_));
     const float* c = uni(cvx_rows(D, mb_, me_));
     const unsigned odim = D.obs_dim;
+    if constexpr (!SINGLE) {
+      // the Grams of these rows, from the table the pre-pass formed for the epoch (k_input_grams): 32 lanes of the last wave - it has one piece
+      // fewer than the others below - fetch the observation block and the central value's block of this mini-epoch's class into S.gx0.  The
+      // reader is wave 0 at the end of phase E; the previous step's read lies three barriers in front of this request
+      const float* gt = uni(gx0_tab + (size_t)mb_ * GX0_STRIDE);
+      if (wave == NWV - 1 && lane < 32)
+        __builtin_amdgcn_global_load_lds(SDX_AS_GLOBAL(gt + (lane < 16 ? GX0_OBS + lane : (me_ == 0 ? GX0_CVX0 : GX0_CVX1) + (lane - 16))), SDX_AS_LDS(&S.gx0[0][0]), 4, 0, 0);
+    }
     if (odim == OBS) {
       // full-width observations: the MB rows are contiguous in the dataset AND in LDS (S.obs, then S.cvx): 960 pieces of 16 bytes, two
       // global_load_lds_dwordx4 per lane (twelve dword loads with their exec masks and M0 writes cost phase A 0.4 us of issue)
@@ -316,18 +327,8 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
         lq_store(LQ, LQ_X1 + (unsigned)s * U0 + 4 * g + r, y[0], y[1], y[2], tag);
       }
       TS(2)
-      if constexpr (!SINGLE) {
-      // ---- in the shadow of the x1 exchange: Gram of the layer-0 inputs
-      float p[22];
-#pragma unroll
-      for (int i = 0; i < 22; ++i) p[i] = 0.0f;
-      if (tid < OBS) gram_acc(&p[0], S.obs[0][tid], S.obs[1][tid], S.obs[2][tid], S.obs[3][tid]);
-      gram_acc(&p[11], S.cvx[0][tid], S.cvx[1][tid], S.cvx[2][tid], S.cvx[3][tid]);
-      if (tid + NTH < ST) gram_acc(&p[11], S.cvx[0][tid + NTH], S.cvx[1][tid + NTH], S.cvx[2][tid + NTH], S.cvx[3][tid + NTH]);
-      block_sum<22>(S, p, S.part, tid, wave, lane);
-      if (tid < 16) { const float v = S.part[tri16(tid)]; S.gx[0][0][tid] = v; S.gx[1][0][tid] = v; }
-      else if (tid >= 64 && tid < 80) S.gx[2][0][tid - 64] = S.part[11 + tri16(tid - 64)];
-      }
+      // (the Gram of the layer-0 inputs that stood here, in the shadow of the x1 exchange, does not depend on the step: it arrives from the
+      // per-epoch table with the rows of the minibatch - k_input_grams, load_rows, S.gx0)
     }
     refresh();
     if (pending) {
@@ -537,9 +538,17 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
 #pragma unroll
         for (int i = 0; i < 30; ++i) p[i] = 0.0f;
 #pragma unroll
-        for (int h = 0; h < U0 / NTH; ++h)
+        for (int h = 0; h < U0 / NTH; ++h) {
 #pragma unroll
           for (int net = 0; net < 3; ++net) { const int k = tid + NTH * h; gram_acc10(&p[net * 10], S.x1[net][0][k], S.x1[net][1][k], S.x1[net][2][k], S.x1[net][3][k]); }
+          // (the first column's terms are ROUNDED products, the second column is accumulated onto them by fma.  A diagonal entry is a sum of two
+          // squares, x x + y y, and 0 + x x folds to the bare product, so either square may be the one contracted into the fma: which one the
+          // compiler picks moved with code elsewhere in the kernel, and with it the last bit of G_x1[s][s].  The opaque copy keeps the first.)
+          if (h == 0) {
+#pragma unroll
+            for (int i = 0; i < 30; ++i) asm("" : "+v"(p[i]));
+          }
+        }
         row_butterfly<30>(p, ub, lane);
       }
       rows_store<8>(S, ub, 32, wave, lane);
@@ -1010,7 +1019,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
               float gg = 0.0f;
 #pragma unroll
               for (int c = 0; c < 4; ++c) gg += S.dyown[net][hi][DY_L0 + c] * S.dyown[net][lo][DY_L0 + c];
-              t[net] = gg * S.gx[net][0][lane] + gg;
+              t[net] = gg * S.gx0[net >> 1][lane] + gg;
             }
           }
 #pragma unroll
@@ -1209,10 +1218,67 @@ extern "C" int sdxpk_persist_prepare(int dev) {
   fprintf(stderr, "libseqdex_hip: k_update_persistent cannot have %zu bytes of LDS on device %d: this handle uses the hipGraph update and the multi-kernel step\n", sizeof(PLds), dev);
   return 0;
 }
-// stamps: SdxpOpts::persist_stamps (phase clock of one CU); fault: SDXP_PERSIST_FAULT=1 (one CU goes silent: the failure-path test)
-extern "C" int sdxpk_update_persistent(const SdxpDev* D, int total_steps, unsigned* failflag, int stamps, int fault, hipStream_t st) {
+// The 4x4 Grams of the layer-0 inputs of every minibatch of the epoch: tab[mb][GX0_OBS | GX0_CVX0 | GX0_CVX1][16], one workgroup per
+// minibatch.  The rows are dataset rows - mb_obs is fixed for the epoch, cvx0 / cvx1 are written by the pre-normalisation in front of the
+// persistent launch - so the epoch kernel, which formed these Grams in the shadow of its x1 edge in every one of the mini-epochs, fetches
+// them with the rows instead (load_rows).  The summation order is the one that shadow had, so that the norm words keep their bits: thread
+// tid holds column tid of the observations (zero past obs_dim) and columns tid, tid + NTH of the central value's rows; value 0..9 the
+// observations' triangle, 11..20 the central value's (10 and 21, |sum_s x_s|^2, had no reader and stay zero: the butterfly keeps its
+// numbering); row_butterfly<22> over the 16-lane DPP rows, then the 32 row sums added from 0.0f in ascending (wave, row) order.  Two
+// passes, cvx0 and cvx1 (the observations' values of the second are not stored).
+__global__ __launch_bounds__(NTH) void k_input_grams(const float* __restrict__ obs, int obs_dim, const float* __restrict__ cvx0, const float* __restrict__ cvx1, float* __restrict__ tab) {
+  __shared__ float red[4 * NWV][24];
+  __shared__ float part[24];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const size_t mb = blockIdx.x;
+  const float* o = obs + mb * MB * obs_dim;
+  float xo[MB];
+#pragma unroll
+  for (int s = 0; s < MB; ++s) xo[s] = tid < obs_dim ? o[(size_t)s * obs_dim + tid] : 0.0f;
+  for (int cls = 0; cls < 2; ++cls) {
+    const float* c = (cls == 0 ? cvx0 : cvx1) + mb * MB * ST;
+    float xa[MB], xb[MB];
+#pragma unroll
+    for (int s = 0; s < MB; ++s) { xa[s] = c[s * ST + tid]; xb[s] = tid + NTH < ST ? c[s * ST + tid + NTH] : 0.0f; }
+    float p[22], u2[6];
+#pragma unroll
+    for (int i = 0; i < 22; ++i) p[i] = 0.0f;
+    if (tid < OBS) gram_acc10(&p[0], xo[0], xo[1], xo[2], xo[3]);
+    gram_acc10(&p[11], xa[0], xa[1], xa[2], xa[3]);
+    if (tid + NTH < ST) gram_acc10(&p[11], xb[0], xb[1], xb[2], xb[3]);
+    row_butterfly<22>(p, u2, lane);
+    if ((lane & 15) < 4) {
+      float* r = red[wave * 4 + (lane >> 4)];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) r[4 * j + (lane & 3)] = u2[j];
+    }
+    __syncthreads();
+    if (tid < 22) {
+      float t = 0.0f;
+#pragma unroll
+      for (int w = 0; w < 4 * NWV; ++w) t += red[w][tid];
+      part[tid] = t;
+    }
+    __syncthreads();
+    float* out = tab + mb * GX0_STRIDE;
+    if (tid < 16) { if (cls == 0) out[GX0_OBS + tid] = part[tri16(tid)]; }
+    else if (tid >= 64 && tid < 80) out[(cls == 0 ? GX0_CVX0 : GX0_CVX1) + tid - 64] = part[11 + tri16(tid - 64)];
+    __syncthreads();   // part and red are written again by the second pass
+  }
+}
+// obs [4 n_mb][obs_dim], cvx0 / cvx1 [4 n_mb][ST] -> tab [n_mb][GX0_STRIDE]; sdxp_update runs it behind the pre-normalisation of a persistent
+// epoch, tests/test_gpu_persist_input_grams.py on rows of its own
+extern "C" int sdxpk_input_grams(const float* obs, int obs_dim, const float* cvx0, const float* cvx1, int n_mb, float* tab, hipStream_t st) {
+  if (obs_dim < 1 || obs_dim > OBS || n_mb < 1) return -1;
+  hipLaunchKernelGGL(k_input_grams, dim3(n_mb), dim3(NTH), 0, st, obs, obs_dim, cvx0, cvx1, tab);
+  return 0;
+}
+extern "C" size_t sdxpk_input_grams_floats(int n_mb) { return (size_t)n_mb * GX0_STRIDE; }
+// stamps: SdxpOpts::persist_stamps (phase clock of one CU); fault: SDXP_PERSIST_FAULT=1 (one CU goes silent: the failure-path test); gx0_tab: the
+// table k_input_grams wrote for this epoch's rows
+extern "C" int sdxpk_update_persistent(const SdxpDev* D, const float* gx0_tab, int total_steps, unsigned* failflag, int stamps, int fault, hipStream_t st) {
   if (hipMemsetAsync(failflag, 0, sizeof(unsigned), st) != hipSuccess) return -1;
-  hipLaunchKernelGGL(k_update_persistent<false>, dim3(NWG), dim3(NTH), sizeof(PLds), st, *D, total_steps, nullptr, failflag, stamps, fault);
+  hipLaunchKernelGGL(k_update_persistent<false>, dim3(NWG), dim3(NTH), sizeof(PLds), st, *D, total_steps, gx0_tab, failflag, stamps, fault);
   return 0;
 }
 // forward + backward of the minibatch under the device cursor -> D.fact (multi-rank path); the fail flag is sticky (not cleared here)

@@ -60,3 +60,32 @@ extern "C" int sdxpk_fwd2_sums_check(const float* w, const float* x, float* ref,
   hipLaunchKernelGGL(k_fwd2_sums_check, dim3(1), dim3(NTH), 0, st, w, x, ref, got);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+// Test entry (tests/test_gpu_persist_input_grams.py): the Grams of the layer-0 inputs in the form the epoch kernel gave them while it formed
+// them itself, in the shadow of its x1 edge - the reference that the per-epoch table (k_input_grams, sdxp_persist.hip) is held to, bit for bit.
+// One workgroup per minibatch; the rows go into the S.obs / S.cvx images (columns of S.obs past obs_dim zero), then gram_acc10 per thread, the
+// 22-value block_sum (row_butterfly over the DPP rows, the 32 row sums added from 0.0f in ascending order) and the 16-entry expansion.
+// obs [4 n_mb][obs_dim], cvx [4 n_mb][ST] -> out [n_mb][2][16]: the observations' Gram, the central value's.
+__global__ __launch_bounds__(NTH) void k_input_grams_reference(const float* obs, int obs_dim, const float* cvx, float* out) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  PLds& S = *reinterpret_cast<PLds*>(smem_raw);
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const size_t mb = blockIdx.x;
+  for (int i = tid; i < MB * OBS; i += NTH) { const int s = i / OBS, k = i % OBS; S.obs[s][k] = k < obs_dim ? obs[(mb * MB + s) * obs_dim + k] : 0.0f; }
+  for (int i = tid; i < MB * ST; i += NTH) (&S.cvx[0][0])[i] = cvx[mb * MB * ST + i];
+  __syncthreads();
+  float p[22];
+#pragma unroll
+  for (int i = 0; i < 22; ++i) p[i] = 0.0f;
+  if (tid < OBS) gram_acc10(&p[0], S.obs[0][tid], S.obs[1][tid], S.obs[2][tid], S.obs[3][tid]);
+  gram_acc10(&p[11], S.cvx[0][tid], S.cvx[1][tid], S.cvx[2][tid], S.cvx[3][tid]);
+  if (tid + NTH < ST) gram_acc10(&p[11], S.cvx[0][tid + NTH], S.cvx[1][tid + NTH], S.cvx[2][tid + NTH], S.cvx[3][tid + NTH]);
+  block_sum<22>(S, p, S.part, tid, wave, lane);
+  if (tid < 16) out[mb * 32 + tid] = S.part[tri16(tid)];
+  else if (tid >= 64 && tid < 80) out[mb * 32 + 16 + tid - 64] = S.part[11 + tri16(tid - 64)];
+}
+extern "C" int sdxpk_input_grams_reference(const float* obs, int obs_dim, const float* cvx, int n_mb, float* out, hipStream_t st) {
+  if (obs_dim < 1 || obs_dim > OBS || n_mb < 1) return -1;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_input_grams_reference), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PLds)) != hipSuccess) return -1;
+  hipLaunchKernelGGL(k_input_grams_reference, dim3(n_mb), dim3(NTH), sizeof(PLds), st, obs, obs_dim, cvx, out);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}

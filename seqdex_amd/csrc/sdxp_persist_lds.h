@@ -36,7 +36,10 @@ struct PLds {
   float dy1[3][MB][U1];
   // Gram matrices (MB x MB) of the factors of the minibatch currently held: inputs gx[net][layer 0..3], gradients gd[net][layer 0..2]
   // (round 6: the gradient factors' Grams never leave the reduction that forms them - layer 0's meets G_x0 on the producing CU, layers 1 / 2
-  // meet theirs at the end of the dY0 shadow - so only the inputs' Grams and one partial squared norm per network are kept)
+  // meet theirs at the end of the dY0 shadow - so only the inputs' Grams and one partial squared norm per network are kept).
+  // Layers 1..3 are formed in the step's shadows.  The [layer 0] slice is no longer written or read: the Grams of the dataset rows come
+  // from the per-epoch table (k_input_grams) with the rows themselves and land in gx0 below; the slice stays so that every member behind it
+  // keeps its offset and the one-minibatch instantiation, which never had these Grams, compiles to the code it had
   float gx[3][4][16];
   float gd2[3][16];          // Gram of dY2 (formed in the dY1 shadow beside the Gram of x3, used at the end of the dY0 shadow)
   float n2rest[4];           // per network: sum over trunk layers 1, 2 of <G_dY, G_x> + their bias terms + the heads' terms (n2h): everything but layer 0
@@ -56,6 +59,11 @@ struct PLds {
   } ctl;
   int fail;
   long long tacc[32], tlast;   // phase clock accumulators of CU 0 (SDXP_PERSIST_STAMPS=1)
+  // Grams of the layer-0 inputs of the minibatch held, 16-entry form: [0] the observation rows (actor and critic), [1] the central value's
+  // normalised rows of this mini-epoch's class.  One 32-lane global_load_lds of load_rows (GX0_*), read by wave 0 at the end of phase E
+  float gx0[2][16];
 };
+// the table k_input_grams writes and load_rows reads: [minibatch][GX0_OBS | GX0_CVX0 | GX0_CVX1][16] floats
+constexpr int GX0_OBS = 0, GX0_CVX0 = 16, GX0_CVX1 = 32, GX0_STRIDE = 48;
 static_assert(sizeof(PLds) + 512 <= 160 * 1024, "PLds (+ the static logstd bank) must fit the 160 KiB LDS of a gfx950 CU");
 }  // namespace

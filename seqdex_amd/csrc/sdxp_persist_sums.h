@@ -13,16 +13,10 @@ __device__ __forceinline__ float pair_sum(float v) {
   const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
   return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
 }
-// accumulate the 4x4 Gram (lower triangle, 10 terms) of (a, b, c, d) ...
+// accumulate the 4x4 Gram (lower triangle, 10 terms) of (a, b, c, d)
 __device__ __forceinline__ void gram_acc10(float* p, float a, float b, float c, float d) {
   p[0] += a * a; p[1] += b * a; p[2] += b * b; p[3] += c * a; p[4] += c * b; p[5] += c * c;
   p[6] += d * a; p[7] += d * b; p[8] += d * c; p[9] += d * d;
-}
-// ... and |sum|^2 (the bias term)
-__device__ __forceinline__ void gram_acc(float* p, float a, float b, float c, float d) {
-  gram_acc10(p, a, b, c, d);
-  const float sb = a + b + c + d;
-  p[10] += sb * sb;
 }
 __device__ __forceinline__ int tri16(int i) { const int a = i >> 2, b = i & 3, hi = a > b ? a : b, lo = a > b ? b : a; return hi * (hi + 1) / 2 + lo; }
 // sums over each 16-lane DPP row, in every lane of the row: the first four levels of wave_sum (quad_perm, quad_perm, row_half_mirror, row_mirror)
