@@ -333,32 +333,9 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     refresh();
     if (pending) {
       // ---- (shadow of x1) Adam of layer 1: row copy and column copy, operands are last step's S.x1 / S.dy1
+      // (one loop over the 24 elements with the next element's operands in flight: adam_l1_ahead)
       const StepScal sc = step_scal(S);
-      float dep = 0.0f;
-#pragma unroll
-      for (int net = 0; net < 3; ++net) {
-        const float gs = sc.gs(net), lrb = sc.lrb(net), isq = sc.isq(net);
-        float d1r[MB], dn1[MB];
-        const int o_r = opaque(r1w, dep), o_t = opaque(tid, dep);
-#pragma unroll
-        for (int s = 0; s < MB; ++s) { d1r[s] = S.dyown[net][s][DY_L1 + o_r] * gs; dn1[s] = S.dy1[net][s][o_t] * gs; }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int k = opaque(q1 * 256 + lane + 64 * i, dep);
-          float gg = 0.0f;
-#pragma unroll
-          for (int s = 0; s < MB; ++s) gg += d1r[s] * S.x1[net][s][k];
-          adam1(w1[net][i], gg, m1[net][i], v1[net][i], lrb, isq); dep = w1[net][i];
-        }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const int k = opaque(4 * g + c, dep);
-          float gg = 0.0f;
-#pragma unroll
-          for (int s = 0; s < MB; ++s) gg += dn1[s] * S.x1[net][s][k];
-          adam1(c1[net][c], gg, cm1[net][c], cv1[net][c], lrb, isq); dep = c1[net][c];
-        }
-      }
+      adam_l1_ahead(S, sc, q1 * 256 + lane, 4 * g, r1w, tid, w1, m1, v1, c1, cm1, cv1, [](int, int, float) {});
       if (tid >= BIAS_L1 && tid < BIAS_L2) {   // layer-1 biases
         const int net = (tid - BIAS_L1) / 2;
         float gg = 0.0f;

@@ -1,4 +1,4 @@
-// sdxp_persist_adam.h - private to sdxp_persist.hip (included by it only): the per-element Adam updates of k_update_persistent and the opaque
+// sdxp_persist_adam.h - private to sdxp_persist.hip (included by it and by the test entries of sdxp_persist_checks.hip): the per-element Adam updates of k_update_persistent and the opaque
 // copies / register pins that keep its schedule and register allocation where they are
 #pragma once
 #include "sdxp_persist_lds.h"
@@ -46,4 +46,80 @@ __device__ __forceinline__ void adam_bias(PLds& S, const StepScal& sc, int slot,
 }
 #define SDX_PIN4X(a, b, c, d) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
 #define SDX_PIN3X(a, b, c) asm volatile("" : "+v"(a), "+v"(b), "+v"(c))
+
+// ---- Adam with the operands of the next element in flight (the x1 shadow)
+// adam1 with every rounding written out: the three products a contraction could take either way go through an opaque copy, the fmas are
+// explicit.  These are the forms hipcc gives adam1 inside the serial loops (tests/test_gpu_persist_adam_ahead.py holds the two to each other):
+//   m = fma(0.1, g, rn(0.9 m)), v = fma(g, rn(0.001 g), rn(0.999 v)), w = fma(-rn(lrb m), rcp(fma(isq, sqrt(v), 1e-8)), w)
+__device__ __forceinline__ float rounded(float x) { asm volatile("" : "+v"(x)); return x; }
+__device__ __forceinline__ void adam1x(float& w, float g, float& m, float& v, float lr_bc1, float isq_bc2) {
+  const float m9 = rounded(0.9f * m), v999 = rounded(0.999f * v), t = rounded(0.001f * g);
+  m = __builtin_fmaf(0.1f, g, m9);
+  v = __builtin_fmaf(g, t, v999);
+  const float lm = rounded(lr_bc1 * m);
+  w = __builtin_fmaf(-lm, __builtin_amdgcn_rcpf(__builtin_fmaf(isq_bc2, __builtin_amdgcn_sqrtf(v), 1e-8f)), w);
+  __builtin_amdgcn_sched_barrier(0);
+}
+// the gradient element sum_s d_s x_s, from 0 in ascending order of s, one fma per sample
+__device__ __forceinline__ float grad4(const float (&d)[MB], const float (&x)[MB]) {
+  static_assert(MB == 4, "four samples");
+  return __builtin_fmaf(d[3], x[3], __builtin_fmaf(d[2], x[2], __builtin_fmaf(d[1], x[1], __builtin_fmaf(d[0], x[0], 0.0f))));
+}
+// Adam of layer 1 as ONE loop over the lane's 24 elements: per network the row elements 0..3 (columns kr + 64 i of S.x1, factors
+// S.dyown[net][.][DY_L1 + o_row]), then the column elements 0..3 (columns kc + c, factors S.dy1[net][.][o_thr]) - the serial loops' order.
+// The four operands of element e are pinned together (one wait), then the four S.x1 operands of element e + 1 are requested - through an
+// index made opaque against the weight element e - 1 wrote, so the request can rise no further, and with a sched_barrier behind it, so it
+// cannot sink into the arithmetic of element e - and fly under that arithmetic.  The pin stands IN FRONT of the request on purpose: every wait
+// hipcc places in this region is lgkmcnt(0), never a partial count, so a wait behind the request would drain the reads just issued; in front of
+// it, it finds reads that were requested a whole element ago.  The factors are requested a network ahead, into the registers their
+// predecessors left: the row factors under column element 1 of the network in front, the column factors under row element 1; each is scaled
+// by the clip factor where it is first used.
+// sink(net, j, gg): the gradient element, for the test entry; the kernel passes an empty one.
+template <class Sink>
+__device__ __forceinline__ void adam_l1_ahead(const PLds& S, const StepScal& sc, int kr, int kc, int o_row, int o_thr, float (&w1)[3][4],
+                                              float (&m1)[3][4], float (&v1)[3][4], float (&c1)[3][4], float (&cm1)[3][4], float (&cv1)[3][4],
+                                              Sink&& sink) {
+  float dr[MB], dn[MB], x[2][MB], dep = 0.0f;   // x[e & 1]: the operands of element e
+  {
+    const int o_r = opaque(o_row, dep), o_t = opaque(o_thr, dep), k = opaque(kr, dep);
+#pragma unroll
+    for (int s = 0; s < MB; ++s) { dr[s] = S.dyown[0][s][DY_L1 + o_r]; dn[s] = S.dy1[0][s][o_t]; x[0][s] = S.x1[0][s][k]; }
+  }
+#pragma unroll
+  for (int e = 0; e < 24; ++e) {
+    const int net = e / 8, j = e % 8;
+    float (&xc)[MB] = x[e & 1], (&xn)[MB] = x[(e + 1) & 1];
+    SDX_PIN4X(xc[0], xc[1], xc[2], xc[3]);
+    if (e + 1 < 24) {
+      const int n1 = (e + 1) / 8, j1 = (e + 1) % 8;
+      const int k = opaque(j1 < 4 ? kr + 64 * j1 : kc + (j1 - 4), dep);
+#pragma unroll
+      for (int s = 0; s < MB; ++s) xn[s] = S.x1[n1][s][k];
+    }
+    if (j == 5 && net < 2) {
+      const int o_r = opaque(o_row, dep);
+#pragma unroll
+      for (int s = 0; s < MB; ++s) dr[s] = S.dyown[net + 1][s][DY_L1 + o_r];
+    }
+    if (j == 1 && net > 0) {
+      const int o_t = opaque(o_thr, dep);
+#pragma unroll
+      for (int s = 0; s < MB; ++s) dn[s] = S.dy1[net][s][o_t];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (j == 0) {
+#pragma unroll
+      for (int s = 0; s < MB; ++s) dr[s] *= sc.gs(net);
+    }
+    if (j == 4) {
+#pragma unroll
+      for (int s = 0; s < MB; ++s) dn[s] *= sc.gs(net);
+    }
+    const float gg = grad4(j < 4 ? dr : dn, xc);
+    sink(net, j, gg);
+    float& w = j < 4 ? w1[net][j] : c1[net][j - 4];
+    adam1x(w, gg, j < 4 ? m1[net][j] : cm1[net][j - 4], j < 4 ? v1[net][j] : cv1[net][j - 4], sc.lrb(net), sc.isq(net));
+    dep = w;
+  }
+}
 }  // namespace

@@ -1,9 +1,10 @@
-// sdxp_persist_checks.hip — test entries for the sum machinery of the persistent PPO update (sdxp_persist_sums.h): each runs the helper
-// k_update_persistent uses beside the trees it stands for, in one workgroup, and hands both results back.  Built with the flags of
+// sdxp_persist_checks.hip — test entries for the machinery of the persistent PPO update (sdxp_persist_sums.h, sdxp_persist_adam.h): each runs the
+// helper k_update_persistent uses beside the form it stands for, in one workgroup, and hands both results back.  Built with the flags of
 // sdxp_persist.hip (Makefile), so that the helpers are compiled here as they are inside the kernel.
 #include "sdx_common.h"
 #include "sdxp_launch.h"
 #include "sdxp_persist_sums.h"
+#include "sdxp_persist_adam.h"
 
 // Test entry (tests/test_gpu_wave_sums.py): one workgroup of NTH threads, in / ref / got are [N][NTH].  ref[i][t] = wave_sum of value i in t's
 // wave, on every lane; got[i][t] = what wave_sums<N> left in lane t for value i - written by the lanes with (t & 3) == (i & 3), the others'
@@ -87,5 +88,84 @@ extern "C" int sdxpk_input_grams_reference(const float* obs, int obs_dim, const 
   if (obs_dim < 1 || obs_dim > OBS || n_mb < 1) return -1;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_input_grams_reference), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PLds)) != hipSuccess) return -1;
   hipLaunchKernelGGL(k_input_grams_reference, dim3(n_mb), dim3(NTH), sizeof(PLds), st, obs, obs_dim, cvx, out);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// Test entry (tests/test_gpu_persist_adam_ahead.py): Adam of layer 1 in the x1 shadow, one workgroup of NTH threads standing for CU g.  x1 [3][MB][U0]
+// goes into the S.x1 image, dy1 [3][MB][U1] into S.dy1 (the column factors, one per lane), dyr [3][MB][2] into S.dyown[.][.][DY_L1 + row] (the
+// row factors of the workgroup's two rows), scal [6] into S.scal (SC_*).  state [3][24][NTH]: (w, m, v) of the lane's elements, element
+// net 8 + j: j < 4 the row element of column (wave & 3) 256 + lane + 64 j, j >= 4 the column element of column 4 g + j - 4.
+// out [2][4][24][NTH]: (gg, m, v, w) of [0] the serial loops the epoch kernel ran before adam_l1_ahead - every operand read behind the
+// arithmetic of the element in front, adam1 - kept here as the reference, and of [1] adam_l1_ahead on the same inputs.
+__global__ __launch_bounds__(NTH) void k_adam_ahead_check(const float* x1, const float* dy1, const float* dyr, const float* scal, int g, const float* state, float* out) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  PLds& S = *reinterpret_cast<PLds*>(smem_raw);
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r1w = wave >> 2, q1 = wave & 3;
+  for (int i = tid; i < 3 * MB * U0; i += NTH) (&S.x1[0][0][0])[i] = x1[i];
+  for (int i = tid; i < 3 * MB * U1; i += NTH) (&S.dy1[0][0][0])[i] = dy1[i];
+  if (tid < 3 * MB * 2) S.dyown[tid / (2 * MB)][(tid / 2) % MB][DY_L1 + tid % 2] = dyr[tid];
+  if (tid < 6) S.scal[tid] = scal[tid];
+  __syncthreads();
+  const StepScal sc = step_scal(S);
+  float w1[3][4], m1[3][4], v1[3][4], c1[3][4], cm1[3][4], cv1[3][4];
+  auto load = [&]() {
+#pragma unroll
+    for (int net = 0; net < 3; ++net)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int r = (net * 8 + j) * NTH + tid, c = (net * 8 + 4 + j) * NTH + tid;
+        w1[net][j] = state[r]; m1[net][j] = state[24 * NTH + r]; v1[net][j] = state[48 * NTH + r];
+        c1[net][j] = state[c]; cm1[net][j] = state[24 * NTH + c]; cv1[net][j] = state[48 * NTH + c];
+      }
+  };
+  auto store = [&](float* o) {   // o: [4][24][NTH], the gradient elements are already there
+#pragma unroll
+    for (int net = 0; net < 3; ++net)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int r = (net * 8 + j) * NTH + tid, c = (net * 8 + 4 + j) * NTH + tid;
+        o[24 * NTH + r] = m1[net][j]; o[48 * NTH + r] = v1[net][j]; o[72 * NTH + r] = w1[net][j];
+        o[24 * NTH + c] = cm1[net][j]; o[48 * NTH + c] = cv1[net][j]; o[72 * NTH + c] = c1[net][j];
+      }
+  };
+  load();
+  {
+    float dep = 0.0f;
+#pragma unroll
+    for (int net = 0; net < 3; ++net) {
+      const float gs = sc.gs(net), lrb = sc.lrb(net), isq = sc.isq(net);
+      float d1r[MB], dn1[MB];
+      const int o_r = opaque(r1w, dep), o_t = opaque(tid, dep);
+#pragma unroll
+      for (int s = 0; s < MB; ++s) { d1r[s] = S.dyown[net][s][DY_L1 + o_r] * gs; dn1[s] = S.dy1[net][s][o_t] * gs; }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int k = opaque(q1 * 256 + lane + 64 * i, dep);
+        float gg = 0.0f;
+#pragma unroll
+        for (int s = 0; s < MB; ++s) gg += d1r[s] * S.x1[net][s][k];
+        out[(net * 8 + i) * NTH + tid] = gg;
+        adam1(w1[net][i], gg, m1[net][i], v1[net][i], lrb, isq); dep = w1[net][i];
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int k = opaque(4 * g + c, dep);
+        float gg = 0.0f;
+#pragma unroll
+        for (int s = 0; s < MB; ++s) gg += dn1[s] * S.x1[net][s][k];
+        out[(net * 8 + 4 + c) * NTH + tid] = gg;
+        adam1(c1[net][c], gg, cm1[net][c], cv1[net][c], lrb, isq); dep = c1[net][c];
+      }
+    }
+  }
+  store(out);
+  load();
+  float* got = out + 4 * 24 * NTH;
+  adam_l1_ahead(S, sc, q1 * 256 + lane, 4 * g, r1w, tid, w1, m1, v1, c1, cm1, cv1, [&](int net, int j, float gg) { got[(net * 8 + j) * NTH + tid] = gg; });
+  store(got);
+}
+extern "C" int sdxpk_adam_ahead_check(const float* x1, const float* dy1, const float* dyr, const float* scal, int g, const float* state, float* out, hipStream_t st) {
+  if (g < 0 || g >= NWG) return -1;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_adam_ahead_check), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PLds)) != hipSuccess) return -1;
+  hipLaunchKernelGGL(k_adam_ahead_check, dim3(1), dim3(NTH), sizeof(PLds), st, x1, dy1, dyr, scal, g, state, out);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
