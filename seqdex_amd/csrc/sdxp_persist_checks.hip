@@ -169,3 +169,87 @@ extern "C" int sdxpk_adam_ahead_check(const float* x1, const float* dy1, const f
   hipLaunchKernelGGL(k_adam_ahead_check, dim3(1), dim3(NTH), sizeof(PLds), st, x1, dy1, dyr, scal, g, state, out);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+// Test entry (tests/test_gpu_persist_gram_x.py): the Grams of x2 and x1 as the epoch kernel forms them in the shadow of its x3 edge, one
+// workgroup of NTH threads.  x1 [3][MB][U0] and x2 [3][MB][U1] go into the S.x1 / S.x2 images; the block below is the kernel's, verbatim - two
+// butterflies, ONE reduction of 64 columns, the first column's products of x1 kept rounded by an opaque copy - but for the stores of terms.
+// terms [2][30][NTH] (Gram: 0 = x2, 1 = x1): what every thread holds in front of its butterfly, value net 10 + e; entries [2][48]: the finished
+// 16-entry matrices of the three networks (S.gx[net][2], S.gx[net][1]).
+__global__ __launch_bounds__(NTH) void k_gram_x_check(const float* x1, const float* x2, float* terms, float* entries) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  PLds& S = *reinterpret_cast<PLds*>(smem_raw);
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  for (int i = tid; i < 3 * MB * U0; i += NTH) (&S.x1[0][0][0])[i] = x1[i];
+  for (int i = tid; i < 3 * MB * U1; i += NTH) (&S.x2[0][0][0])[i] = x2[i];
+  __syncthreads();
+  {
+    float ua[8], ub[8];
+    {
+      float p[30];
+#pragma unroll
+      for (int i = 0; i < 30; ++i) p[i] = 0.0f;
+#pragma unroll
+      for (int net = 0; net < 3; ++net) gram_acc10(&p[net * 10], S.x2[net][0][tid], S.x2[net][1][tid], S.x2[net][2][tid], S.x2[net][3][tid]);
+#pragma unroll
+      for (int i = 0; i < 30; ++i) terms[i * NTH + tid] = p[i];
+      row_butterfly<30>(p, ua, lane);
+    }
+    rows_store<8>(S, ua, 0, wave, lane);
+    {
+      float p[30];
+#pragma unroll
+      for (int i = 0; i < 30; ++i) p[i] = 0.0f;
+#pragma unroll
+      for (int h = 0; h < U0 / NTH; ++h) {
+#pragma unroll
+        for (int net = 0; net < 3; ++net) { const int k = tid + NTH * h; gram_acc10(&p[net * 10], S.x1[net][0][k], S.x1[net][1][k], S.x1[net][2][k], S.x1[net][3][k]); }
+        if (h == 0) {
+#pragma unroll
+          for (int i = 0; i < 30; ++i) asm("" : "+v"(p[i]));
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 30; ++i) terms[(30 + i) * NTH + tid] = p[i];
+      row_butterfly<30>(p, ub, lane);
+    }
+    rows_store<8>(S, ub, 32, wave, lane);
+    rows_reduce(S, 64, S.part, tid);
+    if (tid < 48) S.gx[tid >> 4][2][tid & 15] = S.part[(tid >> 4) * 10 + tri16(tid & 15)];
+    else if (tid >= 64 && tid < 64 + 48) { const int t = tid - 64; S.gx[t >> 4][1][t & 15] = S.part[32 + (t >> 4) * 10 + tri16(t & 15)]; }
+  }
+  __syncthreads();
+  if (tid < 48) { entries[tid] = S.gx[tid >> 4][2][tid & 15]; entries[48 + tid] = S.gx[tid >> 4][1][tid & 15]; }
+}
+extern "C" int sdxpk_gram_x_check(const float* x1, const float* x2, float* terms, float* entries, hipStream_t st) {
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_gram_x_check), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PLds)) != hipSuccess) return -1;
+  hipLaunchKernelGGL(k_gram_x_check, dim3(1), dim3(NTH), sizeof(PLds), st, x1, x2, terms, entries);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// Test entry (tests/test_gpu_row_butterfly.py): one workgroup of NTH threads, in / ref / got are [N][NTH].  ref[i][t] = the sum of value i over
+// t's 16-lane DPP row as ONE plain tree per value - partners lane ^ 1, ^ 2, ^ 4, ^ 8, fetched with __shfl_xor (ds_bpermute: no DPP) - on
+// every lane; got[i][t] = what row_butterfly<N> left in lane t for value i - written by the lanes with (t & 3) == (i & 3), the others' slots
+// are not touched.
+template <int N>
+__global__ __launch_bounds__(NTH) void k_row_butterfly_check(const float* in, float* ref, float* got) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  float v[N], u[(N + 3) / 4];
+#pragma unroll
+  for (int i = 0; i < N; ++i) v[i] = in[i * NTH + tid];
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    float s = v[i];
+#pragma unroll
+    for (int m = 1; m < 16; m <<= 1) { float o = __shfl_xor(s, m, 64); asm volatile("" : "+v"(o)); s = s + o; }
+    ref[i * NTH + tid] = s;
+  }
+  row_butterfly<N>(v, u, lane);
+#pragma unroll
+  for (int j = 0; j < (N + 3) / 4; ++j)
+    if (4 * j + (lane & 3) < N) got[(4 * j + (lane & 3)) * NTH + tid] = u[j];
+}
+extern "C" int sdxpk_row_butterfly_check(const float* in, float* ref, float* got, int n, hipStream_t st) {
+  if (n == 12) hipLaunchKernelGGL(k_row_butterfly_check<12>, dim3(1), dim3(NTH), 0, st, in, ref, got);
+  else if (n == 30) hipLaunchKernelGGL(k_row_butterfly_check<30>, dim3(1), dim3(NTH), 0, st, in, ref, got);
+  else if (n == 48) hipLaunchKernelGGL(k_row_butterfly_check<48>, dim3(1), dim3(NTH), 0, st, in, ref, got);
+  else return -1;
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}

@@ -30,33 +30,44 @@ template <int CTRL, int BANK>
 __device__ __forceinline__ float dpp_mov(float old, float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v), CTRL, 0xF, BANK, false));
 }
-// the two halving levels + the two levels inside the 16-lane DPP row: u2[j] = sum over the row's lanes of value 4 j + (lane & 3)
+// v + (the value of the lane CTRL names), every lane of the row a valid source (quad_perm / row_ror): bound_ctrl set, so the move has no `old`
+// operand to materialise and folds into ONE v_add_f32_dpp
+template <int CTRL>
+__device__ __forceinline__ float dpp_pair(float v) {
+  asm("" : "+v"(v));   // (the ROUNDED value: a bare product must not be contracted with this add into an fma - the partner adds the rounded one)
+  return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+}
+// the two halving levels + the two levels inside the 16-lane DPP row: u2[j] = sum over the row's lanes of value 4 j + (lane & 3).
+// A halving level is written as BOTH pair sums - even value + its partner's, odd value + its partner's, one v_add_f32_dpp each, the source a
+// plain register - and one select of the sum this lane keeps: 3 instructions per pair.  (Written as two selects - what to keep, what to send -
+// in front of one add, the compiler fused the move into the add for fewer than half of the pairs, and the moves that stayed needed a zero `old`
+// register each: 129 VALU instructions for N = 30 stand-alone, 101 in this form.)  The lane that keeps a value adds the same two operands as
+// before - its own and its partner's - and IEEE addition commutes: the bits are those of the tree lane ^ 1, ^ 2, ^ 4, ^ 8 per value.
 template <int N>
 __device__ __forceinline__ void row_butterfly(const float (&v)[N], float (&u2)[(N + 3) / 4], int lane) {
   constexpr int N4 = (N + 3) / 4;
   const bool b0 = lane & 1, b1 = lane & 2;
   float u1[2 * N4];
 #pragma unroll
-  for (int j = 0; j < 2 * N4; ++j) {
-    const float e = 2 * j < N ? v[2 * j] : 0.0f, o = 2 * j + 1 < N ? v[2 * j + 1] : 0.0f;
-    const float keep = b0 ? o : e, send = b0 ? e : o;
-    u1[j] = keep + dpp_mov<0xB1, 0xF>(0.0f, send);           // partner lane ^ 1
+  for (int j = 0; j < 2 * N4; ++j) {                         // partner lane ^ 1 (quad_perm [1,0,3,2])
+    const float e = 2 * j < N ? dpp_pair<0xB1>(v[2 * j]) : 0.0f, o = 2 * j + 1 < N ? dpp_pair<0xB1>(v[2 * j + 1]) : 0.0f;
+    u1[j] = b0 ? o : e;
   }
 #pragma unroll
   for (int j = 0; j < N4; ++j) {
-    const float keep = b1 ? u1[2 * j + 1] : u1[2 * j], send = b1 ? u1[2 * j] : u1[2 * j + 1];
-    float t = keep + dpp_mov<0x4E, 0xF>(0.0f, send);         // partner lane ^ 2: t = quad sum of value 4 j + (lane & 3)
-    float x = dpp_mov<0x114, 0xA>(0.0f, t);                  // lane ^ 4: row_shr:4 into banks 1,3 ...
-    x = dpp_mov<0x104, 0x5>(x, t);                           // ... row_shl:4 into banks 0,2
+    const float e = dpp_pair<0x4E>(u1[2 * j]), o = 2 * (2 * j + 1) < N ? dpp_pair<0x4E>(u1[2 * j + 1]) : 0.0f;
+    float t = b1 ? o : e;                                    // partner lane ^ 2 (quad_perm [2,3,0,1]): t = quad sum of value 4 j + (lane & 3)
+    float x = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, t), 0x12C, 0xF, 0xF, true));   // lane ^ 4: row_ror:12 (lane + 4) is the partner of banks 0, 2 ...
+    x = dpp_mov<0x124, 0xA>(x, t);                           // ... row_ror:4 (lane - 4) into banks 1, 3
     t += x;
-    t += dpp_mov<0x128, 0xF>(0.0f, t);                       // lane ^ 8 (row_ror:8): sum over the 16-lane row
+    t = dpp_pair<0x128>(t);                                  // lane ^ 8 (row_ror:8): sum over the 16-lane row
     u2[j] = t;
   }
 }
 // N wave sums at once: the row butterfly, then the rows meet through v_permlane16_swap (partner lane ^ 16: rows 0 + 1, 2 + 3) and
 // v_permlane32_swap (lane ^ 32).  Every lane ends with u[j] = the whole wave's sum of value 4 j + (lane & 3).  The pairs of the six levels
 // are those of wave_sum's DPP tree (quad_perm, quad_perm, row_half_mirror, row_mirror, row_bcast15, row_bcast31) and IEEE addition
-// commutes, so u[j] equals wave_sum(v[4 j + (lane & 3)]) bit for bit - at N / 2, N / 4, N / 4, ... adds per level instead of N.
+// commutes, so u[j] equals wave_sum(v[4 j + (lane & 3)]) bit for bit - at N, N / 2, N / 4, N / 4, ... adds per level (and a select per pair on the first two) instead of N on all six.
 template <int N>
 __device__ __forceinline__ void wave_sums(const float (&v)[N], float (&u)[(N + 3) / 4], int lane) {
   // (opaque copies: the sums are those of the ROUNDED values - a value that is a bare product must not be contracted with the butterfly's first
