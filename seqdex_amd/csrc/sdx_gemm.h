@@ -37,6 +37,31 @@ struct GemmArgs {
   const float* H; int ldh;      // EPI 3: C = acc * ELU'(H[i][j]) with H the layer OUTPUT
   float* rowsum;                // EPI 4: rowsum[z * cz + i] = sum_k A(i, k) over the split (the bias gradient of a dY^T X product)
 };
+// The three products of an MLP layer with `in` inputs and `out` outputs over `rows` samples as GemmArgs (host side).  Dense arrays have
+// no leading dimension of their own: X [rows][in], W [out][in] as the flat parameter layout stores it, H / dX [rows][in]; a field a
+// form does not read stays zero.
+// forward, gemm<0, 0, 1> (ELU) / gemm<0, 0, 2> (none): Y [rows][out] (ldy) = act(X W^T + b), the whole reduction in one split
+static inline GemmArgs gemm_forward(const float* X, const float* W, const float* b, float* Y, int ldy, int rows, int out, int in) {
+  GemmArgs g = {};
+  g.A = X; g.lda = in; g.B = W; g.ldb = in; g.C = Y; g.ldc = ldy;
+  g.M = rows; g.N = out; g.K = in; g.kchunk = in; g.bias = b;
+  return g;
+}
+// data gradient, gemm<0, 1, 3>: dX = (dY W) * ELU'(H), dY [rows][out] (lddy), H the output of the layer below
+static inline GemmArgs gemm_data_grad(const float* dY, int lddy, const float* W, const float* H, float* dX, int rows, int out, int in) {
+  GemmArgs g = {};
+  g.A = dY; g.lda = lddy; g.B = W; g.ldb = in; g.C = dX; g.ldc = in;
+  g.M = rows; g.N = in; g.K = out; g.kchunk = out; g.H = H; g.ldh = in;
+  return g;
+}
+// weight gradient, gemm<1, 1, 4>: split z adds rows [z * rchunk, (z + 1) * rchunk) of G = dY^T X into part + z * pz, laid out as the flat
+// parameter layout has it, [G [out][in] | b [out]], b the row sums of dY^T.  One split with rchunk = rows writes the gradient itself
+static inline GemmArgs gemm_weight_grad(const float* dY, int lddy, const float* X, float* part, size_t pz, int rows, int rchunk, int out, int in) {
+  GemmArgs g = {};
+  g.A = dY; g.lda = lddy; g.B = X; g.ldb = in; g.C = part; g.ldc = in; g.cz = pz;
+  g.M = out; g.N = in; g.K = rows; g.kchunk = rchunk; g.rowsum = part + (size_t)out * in;
+  return g;
+}
 
 // EPI: 0 none, 1 bias + ELU, 2 bias, 3 times ELU'(H), 4 none + row sums of A.  WT: waves own (32 WT) x (32 WT) of a (64 WT)^2 tile.
 // The global loads of reduction chunk c+1 are issued before the MFMAs of chunk c (register double buffering).
@@ -161,14 +186,7 @@ __global__ __launch_bounds__(256) void k_gemm(GemmBatch gb) {
   }
 }
 
-// out[i] = sum_z part[z * pz + i] in fixed order
-static __global__ __launch_bounds__(256) void k_reduce_parts(const float* __restrict__ part, size_t pz, int S, size_t n, float* __restrict__ out) {
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-    float a = 0.0f;
-    for (int z = 0; z < S; ++z) a += part[(size_t)z * pz + i];
-    out[i] = a;
-  }
-}
+// out[q][i] = sum_z part[q][z * pz[q] + i], i < n[q], in fixed order, for up to three products (blockIdx.y = q)
 struct ReduceBatch { const float* part[3]; size_t pz[3]; size_t n[3]; float* out[3]; int S; };
 static __global__ __launch_bounds__(256) void k_reduce_parts3(ReduceBatch rb) {
   const int q = blockIdx.y;

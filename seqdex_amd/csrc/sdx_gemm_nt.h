@@ -50,6 +50,38 @@ struct NtArgs {
   float* rowsum;                 // EPI_TN: rowsum[z cz + i] = sum_k A[i][k] over the split
 };
 struct NtBatch { NtArgs a[3]; int splits; };
+// The products of an MLP layer with `in` inputs and `out` outputs over `rows` samples as NtArgs (host side).  Staged operands are in
+// the element type of the run; an optional copy is null when the run does not keep it; a field a form does not read stays zero.
+// forward, gemm_nt<BF, EPI_FWD>: Y = ELU(X W^T + b).  X [rows][inp] and W [out][inp] are padded with zeros to inp, a whole number of
+// chunks, and the whole reduction is one split.  Y leaves as fp32 Yf, element-type copy Yn (both [rows][out]) and / or Yt [out][ldt]
+static inline NtArgs nt_forward(const void* X, const void* W, int inp, const float* b, int rows, int out, float* Yf, void* Yn, void* Yt, int ldt) {
+  NtArgs g = {};
+  g.A = X; g.lda = inp; g.B = W; g.ldb = inp; g.M = rows; g.N = out; g.K = inp; g.kchunk = inp;
+  g.Cf = Yf; g.ldc = out; g.Cn = Yn; g.ldn = out; g.Ct = Yt; g.ldt = ldt; g.bias = b;
+  return g;
+}
+// data gradient, gemm_nt<BF, EPI_NN>: dX = (dY W) * ELU'(H).  dY [rows][out], Wt [in][out] the transposed weights, H [rows][in] the output
+// of the layer below; dX leaves as dXn [rows][in] and / or dXt [in][ldt], the latter multiplied from Ht [in][ldt] (null with dXt)
+static inline NtArgs nt_data_grad(const void* dY, const void* Wt, const void* H, const void* Ht, int rows, int out, int in, void* dXn, void* dXt, int ldt) {
+  NtArgs g = {};
+  g.A = dY; g.lda = out; g.B = Wt; g.ldb = out; g.M = rows; g.N = in; g.K = out; g.kchunk = out;
+  g.Cn = dXn; g.ldn = in; g.Ct = dXt; g.ldt = ldt; g.H = H; g.ldh = in; g.Ht = Ht; g.ldht = ldt;
+  return g;
+}
+// weight gradient, gemm_nt<BF, EPI_TN>: split z adds rows [z * rchunk, (z + 1) * rchunk) of G = dY^T X into part + z * pz, laid out as the
+// flat parameter layout has it, [G [out][in] | b [out]], b the row sums of dY^T.  dYt [out][lddyt] and Xt [in][ldxt] are the transposed
+// copies, padded with zeros to rowsp rows, a whole number of chunks; rchunk is one too
+static inline NtArgs nt_weight_grad(const void* dYt, int lddyt, const void* Xt, int ldxt, float* part, size_t pz, int rowsp, int rchunk, int out, int in) {
+  NtArgs g = {};
+  g.A = dYt; g.lda = lddyt; g.B = Xt; g.ldb = ldxt; g.M = out; g.N = in; g.K = rowsp; g.kchunk = rchunk;
+  g.Cf = part; g.ldc = in; g.cz = pz; g.rowsum = part + (size_t)out * in;
+  return g;
+}
+// the same gradient as gemm_tt reads it (k_gemm_tt below), fp32 only: dY [rows][out] and X [rows][ldx] as the other products leave them,
+// no padding of the rows; rchunk a multiple of 32.  The fields are nt_weight_grad's: there lda / ldb stride over features, here over rows
+static inline NtArgs tt_weight_grad(const float* dY, const void* X, int ldx, float* part, size_t pz, int rows, int rchunk, int out, int in) {
+  return nt_weight_grad(dY, out, X, ldx, part, pz, rows, rchunk, out, in);
+}
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -547,6 +579,12 @@ __global__ __launch_bounds__(256, 2) void k_gemm_tt(NtBatch nb, int nx, int ny, 
 // dt [Kp][ldt] (rows K .. Kp zeroed; columns R .. ldt are never written: they stay as allocated, i.e. zero).  64 x 64 tiles through LDS.
 struct StageArgs { const float* src; int lds, R, K, Kp; void* dn; int ldn; void* dt; int ldt; };
 struct StageBatch { StageArgs a[9]; };
+// dense src [R][K] -> dn [R][Kp] (or null) and dt [Kp][ldt] (or null)
+static inline StageArgs stage_args(const float* src, int R, int K, int Kp, void* dn, void* dt, int ldt) {
+  StageArgs a = {};
+  a.src = src; a.lds = K; a.R = R; a.K = K; a.Kp = Kp; a.dn = dn; a.ldn = Kp; a.dt = dt; a.ldt = ldt;
+  return a;
+}
 template <int BF>
 __global__ __launch_bounds__(256) void k_stage(StageBatch sb) {
   typedef typename std::conditional<BF != 0, __bf16, float>::type elem_t;

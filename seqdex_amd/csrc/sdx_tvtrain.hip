@@ -149,7 +149,7 @@ static void tv_forward(sdxtv_trainer* h, const float* x, int rows, float* const*
   const float* cur = x;
   int in = TV_IN;
   for (int l = 0; l < 4; ++l) {
-    GemmArgs g = {cur, in, h->p + h->woff[l], in, outs[l], TV_U[l], 0, rows, TV_U[l], in, in, h->p + h->boff[l], nullptr, 0, nullptr};
+    const GemmArgs g = gemm_forward(cur, h->p + h->woff[l], h->p + h->boff[l], outs[l], TV_U[l], rows, TV_U[l], in);
     gemm<0, 0, 1>(&g, 1, 1, st);                              // ELU after every layer, the output layer included (TV:45)
     cur = outs[l];
     in = TV_U[l];
@@ -173,10 +173,10 @@ extern "C" int sdxtv_step(sdxtv_handle h, float lr, void* stream) {
   for (int l = 3; l >= 0; --l) {
     const int Nl = TV_U[l], Kl = l == 0 ? TV_IN : TV_U[l - 1];
     const float* Xl = l == 0 ? h->x : h->h[l - 1];
-    GemmArgs gw = {h->dy[l], Nl, Xl, Kl, h->g + h->woff[l], Kl, 0, Nl, Kl, B, B, nullptr, nullptr, 0, h->g + h->boff[l]};
+    const GemmArgs gw = gemm_weight_grad(h->dy[l], Nl, Xl, h->g + h->woff[l], 0, B, B, Nl, Kl);   // one split: [W_l | b_l] of the gradient itself
     gemm<1, 1, 4>(&gw, 1, 1, st);                             // G_l = dY_l^T X_l, bias gradient = row sums
     if (l > 0) {
-      GemmArgs gx = {h->dy[l], Nl, h->p + h->woff[l], Kl, h->dy[l - 1], Kl, 0, B, Kl, Nl, Nl, nullptr, h->h[l - 1], Kl, nullptr};
+      const GemmArgs gx = gemm_data_grad(h->dy[l], Nl, h->p + h->woff[l], h->h[l - 1], h->dy[l - 1], B, Nl, Kl);
       gemm<0, 1, 3>(&gx, 1, 1, st);
     }
   }

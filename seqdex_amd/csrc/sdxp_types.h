@@ -96,8 +96,12 @@ struct SdxpDev {
   unsigned long long* ll; // [SDXP_LL_WORDS] (value, step tag) words exchanged between the CUs of the persistent update kernel
 };
 
+// trunk layer l of network net (0 actor, 1 critic, 2 central value) on the large-minibatch path: input width (layer 0: obs_dim / state_dim,
+// else units[l - 1]); the same rounded up to the NT path's chunk (K itself off that path); W_l and b_l in the flat parameter / gradient buffers
+struct SdxpBigLayer { int K, kp; size_t woff, boff; };
 // workspace of the large-minibatch update path (sdxp_bigmb.hip: laid out by sdxpk_big_setup through the handle's allocator)
 struct SdxpBigWs {
+  SdxpBigLayer layer[3][3];   // [net][l], filled once by sdxpk_big_setup
   float* h[3][3];             // trunk outputs  [MB][units[l]] in fp32 (the heads read l = 2; bf16 NT runs do not write l = 0, 1: see hn)
   float* dy[3][3];            // dLoss/d(pre-activation) [MB][units[l]] (NT path: only l = 2, written by the head kernels)
   float* mu;                  // [MB][24]
@@ -112,10 +116,9 @@ struct SdxpBigWs {
   int nt;                     // 1: the trunk products run on k_gemm_nt
   int nt_tile, fused_heads;   // SdxpOpts::nt_tile; 1: heads, losses and head gradients in k_big_heads, 0: the 13-launch head section
   int KC, MBp, Rp;            // chunk elements (32 fp32 / 64 bf16); MB rounded up to KC; dataset rows + 64 (row stride of the transposed inputs)
-  int kp[3][3];               // padded reduction length of forward layer l of net
-  void* xn[3];                // dataset inputs [R][kp0]: [0] observations (actor + critic), [1] cvx0, [2] cvx1
+  void* xn[3];                // dataset inputs [R][kp0] (kp0 = layer[.][0].kp): [0] observations (actor + critic), [1] cvx0, [2] cvx1
   void* xt[3];                // their transposes [kp0][Rp]
-  void* wn[3][3];             // weights [units[l]][kp[net][l]]
+  void* wn[3][3];             // weights [units[l]][layer[net][l].kp]
   void* wt[3][3];             // transposed weights [K_l][units[l]], l = 1, 2
   void* hn[3][2];             // layer outputs l = 0, 1 in the element type [MB][units[l]] (fp32 runs: the h arrays themselves)
   void* ht[3][2];             // ... transposed [units[l]][MBp]
