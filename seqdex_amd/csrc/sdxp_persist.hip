@@ -801,9 +801,14 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       if (wave == 0) {
         float v = 0.0f;
         if (tid < 24) {   // (net MB + s, c)
+          // rows 16 j .. 16 j + 15 of the column, j ascending: rows 4 w + 2 bc, 4 w + 2 bc + 1 of S.red, all sixteen requested in front of the first add
+          float r[2 * NWV];
+#pragma unroll
+          for (int w = 0; w < NWV; ++w) { r[2 * w] = S.red[4 * w + 2 * bc][bi]; r[2 * w + 1] = S.red[4 * w + 2 * bc + 1][bi]; }
+          asm volatile("" ::: "memory");
           float t = 0.0f;
 #pragma unroll
-          for (int w = 0; w < NWV; ++w) { t += S.red[4 * w + 2 * bc][bi]; t += S.red[4 * w + 2 * bc + 1][bi]; }   // rows 16 j .. 16 j + 15 of the column, j ascending
+          for (int j = 0; j < 2 * NWV; ++j) t += r[j];
           v = t * eg;
           S.dyown[bnet][bs][DY_L1 + bc] = v;
         }
@@ -911,9 +916,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       SDX_LDS_BARRIER();
       if (tid < 64) {                                 // column tid: rows of waves 0..3 (x3) or 4..7 (dY2)
         const int r0 = tid < 32 ? 0 : 2 * NWV;
-        float t = 0.0f;
-#pragma unroll
-        for (int w = 0; w < 2 * NWV; ++w) t += S.red[r0 + w][tid];
+        const float t = ordered_sum_ahead<2 * NWV, 64>(&S.red[r0][tid]);
         const int c = tid & 31, net = c / 10, e = c - net * 10;
         // entry e of the lower triangle -> both (hi, lo) and (lo, hi) of the 4x4 matrix
         const int hi = e < 1 ? 0 : (e < 3 ? 1 : (e < 6 ? 2 : 3)), lo = e - hi * (hi + 1) / 2;
@@ -965,9 +968,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       if (wave == 0) {
         float v = 0.0f;
         if (tid < 48) {
-          float t = 0.0f;
-#pragma unroll
-          for (int w = 0; w < 4 * NWV; ++w) t += S.red[w][tid];
+          const float t = ordered_sum_ahead<4 * NWV, 64>(&S.red[0][tid]);
           v = t * eg;
           S.dyown[enet][es][DY_L0 + ec] = v;
         }
@@ -1066,10 +1067,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       SDX_LDS_BARRIER();          // (rows_reduce, opened up: the stage between its two barriers occupies 32 threads ...)
       lq_peek<4>(LQ, LQ_G0 + lane, 64, pg0); pg0_issued = true;   // (0.7 us into the shadow: the words left their CUs 0.7 + 2.0 (phase E) us ago; the round trip ends with the shadow)
       if (tid < 32) {
-        float t = 0.0f;
-#pragma unroll
-        for (int w = 0; w < 4 * NWV; ++w) t += S.red[w][tid];
-        S.part[tid] = t;
+        S.part[tid] = ordered_sum_ahead<4 * NWV, 64>(&S.red[0][tid]);
       }
       // ... so this lane's layer-0 gradient elements are formed here, by every wave (dyown[.][.][DY_L0 ..] were published by the barrier above;
       // S.obs / S.cvx still hold this minibatch): 4 + 5 batches of four independent LDS loads instead of 13 dependent round trips on the chain

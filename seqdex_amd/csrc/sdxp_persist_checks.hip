@@ -253,3 +253,28 @@ extern "C" int sdxpk_row_butterfly_check(const float* in, float* ref, float* got
   else return -1;
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+// Test entry (tests/test_gpu_persist_ordered_sum.py): one workgroup of NTH threads, rows [4 NWV][64] go into S.red.  ref[n][c] (n = 0: 16 rows,
+// 1: 32 rows; c < 64): the plain serial loop, every row read through a volatile pointer so that each add waits for its own read - the form the
+// reductions of k_update_persistent had; got[n][c]: ordered_sum_ahead on the same rows.
+__global__ __launch_bounds__(NTH) void k_ordered_sum_check(const float* rows, float* ref, float* got) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  PLds& S = *reinterpret_cast<PLds*>(smem_raw);
+  const int tid = threadIdx.x;
+  for (int i = tid; i < 4 * NWV * 64; i += NTH) (&S.red[0][0])[i] = rows[i];
+  __syncthreads();
+  if (tid < 64) {
+    const volatile float* col = &S.red[0][tid];
+    float t = 0.0f;
+    for (int w = 0; w < 2 * NWV; ++w) t += col[w * 64];
+    ref[tid] = t;
+    for (int w = 2 * NWV; w < 4 * NWV; ++w) t += col[w * 64];
+    ref[64 + tid] = t;
+    got[tid] = ordered_sum_ahead<2 * NWV, 64>(&S.red[0][tid]);
+    got[64 + tid] = ordered_sum_ahead<4 * NWV, 64>(&S.red[0][tid]);
+  }
+}
+extern "C" int sdxpk_ordered_sum_check(const float* rows, float* ref, float* got, hipStream_t st) {
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_ordered_sum_check), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PLds)) != hipSuccess) return -1;
+  hipLaunchKernelGGL(k_ordered_sum_check, dim3(1), dim3(NTH), sizeof(PLds), st, rows, ref, got);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}

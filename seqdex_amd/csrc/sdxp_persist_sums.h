@@ -136,6 +136,21 @@ __device__ __forceinline__ void fwd2_store(PLds& S, const float (&u)[3], int wav
     for (int net = 0; net < 3; ++net) S.fpart[(net * MB + s) * NWV + wave] = u[net];
   }
 }
+// 0.0f + col[0] + col[STRIDE] + ... + col[(N - 1) STRIDE], added in ascending order - the bits of the serial loop `t += S.red[w][c]` - with all
+// N LDS reads requested in front of the first add.  Written as the plain loop, the compiler (at the kernel's register limit) requested two values,
+// waited for them with lgkmcnt(0), added, and only then requested the next two: N / 2 dependent LDS round trips between two barriers of a
+// reduction that every wave of the CU waits for.  The compiler barrier keeps the reads in front of the adds; the N values live only here.
+template <int N, int STRIDE>
+__device__ __forceinline__ float ordered_sum_ahead(const float* col) {
+  float r[N];
+#pragma unroll
+  for (int w = 0; w < N; ++w) r[w] = col[w * STRIDE];
+  asm volatile("" ::: "memory");
+  float t = 0.0f;
+#pragma unroll
+  for (int w = 0; w < N; ++w) t += r[w];
+  return t;
+}
 template <int N4>
 __device__ __forceinline__ void rows_store(PLds& S, const float (&u2)[N4], int off, int wave, int lane) {
   if ((lane & 15) < 4) {
@@ -148,12 +163,7 @@ __device__ __forceinline__ void rows_store(PLds& S, const float (&u2)[N4], int o
 // acknowledgement of the exchange words just published and the next minibatch's prefetched rows; nothing here is ordered through HBM
 __device__ __forceinline__ void rows_reduce(PLds& S, int n, float* out, int tid) {
   SDX_LDS_BARRIER();
-  if (tid < n) {
-    float t = 0.0f;
-#pragma unroll
-    for (int w = 0; w < 4 * NWV; ++w) t += S.red[w][tid];
-    out[tid] = t;
-  }
+  if (tid < n) out[tid] = ordered_sum_ahead<4 * NWV, 64>(&S.red[0][tid]);
   SDX_LDS_BARRIER();
 }
 // block-wide sums of N per-thread values (N <= 64); result in out[0..N).  Two "halving" butterfly levels (lane pairs keep the even /
