@@ -1,5 +1,5 @@
 // sdxp_device.h — device helpers shared by the PPO units (sdxp_rollout.hip, sdxp_update.hip, sdxp_multirank.hip, sdxp_persist.hip): ELU, the DPP wave sum
-// and the accessors of the rank-MB factor buffers of SdxpDev.
+// the accessors of the rank-MB factor buffers of SdxpDev, and the parameter map of the rank-MB kernels (trunk_slot, head_row, trunk_kmax).
 #pragma once
 #include "sdx_common.h"
 #include "sdxp_types.h"
@@ -48,3 +48,28 @@ __device__ __forceinline__ float dy_at(const SdxpDev& D, int net, int l, int par
   if (l == 2) return D.dy2[net][(size_t)par * MB * Nl + s * Nl + n];
   return D.dxacc[net][l][(size_t)par * MB * Nl + s * Nl + n] * elu_grad_from_out(D.x[net][l + 1][(size_t)par * MB * Nl + s * Nl + n]);
 }
+
+// ---- the parameter map of the rank-MB kernels, stated once.  Actor and critic share the actor-critic buffers (ac, ac_m, ac_v, ac_g; offsets
+// SdxpDev::off), the central value has its own (cv, ...; SdxpDev::coff).
+// Trunk layer l of network net: weight [N][K] at woff, bias [N] at boff of the network's parameter / moment / gradient buffers
+struct TrunkSlot { int K, N; size_t woff, boff; float *P, *M, *V, *G; };
+__device__ __forceinline__ TrunkSlot trunk_slot(const SdxpDev& D, int net, int l) {
+  // (the eight pointers are read, then chosen among: written as net == 2 ? D.cv : D.ac the compiler chooses the address first and the
+  // kernels' scalar preambles become chains of dependent loads)
+  float *const ac = D.ac, *const ac_m = D.ac_m, *const ac_v = D.ac_v, *const ac_g = D.ac_g, *const cv = D.cv, *const cv_m = D.cv_m, *const cv_v = D.cv_v, *const cv_g = D.cv_g;
+  return {(l == 0) ? (net == 2 ? D.state_dim : D.obs_dim) : D.units[l - 1], D.units[l],
+          net == 0 ? D.off.a_w[l] : net == 1 ? D.off.c_w[l] : D.coff.w[l], net == 0 ? D.off.a_b[l] : net == 1 ? D.off.c_b[l] : D.coff.b[l],
+          net == 2 ? cv : ac, net == 2 ? cv_m : ac_m, net == 2 ? cv_v : ac_v, net == 2 ? cv_g : ac_g};
+}
+// Head row `row`: rows 0 .. A-1 are mu, row A the critic's value, row A+1 the central value.  net: whose trunk feeds it; buf: 0 the
+// actor-critic buffers, 1 the central value's; weight [units[2]] at woff, bias at boff; col: the row's column of dhead [MB][34]
+struct HeadRow { int net, buf, col; size_t woff, boff; };
+__device__ __forceinline__ HeadRow head_row(const SdxpDev& D, int row) {
+  const int A = D.act_dim;
+  return {row < A ? 0 : (row == A ? 1 : 2), row <= A ? 0 : 1, row < A ? row : 32 + (row - A),
+          row < A ? D.off.mu_w + (size_t)row * D.units[2] : (row == A ? D.off.v_w : D.coff.v_w), row < A ? D.off.mu_b + row : (row == A ? D.off.v_b : D.coff.v_b)};
+}
+// launch shapes of the kernels that give a wave one weight row of trunk layer l (k_grad_layer, k_grad_layer_w, the trunk blocks of the
+// apply grid): the longest row among the three networks (the LDS image of the layer's input is sized by it), and the workgroups of four rows
+inline int trunk_kmax(const SdxpDev* D, int l) { return l == 0 ? (D->state_dim > D->obs_dim ? D->state_dim : D->obs_dim) : D->units[l - 1]; }
+__host__ __device__ inline int trunk_row_blocks(const SdxpDev& D, int l) { return 3 * ((D.units[l] + 3) / 4); }

@@ -24,7 +24,8 @@
 
 #include "sdx_common.h"
 #include "sdxp_launch.h"
-#include "sdxp_persist_exchange.h"   // u64, u32x4, load16 / store16: the words and the 16-byte access of the update kernel
+#include "sdxp_tagged_words.h"       // u32x4, load16 / store16: the 16-byte words and their access
+#include "sdxp_persist_exchange.h"   // u64: the 8-byte words of the update kernel
 
 namespace {
 constexpr int XNWG = 256, XNTH = 512;

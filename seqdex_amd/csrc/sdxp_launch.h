@@ -23,7 +23,7 @@ void sdxpk_store_rewards(const SdxpDev* D, int t, const float* rew, const int64_
 void sdxpk_value_head(const SdxpDev* D, float* out, hipStream_t st);
 void sdxpk_gae_only(const SdxpDev* D, const float* last_values, const int64_t* last_dones, hipStream_t st);
 void sdxpk_adv_norm(const SdxpDev* D, hipStream_t st);
-// sdxp_update.hip: the rank-MB step (minibatch_size 2 / 4 / 8; -1 for any other)
+// sdxp_update.hip: the rank-MB step (minibatch_size 2 / 4 / 8; -1 for any other); parameter addressing: trunk_slot / head_row of sdxp_device.h
 void sdxpk_begin_epoch(const SdxpDev* D, hipStream_t st);
 int sdxpk_prenorm(const SdxpDev* D, int mb_size, hipStream_t st);
 int sdxpk_update_begin(const SdxpDev* D, int mb_size, hipStream_t st);
@@ -31,7 +31,8 @@ int sdxpk_update_step(const SdxpDev* D, int mb_size, hipStream_t st);
 int sdxpk_update_flush_layers(const SdxpDev* D, int mb_size, hipStream_t st);
 int sdxpk_backward_explicit(const SdxpDev* D, int mb_size, hipStream_t st);
 int sdxpk_backward_factors(const SdxpDev* D, int mb_size, hipStream_t st);
-// sdxp_multirank.hip
+// sdxp_multirank.hip: what follows the exchange.  The rebuild from all ranks' factors is rebuild_row / head_elem there, stored by the first two
+// launchers' kernels and kept in registers by the fused one, whose grid-wide meeting is built from sdxp_tagged_words.h
 int sdxpk_grads_from_factors(const SdxpDev* D, int mb_size, hipStream_t st);
 int sdxpk_apply_factors(const SdxpDev* D, int mb_size, hipStream_t st);
 int sdxpk_apply_fused_prepare(const SdxpDev* D, int mb_size);
@@ -60,7 +61,7 @@ void sdxpk_big_step(const SdxpDev* D, const SdxpBigWs* ws, int mb, int me, hipSt
 int sdxpk_gemm_nt_launch(int bf, int epi, const NtArgs* gs, int count, int splits, int tile, hipStream_t st);
 int sdxpk_gemm_tt_launch(const NtArgs* gs, int count, int splits, const float* zeros, int tile, hipStream_t st);
 int sdxpk_gemm_launch(int at, int bt, int epi, int bf, const GemmArgs* gs, int count, int splits, int tile, hipStream_t st);
-// sdxp_exbench.hip
+// sdxp_exbench.hip (the 16-byte words of sdxp_tagged_words.h and the 8-byte words of sdxp_persist_exchange.h, timed bare)
 int sdxpk_exchange_bench(void* ll, long long* out, int words, int rounds, int fmt, int src, int pattern, unsigned tag0, hipStream_t st);
 int sdxpk_pingpong_bench(void* ll, long long* out, int peer, int rounds, unsigned tag0, hipStream_t st);
 }

@@ -1,14 +1,17 @@
 // sdxp_multirank.hip — the multi-rank optimiser step from the exchange on: the gradient rebuilt from every rank's factors, the bit-reproducible squared
 // norm, clip + Adam on flat gradients (all-reduced, rebuilt, or left by the GEMM step of sdxp_bigmb.hip: sdxpk_apply_flat) and the one-launch apply.  What
 // precedes the exchange (k_grad_layer / k_grad_heads, k_pack_factors) stays in sdxp_update.hip beside k_layer: in a unit that calls layer_input with cur = true only, the constant is propagated into it before inlining and their code changes.
+// Where a parameter lives is sdxp_device.h's to say (trunk_slot, head_row); the rebuild from fact_all is stated once (rebuild_row, head_elem)
+// for the kernels that store the flat gradient and for the one-launch apply that keeps it in registers; the grid both forms of the apply
+// share is apply_job; the words of the one-launch apply's meeting are sdxp_tagged_words.h's.
 #include "sdxp_device.h"
 #include "sdxp_launch.h"
 #include "sdxp_ppo_terms.h"
+#include "sdxp_tagged_words.h"
 #include <cstddef>
 
 // block-level sum of the squared-gradient contributions of this workgroup, written (no atomics) to the slot of this workgroup:
 // part[slot] for the actor-critic buffer, part[SDXP_SQN_STRIDE + slot] for the central value.  Every thread of the 256 calls it.
-typedef unsigned int tw_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void write_sqn_partials(float ss_ac, float ss_cv, float* part, int slot) {
   __shared__ float s_sq[2][4];
   const int tid = threadIdx.x;
@@ -21,30 +24,33 @@ __device__ __forceinline__ void write_sqn_partials(float ss_ac, float ss_cv, flo
   }
 }
 
+// ---- the SUM over ranks of the minibatch gradients rebuilt from fact_all, stated once: the kernels of the three-launch apply store what
+// these functions yield to the flat gradient, the one-launch apply keeps it in registers for its Adam.  Ranks in ascending order on every
+// rank, samples in ascending order within a rank: identical sums everywhere and in both forms.
+// Trunk layers: a workgroup has four rows of layer l of one network, a wave one row n, a lane its columns lane + 64 j (K <= 1024: 16 per lane)
+struct RowJob { int net, n; bool valid; TrunkSlot t; };
+__device__ __forceinline__ RowJob row_job(const SdxpDev& D, int l, int bidx) {   // workgroup bidx of the trunk_row_blocks(D, l) of layer l
+  const int blocks_per_net = (D.units[l] + 3) / 4;
+  const int net = bidx / blocks_per_net, n = (bidx % blocks_per_net) * 4 + ((int)threadIdx.x >> 6);
+  return {net, n, n < D.units[l], trunk_slot(D, net, l)};
+}
+// the accumulation: g[j] the gradient of weight (n, lane + 64 j), sb of the row's bias.  Every thread of the 256 calls it (LDS image of the input).
 template <int MB>
-__device__ __forceinline__ void grad_layer_w_body(const SdxpDev& D, int l, int bidx, float* part = nullptr, int slot = 0) {
+__device__ __forceinline__ void rebuild_row(const SdxpDev& D, int l, const RowJob& r, float (&g)[16], float& sb) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int Nl = D.units[l];
-  const int blocks_per_net = (Nl + 3) / 4;
-  const int net = bidx / blocks_per_net, n = (bidx % blocks_per_net) * 4 + wave;
-  const int K = (l == 0) ? (net == 2 ? D.state_dim : D.obs_dim) : D.units[l - 1];
-  float* G = net == 2 ? D.cv_g : D.ac_g;
-  const size_t woff = net == 0 ? D.off.a_w[l] : net == 1 ? D.off.c_w[l] : D.coff.w[l];
-  const size_t boff = net == 0 ? D.off.a_b[l] : net == 1 ? D.off.c_b[l] : D.coff.b[l];
-  const bool valid = n < Nl;
-  float g[16], sb = 0.0f;   // K <= 1024: 16 columns per lane
+  const int tid = threadIdx.x, lane = tid & 63, K = r.t.K, Nl = r.t.N;
+  sb = 0.0f;
 #pragma unroll
   for (int j = 0; j < 16; ++j) g[j] = 0.0f;
-  for (int r = 0; r < D.world; ++r) {      // ascending rank order on every rank: identical sums everywhere
-    const float* F = D.fact_all + (size_t)r * D.foff.total;
-    const float* gx = F + D.foff.x[net][l];
+  for (int rk = 0; rk < D.world; ++rk) {
+    const float* F = D.fact_all + (size_t)rk * D.foff.total;
+    const float* gx = F + D.foff.x[r.net][l];
     for (int i = tid; i < MB * K; i += 256) sm[i] = gx[i];
     __syncthreads();
-    if (valid) {
+    if (r.valid) {
       float dyn[MB];
 #pragma unroll
-      for (int s = 0; s < MB; ++s) { dyn[s] = F[D.foff.dy[net][l] + s * Nl + n]; sb += dyn[s]; }
+      for (int s = 0; s < MB; ++s) { dyn[s] = F[D.foff.dy[r.net][l] + s * Nl + r.n]; sb += dyn[s]; }
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
         const int k = lane + 64 * j;
@@ -56,61 +62,89 @@ __device__ __forceinline__ void grad_layer_w_body(const SdxpDev& D, int l, int b
     }
     __syncthreads();
   }
+}
+// this lane's share of the squared norm of the rank AVERAGE of the row
+__device__ __forceinline__ float row_sqn_share(const SdxpDev& D, const RowJob& r, const float (&g)[16], float sb) {
+  const int lane = threadIdx.x & 63;
+  const float sc = 1.0f / (float)D.world;
   float ss = 0.0f;
-  if (valid) {
-    const float sc = 1.0f / (float)D.world;
+  if (r.valid) {
 #pragma unroll
-    for (int j = 0; j < 16; ++j) { const int k = lane + 64 * j; if (k < K) { G[woff + (size_t)n * K + k] = g[j]; ss += (g[j] * sc) * (g[j] * sc); } }
-    if (lane == 0) { G[boff + n] = sb; ss += (sb * sc) * (sb * sc); }
+    for (int j = 0; j < 16; ++j) { if (lane + 64 * j < r.t.K) ss += (g[j] * sc) * (g[j] * sc); }
+    if (lane == 0) ss += (sb * sc) * (sb * sc);
   }
-  if (part) write_sqn_partials(net == 2 ? 0.0f : ss, net == 2 ? ss : 0.0f, part, slot);
+  return ss;
+}
+__device__ __forceinline__ void row_store(const RowJob& r, const float (&g)[16], float sb) {
+  const int lane = threadIdx.x & 63;
+  if (!r.valid) return;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) { const int k = lane + 64 * j; if (k < r.t.K) r.t.G[r.t.woff + (size_t)r.n * r.t.K + k] = g[j]; }
+  if (lane == 0) r.t.G[r.t.boff + r.n] = sb;
+}
+template <int MB>
+__device__ __forceinline__ void grad_layer_w_body(const SdxpDev& D, int l, int bidx, float* part = nullptr, int slot = 0) {
+  const RowJob r = row_job(D, l, bidx);
+  float g[16], sb;
+  rebuild_row<MB>(D, l, r, g, sb);
+  row_store(r, g, sb);
+  if (!part) return;
+  const float ss = row_sqn_share(D, r, g, sb);
+  write_sqn_partials(r.net == 2 ? 0.0f : ss, r.net == 2 ? ss : 0.0f, part, slot);
 }
 template <int MB>
 __global__ __launch_bounds__(256) void k_grad_layer_w(SdxpDev D, int l) { grad_layer_w_body<MB>(D, l, blockIdx.x); }
+// Heads: this thread's element of the head gradient.  i: an index into the main slice [A + 2 rows][units[2]], or past it; t: the thread's
+// place among the tails that the last heads block adds (0 .. A + 1 the rows' biases, 64 .. 64 + A - 1 logstd, 128 the SUM of the ranks'
+// minibatch KL - no parameter: it goes where sdxp_apply(0, -INFINITY) and the LR rule look for it), -1 elsewhere
+struct HeadElem { int buf; bool kl; size_t idx; float g; };   // buf: HeadRow::buf, -1: this thread has none; idx: into the buffer's flat gradient
 template <int MB>
-__device__ __forceinline__ void grad_heads_w_body(const SdxpDev& D, int hb, int nhb, float* part = nullptr, int slot = 0) {   // block hb of nhb; the last one also does the tails
-  const int tid = threadIdx.x, U = D.units[2], A = D.act_dim, W = D.world;
+__device__ __forceinline__ HeadElem head_elem(const SdxpDev& D, int i, int t) {
+  const int U = D.units[2], A = D.act_dim, W = D.world;
   const size_t T = D.foff.total;
-  const float sc = 1.0f / (float)W;
-  float ss_ac = 0.0f, ss_cv = 0.0f;
-  for (int i = hb * 256 + tid; i < (A + 2) * U; i += nhb * 256) {
-    const int row = i / U, k = i % U;
-    const int net = row < A ? 0 : (row == A ? 1 : 2);
-    float g = 0.0f;
+  HeadElem e = {-1, false, 0, 0.0f};
+  if (i < (A + 2) * U) {
+    const HeadRow hr = head_row(D, i / U);
+    const int k = i % U;
     for (int r = 0; r < W; ++r) {
       const float* F = D.fact_all + r * T;
       const float* dh = F + D.foff.dh;
-      const float* h = F + D.foff.h[net];
-      for (int s = 0; s < MB; ++s) g += (row < A ? dh[s * 34 + row] : dh[s * 34 + 32 + (row - A)]) * h[s * U + k];
+      const float* h = F + D.foff.h[hr.net];
+      for (int s = 0; s < MB; ++s) e.g += dh[s * 34 + hr.col] * h[s * U + k];
     }
-    if (row < A) D.ac_g[D.off.mu_w + (size_t)row * U + k] = g;
-    else if (row == A) D.ac_g[D.off.v_w + k] = g;
-    else D.cv_g[D.coff.v_w + k] = g;
-    if (row <= A) ss_ac += (g * sc) * (g * sc); else ss_cv += (g * sc) * (g * sc);
-  }
-  if (hb != nhb - 1) { if (part) write_sqn_partials(ss_ac, ss_cv, part, slot); return; }
-  if (tid < A + 2) {
-    float g = 0.0f;
+    e.buf = hr.buf; e.idx = hr.woff + k;
+  } else if (t >= 0 && t < A + 2) {
+    const HeadRow hr = head_row(D, t);
     for (int r = 0; r < W; ++r) {
       const float* dh = D.fact_all + r * T + D.foff.dh;
-      for (int s = 0; s < MB; ++s) g += tid < A ? dh[s * 34 + tid] : dh[s * 34 + 32 + (tid - A)];
+      for (int s = 0; s < MB; ++s) e.g += dh[s * 34 + hr.col];
     }
-    if (tid < A) D.ac_g[D.off.mu_b + tid] = g;
-    else if (tid == A) D.ac_g[D.off.v_b] = g;
-    else D.cv_g[D.coff.v_b] = g;
-    if (tid <= A) ss_ac += (g * sc) * (g * sc); else ss_cv += (g * sc) * (g * sc);
+    e.buf = hr.buf; e.idx = hr.boff;
+  } else if (t >= 64 && t < 64 + A) {
+    for (int r = 0; r < W; ++r) e.g += D.fact_all[r * T + D.foff.dls + (t - 64)];
+    e.buf = 0; e.idx = D.off.logstd + (t - 64);
+  } else if (t == 128) {
+    for (int r = 0; r < W; ++r) e.g += D.fact_all[r * T + D.foff.kl];
+    e.buf = 0; e.kl = true; e.idx = D.g_tail;
   }
-  if (tid >= 64 && tid < 64 + A) {
-    float g = 0.0f;
-    for (int r = 0; r < W; ++r) g += D.fact_all[r * T + D.foff.dls + (tid - 64)];
-    D.ac_g[D.off.logstd + (tid - 64)] = g;
-    ss_ac += (g * sc) * (g * sc);
-  }
-  if (tid == 128) {   // SUM of the ranks' minibatch KL, where sdxp_apply(0, -INFINITY) looks for it
-    float kl = 0.0f;
-    for (int r = 0; r < W; ++r) kl += D.fact_all[r * T + D.foff.kl];
-    D.ac_g[D.g_tail] = kl;
-  }
+  return e;
+}
+// the element's share of the squared norms of the rank average (write_sqn_partials' two sums)
+__device__ __forceinline__ void head_sqn_share(const SdxpDev& D, const HeadElem& e, float& ss_ac, float& ss_cv) {
+  const float sc = 1.0f / (float)D.world;
+  if (e.buf < 0 || e.kl) return;
+  if (e.buf) ss_cv += (e.g * sc) * (e.g * sc); else ss_ac += (e.g * sc) * (e.g * sc);
+}
+template <int MB>
+__device__ __forceinline__ void grad_heads_w_body(const SdxpDev& D, int hb, int nhb, float* part = nullptr, int slot = 0) {   // block hb of nhb; the last one also does the tails
+  const int tid = threadIdx.x, n_main = (D.act_dim + 2) * D.units[2];
+  float ss_ac = 0.0f, ss_cv = 0.0f;
+  auto store = [&](const HeadElem& e) {
+    if (e.buf >= 0) (e.buf ? D.cv_g : D.ac_g)[e.idx] = e.g;
+    head_sqn_share(D, e, ss_ac, ss_cv);
+  };
+  for (int i = hb * 256 + tid; i < n_main; i += nhb * 256) store(head_elem<MB>(D, i, -1));
+  if (hb == nhb - 1) store(head_elem<MB>(D, n_main, tid));
   if (part) write_sqn_partials(ss_ac, ss_cv, part, slot);
 }
 template <int MB>
@@ -170,16 +204,26 @@ __global__ void k_apply_fin(SdxpDev D, int which, float kl_host) {
 
 // ---- the factor path's "apply" in four launches: every gradient block of the three layers and the heads at once, the squared
 // norms of both flat gradients, clip + Adam of both networks, the step counters / LR rule
+// The grid of k_grad_all_w / k_apply_factors_fused: the trunk_row_blocks of layers 0, 1, 2, then the heads blocks (one main-slice element
+// per thread, + one block for the tails).  Workgroup b is block ApplyJob::b of trunk layer l, or (l = -1) heads block b; heads0: the first heads block
+struct ApplyJob { int l, b, heads0; };
+__host__ __device__ inline ApplyJob apply_job(const SdxpDev& D, int b) {
+  const int heads0 = trunk_row_blocks(D, 0) + trunk_row_blocks(D, 1) + trunk_row_blocks(D, 2);
+  int l = 0;
+  for (; l < 3 && b >= trunk_row_blocks(D, l); ++l) b -= trunk_row_blocks(D, l);
+  return {l < 3 ? l : -1, b, heads0};
+}
+struct ApplyGrid { int nb, Kmax; };
+static ApplyGrid apply_grid(const SdxpDev* D) {
+  const int nhb = ((D->act_dim + 2) * D->units[2] + 255) / 256 + 1;
+  return {apply_job(*D, 0).heads0 + nhb, D->units[0] > D->state_dim ? D->units[0] : D->state_dim};
+}
 template <int MB>
 __global__ __launch_bounds__(256) void k_grad_all_w(SdxpDev D, int with_norm) {
-  const int nb0 = 3 * ((D.units[0] + 3) / 4), nb1 = 3 * ((D.units[1] + 3) / 4), nb2 = 3 * ((D.units[2] + 3) / 4);
   float* part = with_norm ? D.sqn_part : nullptr;      // squared-norm contribution of every workgroup (the gradients are still in registers)
-  int b = blockIdx.x, l;
-  if (b < nb0) l = 0;
-  else if (b < nb0 + nb1) { l = 1; b -= nb0; }
-  else if (b < nb0 + nb1 + nb2) { l = 2; b -= nb0 + nb1; }
-  else { grad_heads_w_body<MB>(D, b - (nb0 + nb1 + nb2), (int)gridDim.x - (nb0 + nb1 + nb2), part, blockIdx.x); return; }
-  grad_layer_w_body<MB>(D, l, b, part, blockIdx.x);
+  const ApplyJob job = apply_job(D, blockIdx.x);
+  if (job.l < 0) grad_heads_w_body<MB>(D, job.b, (int)gridDim.x - job.heads0, part, blockIdx.x);
+  else grad_layer_w_body<MB>(D, job.l, job.b, part, blockIdx.x);
 }
 __global__ __launch_bounds__(256) void k_sqnorm2(SdxpDev D, float scale) {
   const int which = blockIdx.y;
@@ -218,12 +262,6 @@ __global__ void k_apply_fin2(SdxpDev D) {
   ppo_adam_advance(*ctl, 0);
   ppo_lr_advance(*ctl, D, D.ac_g[D.g_tail] / (float)ctl->world);
 }
-// grid of k_grad_all_w / k_apply_factors_fused: four trunk-layer rows of one network per workgroup, then nhb head blocks (one output per thread, + one for the tails)
-struct ApplyGrid { int nb, Kmax; };
-static ApplyGrid apply_grid(const SdxpDev* D) {
-  const int nhb = ((D->act_dim + 2) * D->units[2] + 255) / 256 + 1;
-  return {3 * ((D->units[0] + 3) / 4) + 3 * ((D->units[1] + 3) / 4) + 3 * ((D->units[2] + 3) / 4) + nhb, D->units[0] > D->state_dim ? D->units[0] : D->state_dim};
-}
 template <int MB>
 static void launch_apply_factors(const SdxpDev* D, hipStream_t st) {
   const ApplyGrid g = apply_grid(D);
@@ -243,9 +281,28 @@ static void launch_apply_factors(const SdxpDev* D, hipStream_t st) {
 // stores (vmcnt(0)) before the relaxed agent-scope ticket increment, consumers read them with agent-scope loads after the ticket completes.
 // A workgroup that waits too long raises the fail flag (bar[SDXP_BAR_APPLY_FAIL]) and every later launch returns at once: sdxp_update_status reports it
 // and the handle goes back to the three-launch form.
+// The meeting's words are (share_ac, share_cv, 0, tag) in the buffer Q.  Wave-uniform retry until every word idx0 + i * stride < limit carries
+// `tag`; x / y: the words' payloads added in ascending i.  false (and *failflag set) if they do not arrive.
+__device__ __forceinline__ bool tw_gather_sum(__amdgpu_buffer_rsrc_t Q, unsigned idx0, unsigned stride, unsigned limit, unsigned tag, float& x, float& y, unsigned* failflag) {
+  unsigned spins = 0;
+  for (;;) {
+    u32x4 w[SDXP_SQN_STRIDE / 256];
+#pragma unroll
+    for (int i = 0; i < SDXP_SQN_STRIDE / 256; ++i) { const unsigned idx = idx0 + i * stride; w[i] = load16(Q, idx < limit ? idx : idx0); }
+    bool good = true;
+    x = 0.0f; y = 0.0f;
+#pragma unroll
+    for (int i = 0; i < SDXP_SQN_STRIDE / 256; ++i) {
+      const bool act = idx0 + i * stride < limit;
+      good = good && (!act || lq_ok(w[i], tag));
+      if (act) { x += __uint_as_float(w[i].x); y += __uint_as_float(w[i].y); }
+    }
+    if (__builtin_amdgcn_ballot_w64(!good) == 0) return true;
+    SDX_POLL_SLEEP_OR_GIVE_UP(spins, failflag)
+  }
+}
 template <int MB>
 __global__ __launch_bounds__(256, 6) void k_apply_factors_fused(SdxpDev D, unsigned* __restrict__ gen, unsigned* __restrict__ failflag) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
   __shared__ float s_sq[2][4], s_n2[2];
   __shared__ int s_ok;
   __shared__ unsigned s_gen;
@@ -253,117 +310,34 @@ __global__ __launch_bounds__(256, 6) void k_apply_factors_fused(SdxpDev D, unsig
   SdxpCtrl* ctl = D.ctrl;
   if (tid == 0) { s_ok = __hip_atomic_load(failflag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0; s_gen = __hip_atomic_load(gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
   __syncthreads();
-  const unsigned tag_gen = s_gen;   // launches of this handle so far (device counter: launches replayed from a hipGraph see it grow); workgroup 0 advances it behind the meeting
+  const unsigned tag = s_gen + 1u;   // s_gen: launches of this handle so far (device counter: launches replayed from a hipGraph see it grow); workgroup 0 advances it behind the meeting
   if (!s_ok) return;   // an earlier launch timed out at its ticket: nothing is applied until the host has looked (sdxp_update_status)
   // ---- what this launch needs of the control block (read before the ticket: workgroup 0 advances the block behind it)
   const float inv_w = 1.0f / (float)ctl->world;
   const PpoAdamScales sa = ppo_adam_scales(ctl->ac_lr, ctl->ac_t + 1), sv = ppo_adam_scales(ctl->cv_lr, ctl->cv_t + 1);
   const float ac_lr_bc1 = sa.lr_bc1, ac_isq = sa.isq_bc2, cv_lr_bc1 = sv.lr_bc1, cv_isq = sv.isq_bc2;
-  // ---- the job of this workgroup (the map of k_grad_all_w): four rows of a trunk layer of one network, or a slice of the heads
-  const int nb0 = 3 * ((D.units[0] + 3) / 4), nb1 = 3 * ((D.units[1] + 3) / 4), nb2 = 3 * ((D.units[2] + 3) / 4);
-  int b = blockIdx.x, l = -1;
-  if (b < nb0) l = 0;
-  else if (b < nb0 + nb1) { l = 1; b -= nb0; }
-  else if (b < nb0 + nb1 + nb2) { l = 2; b -= nb0 + nb1; }
-  else b -= nb0 + nb1 + nb2;
-  const int W = D.world;
-  const float sc = 1.0f / (float)W;
+  // ---- the job of this workgroup: four rows of a trunk layer of one network (g, sb), or a slice of the heads (at most one element per thread)
+  const ApplyJob job = apply_job(D, blockIdx.x);
   float g[16], sb = 0.0f, ss_ac = 0.0f, ss_cv = 0.0f;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) g[j] = 0.0f;
-  // layer job
-  int net = 0, n = 0, K = 0;
-  size_t woff = 0, boff = 0;
-  bool valid = false;
-  // heads job: at most one element per thread (main slice, or - last heads block - a bias / logstd entry)
-  float gh = 0.0f;
-  int h_which = -1;     // 0: actor-critic buffer, 1: central value, -1: none
-  size_t h_idx = 0;
-  if (l >= 0) {
-    const int Nl = D.units[l];
-    const int blocks_per_net = (Nl + 3) / 4;
-    net = b / blocks_per_net; n = (b % blocks_per_net) * 4 + wave;
-    K = (l == 0) ? (net == 2 ? D.state_dim : D.obs_dim) : D.units[l - 1];
-    woff = net == 0 ? D.off.a_w[l] : net == 1 ? D.off.c_w[l] : D.coff.w[l];
-    boff = net == 0 ? D.off.a_b[l] : net == 1 ? D.off.c_b[l] : D.coff.b[l];
-    valid = n < Nl;
-    for (int r = 0; r < W; ++r) {      // ascending rank order on every rank: identical sums everywhere (grad_layer_w_body's arithmetic)
-      const float* F = D.fact_all + (size_t)r * D.foff.total;
-      const float* gx = F + D.foff.x[net][l];
-      for (int i = tid; i < MB * K; i += 256) sm[i] = gx[i];
-      __syncthreads();
-      if (valid) {
-        float dyn[MB];
-#pragma unroll
-        for (int s = 0; s < MB; ++s) { dyn[s] = F[D.foff.dy[net][l] + s * Nl + n]; sb += dyn[s]; }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          const int k = lane + 64 * j;
-          if (k < K) {
-#pragma unroll
-            for (int s = 0; s < MB; ++s) g[j] += dyn[s] * sm[s * K + k];
-          }
-        }
-      }
-      __syncthreads();
-    }
-    float ss = 0.0f;
-    if (valid) {
-#pragma unroll
-      for (int j = 0; j < 16; ++j) { const int k = lane + 64 * j; if (k < K) ss += (g[j] * sc) * (g[j] * sc); }
-      if (lane == 0) ss += (sb * sc) * (sb * sc);
-    }
-    if (net == 2) ss_cv = ss; else ss_ac = ss;
+  RowJob row = {};
+  HeadElem he = {-1, false, 0, 0.0f};
+  if (job.l >= 0) {
+    row = row_job(D, job.l, job.b);
+    rebuild_row<MB>(D, job.l, row, g, sb);
+    const float ss = row_sqn_share(D, row, g, sb);
+    if (row.net == 2) ss_cv = ss; else ss_ac = ss;
   } else {
-    const int hb = b, nhb = (int)gridDim.x - (nb0 + nb1 + nb2);
-    const int U = D.units[2], A = D.act_dim;
-    const size_t T = D.foff.total;
-    const int i = hb * 256 + tid;
-    if (i < (A + 2) * U) {
-      const int row = i / U, k = i % U;
-      const int hnet = row < A ? 0 : (row == A ? 1 : 2);
-      for (int r = 0; r < W; ++r) {
-        const float* F = D.fact_all + r * T;
-        const float* dh = F + D.foff.dh;
-        const float* h = F + D.foff.h[hnet];
-        for (int s = 0; s < MB; ++s) gh += (row < A ? dh[s * 34 + row] : dh[s * 34 + 32 + (row - A)]) * h[s * U + k];
-      }
-      if (row < A) { h_which = 0; h_idx = D.off.mu_w + (size_t)row * U + k; }
-      else if (row == A) { h_which = 0; h_idx = D.off.v_w + k; }
-      else { h_which = 1; h_idx = D.coff.v_w + k; }
-      if (row <= A) ss_ac += (gh * sc) * (gh * sc); else ss_cv += (gh * sc) * (gh * sc);
-    }
-    if (hb == nhb - 1) {   // the tails: head biases, logstd, the ranks' KL sum
-      if (tid < A + 2) {
-        for (int r = 0; r < W; ++r) {
-          const float* dh = D.fact_all + r * T + D.foff.dh;
-          for (int s = 0; s < MB; ++s) gh += tid < A ? dh[s * 34 + tid] : dh[s * 34 + 32 + (tid - A)];
-        }
-        if (tid < A) { h_which = 0; h_idx = D.off.mu_b + tid; }
-        else if (tid == A) { h_which = 0; h_idx = D.off.v_b; }
-        else { h_which = 1; h_idx = D.coff.v_b; }
-        if (tid <= A) ss_ac += (gh * sc) * (gh * sc); else ss_cv += (gh * sc) * (gh * sc);
-      }
-      if (tid >= 64 && tid < 64 + A) {
-        for (int r = 0; r < W; ++r) gh += D.fact_all[r * T + D.foff.dls + (tid - 64)];
-        h_which = 0; h_idx = D.off.logstd + (tid - 64);
-        ss_ac += (gh * sc) * (gh * sc);
-      }
-      if (tid == 128) {   // SUM of the ranks' minibatch KL, where the LR rule (and sdxp_apply(0, -INFINITY)) looks for it
-        float kl = 0.0f;
-        for (int r = 0; r < W; ++r) kl += D.fact_all[r * T + D.foff.kl];
-        __hip_atomic_store(&D.ac_g[D.g_tail], kl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
+    he = head_elem<MB>(D, job.b * 256 + tid, job.b == (int)gridDim.x - job.heads0 - 1 ? tid : -1);
+    if (he.kl) __hip_atomic_store(&D.ac_g[he.idx], he.g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    head_sqn_share(D, he, ss_ac, ss_cv);
   }
   // ---- this workgroup's shares of the two squared norms (write_sqn_partials' order), then the grid-wide meeting: NO atomics.
   // (First versions: one device-scope counter - 1 380 arrivals served one after the other at the memory side: 105 us per optimiser step
   // against 68 with three launches; 64 counters: 87 us, the kernel alone 46.5 us against 7.8 + 18.4 + 4.7 for the three.)  The meeting is
-  // two hops of tagged 16-byte words, the persistent kernel's exchange discipline (write-through store, polling agent-scope loads, the
-  // tag - spread and folded with the payload so that a torn word is polled again - in the last dword), laid out so that the sums are
-  // k_adam3's to the bit: every workgroup publishes (share_ac, share_cv); workgroup w < 4 plays wave w of k_adam3's fold - lane l adds
-  // the shares 64 w + l + 256 k in ascending k, then wave_sum - and publishes that wave's sum; every workgroup gathers the four sums
-  // and adds them as (s0 + s1) + (s2 + s3).
+  // two hops of tagged 16-byte words, the persistent kernel's exchange discipline (sdxp_tagged_words.h: write-through store, polling
+  // agent-scope loads, a torn word polled again), laid out so that the sums are k_adam3's to the bit: every workgroup publishes
+  // (share_ac, share_cv); workgroup w < 4 plays wave w of k_adam3's fold - lane l adds the shares 64 w + l + 256 k in ascending k, then
+  // wave_sum - and publishes that wave's sum; every workgroup gathers the four sums and adds them as (s0 + s1) + (s2 + s3).
   ss_ac = wave_sum(ss_ac); ss_cv = wave_sum(ss_cv);
   if (lane == 0) { s_sq[0][wave] = ss_ac; s_sq[1][wave] = ss_cv; }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the KL word of thread 128 has left before the barrier that precedes this workgroup's word
@@ -371,49 +345,17 @@ __global__ __launch_bounds__(256, 6) void k_apply_factors_fused(SdxpDev D, unsig
   if (wave == 0) {
     const __amdgpu_buffer_rsrc_t Q = __builtin_amdgcn_make_buffer_rsrc(D.sqn_part + SDXP_TW_OFF, 0, (SDXP_SQN_STRIDE + 64) * 16, 0x00020000);
     const unsigned nwg = gridDim.x;
-    const unsigned tagm = (tag_gen + 1u) * 0x9E3779B1u;
-    int ok = 1;
-    auto put = [&](unsigned idx, float x, float y) {
-      tw_u32x4 w; w.x = __float_as_uint(x); w.y = __float_as_uint(y); w.z = 0u; w.w = tagm ^ w.x ^ w.y;
-      __builtin_amdgcn_raw_buffer_store_b128(w, Q, idx * 16u, 0, 16);
-    };
-    // wave-uniform retry until every word idx0 + i * stride < limit carries this launch's tag; x / y: the words' payloads added in ascending i
-    auto gather_sum = [&](unsigned idx0, unsigned stride, unsigned limit, float& x, float& y) {
-      unsigned spins = 0;
-      for (;;) {
-        tw_u32x4 w[SDXP_SQN_STRIDE / 256];
-#pragma unroll
-        for (int i = 0; i < SDXP_SQN_STRIDE / 256; ++i) { const unsigned idx = idx0 + i * stride; w[i] = __builtin_amdgcn_raw_buffer_load_b128(Q, (idx < limit ? idx : idx0) * 16u, 0, 16); }
-        bool good = true;
-        x = 0.0f; y = 0.0f;
-#pragma unroll
-        for (int i = 0; i < SDXP_SQN_STRIDE / 256; ++i) {
-          const bool act = idx0 + i * stride < limit;
-          good = good && (!act || (w[i].w ^ w[i].x ^ w[i].y ^ w[i].z) == tagm);
-          if (act) { x += __uint_as_float(w[i].x); y += __uint_as_float(w[i].y); }
-        }
-        if (__builtin_amdgcn_ballot_w64(!good) == 0) return;
-        __builtin_amdgcn_s_sleep(1);
-        if ((++spins & 255u) == 0) {
-          const unsigned f = __hip_atomic_load(failflag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (spins > (1u << 20) || __builtin_amdgcn_readfirstlane(f) != 0) {
-            if (lane == 0) __hip_atomic_store(failflag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            ok = 0;
-            return;
-          }
-        }
-      }
-    };
-    if (lane == 0) put(blockIdx.x, (s_sq[0][0] + s_sq[0][1]) + (s_sq[0][2] + s_sq[0][3]), (s_sq[1][0] + s_sq[1][1]) + (s_sq[1][2] + s_sq[1][3]));
+    bool ok = true;
+    if (lane == 0) lq_store(Q, blockIdx.x, (s_sq[0][0] + s_sq[0][1]) + (s_sq[0][2] + s_sq[0][3]), (s_sq[1][0] + s_sq[1][1]) + (s_sq[1][2] + s_sq[1][3]), 0.0f, tag);
     if (blockIdx.x < 4) {   // wave blockIdx.x of k_adam3's fold
       float x, y;
       const unsigned t = 64u * blockIdx.x + lane;
-      gather_sum(t < nwg ? t : 0u, 256u, t < nwg ? nwg : 0u, x, y);
+      ok = tw_gather_sum(Q, t < nwg ? t : 0u, 256u, t < nwg ? nwg : 0u, tag, x, y, failflag);
       x = wave_sum(x); y = wave_sum(y);
-      if (ok && lane == 0) put(SDXP_SQN_STRIDE + blockIdx.x, x, y);
+      if (ok && lane == 0) lq_store(Q, SDXP_SQN_STRIDE + blockIdx.x, x, y, 0.0f, tag);
     }
     float x = 0.0f, y = 0.0f;
-    if (ok) gather_sum(SDXP_SQN_STRIDE + (lane < 4 ? lane : 0), 64u, SDXP_SQN_STRIDE + 4u, x, y);   // (one word per lane: 0.0f + the sum, exact)
+    ok = ok && tw_gather_sum(Q, SDXP_SQN_STRIDE + (lane < 4 ? lane : 0), 64u, SDXP_SQN_STRIDE + 4u, tag, x, y, failflag);   // (one word per lane: 0.0f + the sum, exact)
     const float x0 = lane0(x), y0 = lane0(y);
     const float x1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 1)), y1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, y), 1));
     const float x2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 2)), y2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, y), 2));
@@ -425,11 +367,13 @@ __global__ __launch_bounds__(256, 6) void k_apply_factors_fused(SdxpDev D, unsig
   const float n2_ac = s_n2[0], n2_cv = s_n2[1];
   const float clip_ac = ppo_clip_scale(D, sqrtf(n2_ac)), clip_cv = ppo_clip_scale(D, sqrtf(n2_cv));
   // ---- Adam of the elements this workgroup holds (k_adam3's arithmetic: adam1x(P, G * inv_w * clip, ...))
-  if (l >= 0) {
-    if (valid) {
-      float* P = net == 2 ? D.cv : D.ac; float* M = net == 2 ? D.cv_m : D.ac_m; float* V = net == 2 ? D.cv_v : D.ac_v;
+  if (job.l >= 0) {
+    if (row.valid) {
+      float *P = row.t.P, *M = row.t.M, *V = row.t.V;
+      const int net = row.net, n = row.n, K = row.t.K;
+      const size_t boff = row.t.boff;
       const float clip = net == 2 ? clip_cv : clip_ac, lr_bc1 = net == 2 ? cv_lr_bc1 : ac_lr_bc1, isq = net == 2 ? cv_isq : ac_isq;
-      const size_t row0 = woff + (size_t)n * K;
+      const size_t row0 = row.t.woff + (size_t)n * K;
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf) {   // eight columns per pass: their 24 loads in flight together, 80 VGPRs without a spill
         if (512 * hf >= K) break;
@@ -455,15 +399,16 @@ __global__ __launch_bounds__(256, 6) void k_apply_factors_fused(SdxpDev D, unsig
         M[boff + n] = bm; V[boff + n] = bv;
       }
     }
-  } else if (h_which >= 0) {
-    float* P = h_which ? D.cv : D.ac; float* M = h_which ? D.cv_m : D.ac_m; float* V = h_which ? D.cv_v : D.ac_v;
-    float hm = M[h_idx], hv = V[h_idx];
-    P[h_idx] = adam1x(P[h_idx], gh * inv_w * (h_which ? clip_cv : clip_ac), hm, hv, h_which ? cv_lr_bc1 : ac_lr_bc1, h_which ? cv_isq : ac_isq);
-    M[h_idx] = hm; V[h_idx] = hv;
+  } else if (he.buf >= 0 && !he.kl) {
+    const int c = he.buf;
+    float* P = c ? D.cv : D.ac; float* M = c ? D.cv_m : D.ac_m; float* V = c ? D.cv_v : D.ac_v;
+    float hm = M[he.idx], hv = V[he.idx];
+    P[he.idx] = adam1x(P[he.idx], he.g * inv_w * (c ? clip_cv : clip_ac), hm, hv, c ? cv_lr_bc1 : ac_lr_bc1, c ? cv_isq : ac_isq);
+    M[he.idx] = hm; V[he.idx] = hv;
   }
   // ---- k_apply_fin2's work, behind the ticket
   if (blockIdx.x == 0 && tid == 0) {
-    __hip_atomic_store(gen, tag_gen + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(gen, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     ctl->gn2_ac = n2_ac; ctl->gn2_cv = n2_cv;
     ppo_adam_advance(*ctl, 1);
     ppo_adam_advance(*ctl, 0);
@@ -496,11 +441,8 @@ extern "C" int sdxpk_apply_factors(const SdxpDev* D, int mb_size, hipStream_t st
 extern "C" int sdxpk_grads_from_factors(const SdxpDev* D, int mb_size, hipStream_t st) {
   return sdxp_for_minibatch(mb_size, [&](auto m) {
     constexpr int MB = decltype(m)::value;
-    for (int l = 0; l < 3; ++l) {
-      const int Nl = D->units[l];
-      const int Kmax = l == 0 ? (D->state_dim > D->obs_dim ? D->state_dim : D->obs_dim) : D->units[l - 1];
-      hipLaunchKernelGGL(k_grad_layer_w<MB>, dim3(3 * ((Nl + 3) / 4)), dim3(256), (size_t)MB * Kmax * sizeof(float), st, *D, l);
-    }
+    for (int l = 0; l < 3; ++l)
+      hipLaunchKernelGGL(k_grad_layer_w<MB>, dim3(trunk_row_blocks(*D, l)), dim3(256), (size_t)MB * trunk_kmax(D, l) * sizeof(float), st, *D, l);
     hipLaunchKernelGGL(k_grad_heads_w<MB>, dim3(1), dim3(256), 0, st, *D);
   });
 }

@@ -1,10 +1,11 @@
-// sdxp_persist_exchange.h - private to the persistent PPO update (included by sdxp_persist.hip; sdxp_exbench.hip borrows the word types and the
-// 16-byte access): the inter-CU exchange of k_update_persistent - tagged 16-byte words for the chain edges (lq_*), tagged 8-byte words for the
-// head matrix (ll_*), the layout of SdxpDev::ll, and the polling gathers with their give-up rule
+// sdxp_persist_exchange.h - private to the persistent PPO update (included by sdxp_persist.hip; sdxp_exbench.hip borrows u64): the inter-CU
+// exchange of k_update_persistent - tagged 16-byte words for the chain edges (lq_*: their word-level primitives are sdxp_tagged_words.h), tagged
+// 8-byte words for the head matrix (ll_*), the layout of SdxpDev::ll, and the polling gathers
 #pragma once
 #include "sdx_common.h"
 #include "sdxp_types.h"
 #include "sdxp_persist_lds.h"
+#include "sdxp_tagged_words.h"
 
 namespace {
 // ---- (value, tag) exchange words ("LL" protocol): one relaxed 8-byte store at agent scope carries the float and the tag of the
@@ -13,51 +14,14 @@ namespace {
 // overwritten before every CU has consumed it ("persistent update kernel").
 typedef unsigned long long u64;
 // The five edges on the step's dependency chain (x1, x2, x3, dY1 and the dY0 norm) travel as 16-BYTE words (v0, v1, v2, tag): the same
-// (sample, unit) of the THREE networks in one word, written and read by one dwordx4 access per lane (device scope, sc1) - the edge's time goes
-// with its word count ("the exchange floor").  A 16-byte access of one lane is not architecturally single-copy atomic (no
-// torn word in ~1e10 gathers checked by sdxp_exbench.hip; RCCL's LL128 protocol relies on the same hardware behaviour): the last dword carries
-// tag ^ fold(payload) (lq_fold below), so a torn word is rejected and polled again instead of being trusted to never occur.  The head matrix
-// (LL_HW: published a phase ahead, gathered row- and column-wise by different consumers) keeps its 8-byte words.
+// (sample, unit) of the THREE networks in one word (sdxp_tagged_words.h) - the edge's time goes with its word count (DESIGN.md section 4b,
+// "the exchange floor").  The head matrix (LL_HW: published a phase ahead, gathered row- and column-wise by different consumers) keeps its 8-byte words.
 // Layout of D.ll: 16-byte words LQ_* first, then the 8-byte head words at LL_HW (u64 index).
 constexpr unsigned LQ_X1 = 0, LQ_X2 = LQ_X1 + MB * U0, LQ_X3 = LQ_X2 + MB * U1, LQ_DY1 = LQ_X3 + MB * U2, LQ_DY0 = LQ_DY1 + MB * U1,
                    LQ_G0 = LQ_DY0 + MB * U0, LQ_END = LQ_G0 + 16 * NWG;   // LQ_G0: [CU]: the CU's share of layer 0's squared gradient norm, the 3 nets per word (round 6; rounds 4-5: 10 Gram entries per CU)
 constexpr size_t LL_HW = 2 * (size_t)LQ_END, LL_END = LL_HW + (ACT + 2) * U2;
 static_assert(LL_END <= SDXP_LL_WORDS, "exchange buffer too small");
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t lq_rsrc(void* ll) { return __builtin_amdgcn_make_buffer_rsrc(ll, 0, SDXP_LL_WORDS * 8, 0x00020000); }
-// one buffer_load / buffer_store_dwordx4 ... sc1 per lane of 16-byte word q (device scope, as the 8-byte agent-scope atomics lower to): the
-// compiler counts these in its s_waitcnt bookkeeping, unlike inline asm
-__device__ __forceinline__ u32x4 load16(__amdgpu_buffer_rsrc_t r, unsigned q) { return __builtin_amdgcn_raw_buffer_load_b128(r, q * 16u, 0, 16); }
-__device__ __forceinline__ void store16(__amdgpu_buffer_rsrc_t r, unsigned q, u32x4 v) { __builtin_amdgcn_raw_buffer_store_b128(v, r, q * 16u, 0, 16); }
-// Tearing is DETECTABLE: the last dword is not the bare tag but tag ^ fold(payload); a consumer accepts a word only when
-// last ^ fold(the payload it read) equals the tag it waits for.  A word whose dwords come from two different stores (new tag over a
-// stale payload or the reverse) fails the test unless the mixed payload folds to the same value (2^-32, or the stale dwords equal the new
-// ones - then nothing is lost) and is simply polled again, like a word that has not arrived.
-// (fold = x ^ y ^ z: one v_xor3_b32.  With rotations of y and z in it - to decorrelate equal values of two networks - the checks cost the
-// step 0.6 us on its dependent chain, 31.4 instead of 30.8; two networks' values that are equal before AND after a step are unchanged ones)
-// Tags advance by 1 per step, so the XOR of two consecutive bare tags is 1, 3, 7, ...: a torn word (new payload over a stale last dword) whose
-// payload fold moved by exactly that - one network's value changing by an ulp - would pass.  The tag is therefore spread over all
-// 32 bits before it meets the fold (lq_tag: one scalar multiply per gather, off the dependent chain): consecutive tags now differ in ~16
-// pseudo-random bit positions, which a slowly varying payload does not reproduce.
-__device__ __forceinline__ unsigned lq_fold(unsigned x, unsigned y, unsigned z) { return x ^ y ^ z; }
-__device__ __forceinline__ unsigned lq_tag(unsigned tag) { return tag * 0x9E3779B1u; }
-__device__ __forceinline__ bool lq_ok(const u32x4& w, unsigned tag) { return (w.w ^ lq_fold(w.x, w.y, w.z)) == lq_tag(tag); }
-__device__ __forceinline__ void lq_store(__amdgpu_buffer_rsrc_t q, unsigned idx, float a, float b, float c, unsigned tag) {
-  u32x4 w;
-  w.x = __float_as_uint(a); w.y = __float_as_uint(b); w.z = __float_as_uint(c); w.w = lq_tag(tag) ^ lq_fold(w.x, w.y, w.z);
-  store16(q, idx, w);
-}
-// The tail of one round of a polling gather that has not found all of its words: sleep, look at the fail flag every 256 spins, and after 2^20
-// of them, or when another wave has given up, set the flag and RETURN FALSE from the gather.  (A macro: as a function the kernel's branches change.)
-#define SDX_POLL_SLEEP_OR_GIVE_UP(spins, failflag)                                                       \
-  __builtin_amdgcn_s_sleep(1);                                                                           \
-  if ((++spins & 255u) == 0) {                                                                           \
-    const unsigned f = __hip_atomic_load(failflag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          \
-    if (spins > (1u << 20) || __builtin_amdgcn_readfirstlane(f) != 0) {                                  \
-      __hip_atomic_store(failflag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                      \
-      return false;                                                                                      \
-    }                                                                                                    \
-  }
 // first look at N packed words, issued some work ahead of where they are needed (lq_peek), and the test whether all of them already
 // carried `tag` (lq_take): when a shadow phase outlasts its exchange edge the words are there, and the round trip of the gather
 // (about 0.6 us) runs under the shadow's last piece of work instead of after it.  A miss falls back to the polling lq_gather.

@@ -1,6 +1,7 @@
 // sdxp_update.hip — the rank-MB optimiser step of the small-minibatch update as a sequence of kernels: the hipGraph path, and the
 // multi-rank steps up to what leaves the rank (flat gradients or packed factors; sdxp_multirank.hip has what follows the exchange).
-// sdxp_persist.hip is the same step as one persistent launch.
+// sdxp_persist.hip is the same step as one persistent launch.  Where a trunk layer or a head row lives in the flat parameter, moment and
+// gradient buffers is sdxp_device.h's to say (trunk_slot, head_row), and so is the launch shape of a row-per-wave kernel (trunk_kmax, trunk_row_blocks).
 // Update with the shipped minibatch_size 4 (YG:50,75): a minibatch gradient of a Linear layer is the rank-MB
 // product dY^T X, so it is never materialised:
 //   * the optimiser step of minibatch i is applied LAZILY inside the forward of minibatch i+1: the layer
@@ -66,14 +67,11 @@ __global__ __launch_bounds__(256) void k_layer(SdxpDev D, int l) {
   constexpr int rows_per_block = 4 * RPW;
   const int blocks_per_net = (Nl + rows_per_block - 1) / rows_per_block;
   const int net = blockIdx.x / blocks_per_net, blk = blockIdx.x % blocks_per_net;
-  const int K = (l == 0) ? (net == 2 ? D.state_dim : D.obs_dim) : D.units[l - 1];
-  const int K4 = K >> 2;
+  const TrunkSlot t = trunk_slot(D, net, l);
+  const int K = t.K, K4 = K >> 2;
   const bool pend = (net == 2 ? ctl->cv_pending : ctl->ac_pending) != 0;
-  float* P = net == 2 ? D.cv : D.ac;
-  float* Mo = net == 2 ? D.cv_m : D.ac_m;
-  float* Vo = net == 2 ? D.cv_v : D.ac_v;
-  const size_t woff = net == 0 ? D.off.a_w[l] : net == 1 ? D.off.c_w[l] : D.coff.w[l];
-  const size_t boff = net == 0 ? D.off.a_b[l] : net == 1 ? D.off.c_b[l] : D.coff.b[l];
+  float *P = t.P, *Mo = t.M, *Vo = t.V;
+  const size_t woff = t.woff, boff = t.boff;
   const float lr = net == 2 ? ctl->cv_lr_applied : ctl->ac_lr_applied;
   const float gs = net == 2 ? ctl->cv_gscale : ctl->ac_gscale;          // grad clip scale of the pending step
   const float bc1 = net == 2 ? ctl->cv_bc1 : ctl->ac_bc1, bc2 = net == 2 ? ctl->cv_bc2 : ctl->ac_bc2;
@@ -215,18 +213,15 @@ __global__ __launch_bounds__(1024) void k_head(SdxpDev D, int flush) {
       const int row = wave + 16 * j;
       w[j] = make_float4(0, 0, 0, 0); m[j] = w[j]; v[j] = w[j]; bias[j] = bm[j] = bv[j] = 0.0f;
       if (row < A + 2) {
-        const int net = row < A ? 0 : (row == A ? 1 : 2);
-        const float* P = net == 2 ? D.cv : D.ac;
-        const float* Mo = net == 2 ? D.cv_m : D.ac_m;
-        const float* Vo = net == 2 ? D.cv_v : D.ac_v;
-        const size_t woff = row < A ? D.off.mu_w + (size_t)row * U : (row == A ? D.off.v_w : D.coff.v_w);
-        const size_t boff = row < A ? D.off.mu_b + row : (row == A ? D.off.v_b : D.coff.v_b);
-        const bool pend = net == 2 ? cpend : apend;
-        w[j] = reinterpret_cast<const float4*>(P + woff)[lane];
-        bias[j] = P[boff];
-        if (pend) {
-          m[j] = reinterpret_cast<const float4*>(Mo + woff)[lane]; v[j] = reinterpret_cast<const float4*>(Vo + woff)[lane];
-          bm[j] = Mo[boff]; bv[j] = Vo[boff];
+        const HeadRow hr = head_row(D, row);
+        const float* P = hr.buf ? D.cv : D.ac;
+        const float* Mo = hr.buf ? D.cv_m : D.ac_m;
+        const float* Vo = hr.buf ? D.cv_v : D.ac_v;
+        w[j] = reinterpret_cast<const float4*>(P + hr.woff)[lane];
+        bias[j] = P[hr.boff];
+        if (hr.buf ? cpend : apend) {
+          m[j] = reinterpret_cast<const float4*>(Mo + hr.woff)[lane]; v[j] = reinterpret_cast<const float4*>(Vo + hr.woff)[lane];
+          bm[j] = Mo[hr.boff]; bv[j] = Vo[hr.boff];
         }
       }
     }
@@ -234,12 +229,12 @@ __global__ __launch_bounds__(1024) void k_head(SdxpDev D, int flush) {
     for (int j = 0; j < 2; ++j) {
       const int row = wave + 16 * j;
       if (row >= A + 2) continue;
-      const int net = row < A ? 0 : (row == A ? 1 : 2);
-      float* P = net == 2 ? D.cv : D.ac;
-      float* Mo = net == 2 ? D.cv_m : D.ac_m;
-      float* Vo = net == 2 ? D.cv_v : D.ac_v;
-      const size_t woff = row < A ? D.off.mu_w + (size_t)row * U : (row == A ? D.off.v_w : D.coff.v_w);
-      const size_t boff = row < A ? D.off.mu_b + row : (row == A ? D.off.v_b : D.coff.v_b);
+      const HeadRow hr = head_row(D, row);
+      const int net = hr.net;
+      float* P = hr.buf ? D.cv : D.ac;
+      float* Mo = hr.buf ? D.cv_m : D.ac_m;
+      float* Vo = hr.buf ? D.cv_v : D.ac_v;
+      const size_t woff = hr.woff, boff = hr.boff;
       const bool pend = net == 2 ? cpend : apend;
       const float lr_bc1 = net == 2 ? cv_lr_bc1 : ac_lr_bc1, isq_bc2 = net == 2 ? cv_isq : ac_isq;
       const float gs = net == 2 ? cv_gs : ac_gs;
@@ -444,8 +439,9 @@ __global__ __launch_bounds__(256) void k_back(SdxpDev D, int l) {   // l = layer
   const int k = kc * 256 + threadIdx.x;
   __shared__ float s_dy[MB][64];
   const int n_per = (Nn + splits - 1) / splits, n0 = sp * n_per, n1 = min(Nn, n0 + n_per);
-  const float* P = net == 2 ? D.cv : D.ac;
-  const size_t woff = net == 0 ? D.off.a_w[l + 1] : net == 1 ? D.off.c_w[l + 1] : D.coff.w[l + 1];
+  const TrunkSlot t = trunk_slot(D, net, l + 1);
+  const float* P = t.P;
+  const size_t woff = t.woff;
   float acc[MB];
 #pragma unroll
   for (int s = 0; s < MB; ++s) acc[s] = 0.0f;
@@ -656,10 +652,10 @@ __global__ __launch_bounds__(256) void k_grad_layer(SdxpDev D, int l) {
   const int par = ctl->step & 1, Nl = D.units[l];
   const int blocks_per_net = (Nl + 3) / 4;
   const int net = blockIdx.x / blocks_per_net, n = (blockIdx.x % blocks_per_net) * 4 + wave;
-  const int K = (l == 0) ? (net == 2 ? D.state_dim : D.obs_dim) : D.units[l - 1];
-  float* G = net == 2 ? D.cv_g : D.ac_g;
-  const size_t woff = net == 0 ? D.off.a_w[l] : net == 1 ? D.off.c_w[l] : D.coff.w[l];
-  const size_t boff = net == 0 ? D.off.a_b[l] : net == 1 ? D.off.c_b[l] : D.coff.b[l];
+  const TrunkSlot t = trunk_slot(D, net, l);
+  const int K = t.K;
+  float* G = t.G;
+  const size_t woff = t.woff, boff = t.boff;
   const float* gx = layer_input<MB>(D, ctl, net, l, true);
   for (int i = tid; i < MB * K; i += 256) sm[i] = gx[i];
   __syncthreads();
@@ -681,20 +677,17 @@ __global__ __launch_bounds__(256) void k_grad_heads(SdxpDev D) {
   const float* dh = D.dhead + (size_t)par * MB * 34;
   for (int i = tid; i < (A + 2) * U; i += 256) {
     const int row = i / U, k = i % U;
-    const int net = row < A ? 0 : (row == A ? 1 : 2);
-    const float* h = D.x[net][3] + (size_t)par * MB * U;
+    const HeadRow hr = head_row(D, row);
+    const float* h = D.x[hr.net][3] + (size_t)par * MB * U;
     float g = 0.0f;
-    for (int s = 0; s < MB; ++s) g += (row < A ? dh[s * 34 + row] : dh[s * 34 + 32 + (row - A)]) * h[s * U + k];
-    if (row < A) D.ac_g[D.off.mu_w + (size_t)row * U + k] = g;
-    else if (row == A) D.ac_g[D.off.v_w + k] = g;
-    else D.cv_g[D.coff.v_w + k] = g;
+    for (int s = 0; s < MB; ++s) g = fmaf(dh[s * 34 + hr.col], h[s * U + k], g);   // (spelled out: left to the compiler the products are paired and added unfused)
+    (hr.buf ? D.cv_g : D.ac_g)[hr.woff + k] = g;
   }
   if (tid < A + 2) {
+    const HeadRow hr = head_row(D, tid);
     float g = 0.0f;
-    for (int s = 0; s < MB; ++s) g += tid < A ? dh[s * 34 + tid] : dh[s * 34 + 32 + (tid - A)];
-    if (tid < A) D.ac_g[D.off.mu_b + tid] = g;
-    else if (tid == A) D.ac_g[D.off.v_b] = g;
-    else D.cv_g[D.coff.v_b] = g;
+    for (int s = 0; s < MB; ++s) g += dh[s * 34 + hr.col];
+    (hr.buf ? D.cv_g : D.ac_g)[hr.boff] = g;
   }
   if (tid < A) D.ac_g[D.off.logstd + tid] = D.dlogstd[(size_t)par * 32 + tid];
 }
@@ -708,7 +701,7 @@ __global__ __launch_bounds__(256) void k_pack_factors(SdxpDev D) {
   const int stride = gridDim.x * 256, t0 = blockIdx.x * 256 + threadIdx.x;
   if (seg < 9) {
     const int net = seg / 3, l = seg % 3;
-    const int K = (l == 0) ? (net == 2 ? D.state_dim : D.obs_dim) : D.units[l - 1];
+    const int K = trunk_slot(D, net, l).K;
     const float* src = layer_input<MB>(D, ctl, net, l, true);
     for (int i = t0; i < MB * K; i += stride) F[D.foff.x[net][l] + i] = src[i];
   } else if (seg < 18) {
@@ -733,7 +726,7 @@ static void launch_layer(const SdxpDev* D, int l, int Kmax, hipStream_t st) {
 template <int MB>
 static void launch_layers(const SdxpDev* D, hipStream_t st) {
   for (int l = 0; l < 3; ++l) {
-    const int Kmax = l == 0 ? (D->state_dim > D->obs_dim ? D->state_dim : D->obs_dim) : D->units[l - 1];
+    const int Kmax = trunk_kmax(D, l);
     const int ki = (Kmax / 4 + 63) / 64;   // float4 columns per lane
     const bool two = (3 * D->units[l]) / 4 >= 512;   // 2 rows per wave when there are plenty of rows
     if (ki <= 1) { if (two) launch_layer<MB, 2, 1>(D, l, Kmax, st); else launch_layer<MB, 1, 1>(D, l, Kmax, st); }
@@ -773,11 +766,8 @@ static int launch_backward(const SdxpDev* D, int mb_size, bool factors, hipStrea
     constexpr int M = decltype(m)::value;
     launch_fwd_bwd<M>(D, st);
     if (factors) hipLaunchKernelGGL(k_pack_factors<M>, dim3(8, 23), dim3(256), 0, st, *D);
-    for (int l = 0; l < 3 && !factors; ++l) {
-      const int Nl = D->units[l];
-      const int Kmax = l == 0 ? (D->state_dim > D->obs_dim ? D->state_dim : D->obs_dim) : D->units[l - 1];
-      hipLaunchKernelGGL(k_grad_layer<M>, dim3(3 * ((Nl + 3) / 4)), dim3(256), (size_t)M * Kmax * sizeof(float), st, *D, l);
-    }
+    for (int l = 0; l < 3 && !factors; ++l)
+      hipLaunchKernelGGL(k_grad_layer<M>, dim3(trunk_row_blocks(*D, l)), dim3(256), (size_t)M * trunk_kmax(D, l) * sizeof(float), st, *D, l);
     if (!factors) hipLaunchKernelGGL(k_grad_heads<M>, dim3(1), dim3(256), 0, st, *D);
     hipLaunchKernelGGL(k_ctrl<M>, dim3(1), dim3(1024), 0, st, *D, 1 | 2 | 8);
   });

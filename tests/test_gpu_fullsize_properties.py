@@ -181,9 +181,9 @@ def test_explicit_path_through_rccl_world1():
         dist.destroy_process_group()
 
 
-def _filled_agent_w(n, seed, data_seed, world):
+def _filled_agent_w(n, seed, data_seed, world, minibatch=4):
     from seqdex_amd.ppo import SdxPPO, make_config
-    ag = SdxPPO(n, config=make_config(n, world_size=world), seed=seed)
+    ag = SdxPPO(n, config=make_config(n, {"config": {"minibatch_size": minibatch}}, world_size=world), seed=seed)
     g = torch.Generator().manual_seed(data_seed)
     for t in range(8):
         obs = torch.randn(n, 396, generator=g).clamp(-5, 5).cuda()
@@ -242,27 +242,32 @@ def test_factor_exchange_equals_gradient_allreduce_world2_emulated():
             ag.close()
 
 
-def test_one_launch_apply_equals_three_launch_apply_bit_for_bit():
+def _one_launch_apply_against_three_launch_apply(minibatch, passes):
     """the apply phase of the multi-rank step as ONE launch (k_apply_factors_fused: gradient rebuild in registers, grid-wide ticket, the
     squared-norm shares folded in k_adam3's order, Adam, control block; SDXP_APPLY_IMPL=fused) against the default three-launch form on the
     same factors of two emulated ranks: parameters, both Adam moments, counters, gradient norms and the learning rate must be bit-identical
-    after every one of 64 optimiser steps' worth of launches (checked at the end: a single differing bit would spread)."""
+    after every one of 64 optimiser steps' worth of launches (checked at the end: a single differing bit would spread).
+    `passes` over the 16-env dataset in minibatches of `minibatch` rows."""
     n, world = 16, 2
-    B = _filled_agent_w(n, 5, 4, world)                   # rank 0, three launches (the default)
+    B = _filled_agent_w(n, 5, 4, world, minibatch)        # rank 0, three launches (the default)
     os.environ["SDXP_APPLY_IMPL"] = "fused"
     try:
-        A = _filled_agent_w(n, 5, 4, world)               # rank 0 again, one-launch apply
-        C = _filled_agent_w(n, 5, 6, world)               # rank 1 (another dataset), one-launch apply
+        A = _filled_agent_w(n, 5, 4, world, minibatch)    # rank 0 again, one-launch apply
+        C = _filled_agent_w(n, 5, 6, world, minibatch)    # rank 1 (another dataset), one-launch apply
     finally:
         del os.environ["SDXP_APPLY_IMPL"]
     try:
         for ag in (A, B, C):
             ag.backward_factors(-1)
-        for ep in range(2):
-            for mb in range(n * 8 // 4):
+        for ep in range(passes):
+            for mb in range(n * 8 // minibatch):
                 for ag in (A, B, C):
                     ag.backward_factors(mb)
-                np.testing.assert_array_equal(A.t["FACTORS"].cpu().numpy(), B.t["FACTORS"].cpu().numpy())
+                # minibatch 4: the forward/backward is the one persistent-style launch, reproducible bit for bit, so the two handles of rank 0
+                # must agree on their factors as well.  Other sizes take the multi-kernel step, whose k_back adds with float atomics over 8
+                # splits: A's and B's own factors may differ in the last bit there (B's are not used: all three apply A's and C's)
+                if minibatch == 4:
+                    np.testing.assert_array_equal(A.t["FACTORS"].cpu().numpy(), B.t["FACTORS"].cpu().numpy())
                 f = torch.stack([A.t["FACTORS"], C.t["FACTORS"]])
                 for ag in (A, B, C):
                     ag.t["FACTORS_ALL"].copy_(f)
@@ -270,7 +275,7 @@ def test_one_launch_apply_equals_three_launch_apply_bit_for_bit():
         for ag in (A, B, C):
             ag.update_status()
         ca, cb, cc = A.ctrl(), B.ctrl(), C.ctrl()
-        assert ca.ac_t == cb.ac_t == cc.ac_t == 2 * (n * 8 // 4) and ca.cv_t == cb.cv_t
+        assert ca.ac_t == cb.ac_t == cc.ac_t == passes * (n * 8 // minibatch) and ca.cv_t == cb.cv_t
         for k in ("ac_lr", "ac_gnorm", "cv_gnorm", "gn2_ac", "gn2_cv", "ac_b1pow", "cv_b2pow"):
             assert getattr(ca, k) == getattr(cb, k) == getattr(cc, k), k
         assert ca.ac_gnorm > 0.0 and ca.cv_gnorm > 0.0
@@ -286,6 +291,108 @@ def test_one_launch_apply_equals_three_launch_apply_bit_for_bit():
     finally:
         for ag in (A, B, C):
             ag.close()
+
+
+def test_one_launch_apply_equals_three_launch_apply_bit_for_bit():
+    """minibatch 4 (the shipped size): two passes over the 32 minibatches"""
+    _one_launch_apply_against_three_launch_apply(4, 2)
+
+
+def test_one_launch_apply_equals_three_launch_apply_bit_for_bit_minibatch_2():
+    """k_apply_factors_fused<2>, the other instantiation of the one-launch apply: one pass over the 64 minibatches"""
+    _one_launch_apply_against_three_launch_apply(2, 1)
+
+
+def _float64_gradients_from_factors(fa, cfg):
+    """The factor layout of sdxp_create restated: per rank x[net][l] [MB][K], then dy[net][l] [MB][units[l]], then h[net] [MB][units[2]], then
+    dhead [MB][34] (columns 0..A-1 mu, 32 critic, 33 central value), dlogstd [32], the KL word.  From fa = FACTORS_ALL [world, F] in float64:
+    (flat actor-critic gradient, flat central-value gradient, KL sum) summed over ranks and rows, each as (value, sum of |dy| |x|)."""
+    MB, units, A = cfg.minibatch, list(cfg.units), cfg.act_dim
+    o = 0
+
+    def take(cols):
+        nonlocal o
+        v = fa[:, o:o + MB * cols].reshape(-1, cols)        # [world * MB, cols]
+        o += MB * cols
+        return v
+    x = {(net, l): take((cfg.state_dim if net == 2 else cfg.obs_dim) if l == 0 else units[l - 1]) for net in range(3) for l in range(3)}
+    dy = {(net, l): take(units[l]) for net in range(3) for l in range(3)}
+    h = [take(units[2]) for net in range(3)]
+    dh = take(34)
+    dls = fa[:, o:o + 32]; o += 32
+    kl = fa[:, o]
+
+    def product(d, v):      # d [T, n], v [T, k] -> the n x k gradient and its bias, flattened as the parameters are laid out
+        return [((d.T @ v).ravel(), (np.abs(d).T @ np.abs(v)).ravel()), (d.sum(0), np.abs(d).sum(0))]
+
+    def trunk(net):
+        return [p for l in range(3) for p in product(dy[net, l], x[net, l])]
+    mu, vc, vcv = product(dh[:, :A], h[0]), product(dh[:, 32:33], h[1]), product(dh[:, 33:34], h[2])
+    ac = trunk(0) + mu + [(dls[:, :A].sum(0), np.abs(dls[:, :A]).sum(0))] + trunk(1) + vc
+    cv = trunk(2) + vcv
+    cat = lambda ps: (np.concatenate([p[0] for p in ps]), np.concatenate([p[1] for p in ps]))
+    return cat(ac), cat(cv), (kl.sum(), np.abs(kl).sum())
+
+
+@pytest.mark.parametrize("minibatch", [2, 4, 8])
+def test_gradient_rebuilt_from_factors_against_float64(minibatch):
+    """k_grad_layer_w / k_grad_heads_w at every minibatch size they are instantiated for, two ranks emulated in one process: every weight,
+    bias and logstd gradient and the KL sum against the same sums formed in float64 from the FACTORS_ALL tensor itself.
+    Bound (derived): an element is a sum of T = world * MB products accumulated in fp32, so |got - want| <= T 2^-23 sum |dy| |x|, twice the
+    standard gamma_T bound (it covers fused and unfused products); a bias, logstd or KL sum is the same with |x| = 1."""
+    n, world = 16, 2
+    A, B = _filled_agent_w(n, 5, 4, world, minibatch), _filled_agent_w(n, 5, 6, world, minibatch)
+    try:
+        for ag in (A, B):
+            ag.backward_factors(-1)
+            ag.backward_factors(0)
+        f = torch.stack([A.t["FACTORS"], B.t["FACTORS"]])
+        for ag in (A, B):
+            ag.t["FACTORS_ALL"].copy_(f)
+            ag.grads_from_factors()
+        torch.cuda.synchronize()
+        (ac, ac_abs), (cv, cv_abs), (kl, kl_abs) = _float64_gradients_from_factors(A.t["FACTORS_ALL"].cpu().numpy().astype(np.float64), A.cfg)
+        all_a, all_b = A.t["ALL_GRADS"].cpu().numpy(), B.t["ALL_GRADS"].cpu().numpy()
+        got = {"ac": A.t["AC_GRADS"].cpu().numpy(), "cv": A.t["CV_GRADS"].cpu().numpy(), "kl": all_a[-64:-63]}
+        want = {"ac": (ac, ac_abs), "cv": (cv, cv_abs), "kl": (np.array([kl]), np.array([kl_abs]))}
+        unit = world * minibatch * 2.0 ** -23
+        for k in ("ac", "cv", "kl"):
+            w, mag = want[k]
+            assert got[k].shape == w.shape, (k, got[k].shape, w.shape)
+            err = np.abs(got[k].astype(np.float64) - w)
+            print("rebuild", minibatch, k, "max |want|", np.abs(w).max(), "max err", err.max(), "max err / bound", (err / np.maximum(unit * mag, 1e-300)).max())
+            assert (err <= unit * mag).all(), (k, float(err.max()))
+        assert max(np.abs(ac).max(), np.abs(cv).max()) > 1e-3       # a zero buffer cannot pass
+        assert all_a.tobytes() == all_b.tobytes()                   # both ranks hold the same flat gradient, byte for byte
+    finally:
+        A.close(); B.close()
+
+
+def test_three_launch_apply_minibatch_8_keeps_ranks_in_lock_step():
+    """k_grad_all_w<8> / k_adam3 / k_apply_fin2 (the one-launch form does not come in 8), two ranks emulated, one pass over the 16
+    minibatches: parameters and both Adam moments of the ranks stay byte-identical, the counter says 16, and every array moved"""
+    n, world, minibatch = 16, 2, 8
+    A, B = _filled_agent_w(n, 5, 4, world, minibatch), _filled_agent_w(n, 5, 6, world, minibatch)
+    keys = ("AC_PARAMS", "CV_PARAMS", "AC_ADAM_M", "AC_ADAM_V", "CV_ADAM_M", "CV_ADAM_V")
+    try:
+        before = {k: A.t[k].cpu().numpy().copy() for k in keys}
+        for ag in (A, B):
+            ag.backward_factors(-1)
+        for mb in range(n * 8 // minibatch):
+            A.backward_factors(mb); B.backward_factors(mb)
+            f = torch.stack([A.t["FACTORS"], B.t["FACTORS"]])
+            for ag in (A, B):
+                ag.t["FACTORS_ALL"].copy_(f)
+                ag.apply_factors()
+        for ag in (A, B):
+            ag.update_status()
+        assert A.ctrl().ac_t == B.ctrl().ac_t == n * 8 // minibatch == 16
+        for k in keys:
+            a = A.t[k].cpu().numpy()
+            assert a.tobytes() == B.t[k].cpu().numpy().tobytes(), k
+            assert np.abs(a - before[k]).max() > 0, k
+    finally:
+        A.close(); B.close()
 
 
 def test_persistent_kernel_failure_falls_back_to_graph_path():
