@@ -3,11 +3,11 @@
 // epilogues the MLP forward / backward passes need.  gfx950 only.
 #pragma once
 #include "sdx_common.h"
+#include "sdx_mfma.h"
 #include <cstddef>
 #include <cstdint>
 #include <type_traits>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
@@ -90,12 +90,7 @@ __global__ __launch_bounds__(256) void k_gemm(GemmBatch gb) {
   const int kbeg = zs * g.kchunk, kend = min(g.K, kbeg + g.kchunk);
   const int wm = (wave >> 1) * 32 * WTM, wn = (wave & 1) * 32 * WTN;
   f32x16 acc[WTM][WTN];
-#pragma unroll
-  for (int u = 0; u < WTM; ++u)
-#pragma unroll
-    for (int v = 0; v < WTN; ++v)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[u][v][i] = 0.0f;
+  mfma_zero(acc);
   // element e = tid + 256 p of a chunk: k-contiguous sources -> (row e / (KT/4), k offset 4 (e % (KT/4)));
   // transposed sources -> (k row e / (T/4), i/j offset 4 (e % (T/4))): consecutive lanes read consecutive 16-byte pieces
   float4 av[NVA], bv[NVB];
@@ -175,7 +170,7 @@ __global__ __launch_bounds__(256) void k_gemm(GemmBatch gb) {
     for (int u = 0; u < WTM; ++u)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = i0 + wm + 32 * u + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int row = mfma_cd_row(i0 + wm + 32 * u, r, lane);
         if (row < g.M) {
           float x = acc[u][v][r] + bias;
           if (EPI == 1) x = belu(x);

@@ -103,6 +103,76 @@ __device__ __forceinline__ float frag_sum(bf16x8 a) {
 #endif
 }
 
+// ---- workgroup -> tile of the 1-D grid, for k_gemm_nt and k_gemm_tt.  The dispatcher hands consecutive workgroup ids to the 8 XCDs
+// in turn (MI355X_MICROARCH.md; a speed assumption only); the remap below gives every XCD one contiguous run of tile indices, x fastest,
+// so that the workgroups that share an A row band (and, over a few bands, the B column bands) meet in ONE L2 instead of fetching it
+// eight times.  The kernels pick the problem nb.a[bz / splits] and the split bz % splits themselves and leave when the tile lies past
+// that problem's edge: with the address of their NtBatch argument handed to this function the compiler laid out the EPI_FWD / EPI_NN
+// epilogues differently (87 to 227 more instructions in the fp32 instantiations), so it takes scalars only.
+struct NtTile { int bx, by, bz; };   // column block, row block, problem * splits + split
+__device__ __forceinline__ NtTile nt_tile(int nx, int ny) {
+  const int total = (int)gridDim.x;
+  int wg;
+  {
+    const int id = (int)blockIdx.x, q = total >> 3, r = total & 7, xcd = id & 7;
+    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
+  }
+  NtTile t;
+  t.bx = wg % nx; t.by = (wg / nx) % ny; t.bz = wg / (nx * ny);
+  return t;
+}
+
+// ---- the two-stage reduction loop of both kernels: issue(c, s) requests chunk c into LDS stage s (global_load_lds), multiply(s, tag)
+// reads the fragments of stage s and runs the chunk's MFMAs; the loads of chunk c + 1 fly while chunk c is multiplied, one barrier per
+// chunk.  tag (std::true_type / std::false_type): the copy of the loop that also sums the rows of A beside the MFMAs (the bias
+// gradient of a dY^T X product: VALU adds of the fragments the MFMAs consume anyway - beside the matrix pipe, not on it) / the plain one.
+// The choice is made ONCE, outside the loop, between the two copies: with a branch between the MFMAs of a 2-accumulator wave (the
+// 128 x 64 tile in fp32) the waves that skipped the extra work got wrong sums on gfx950 (tools/diag_gemm_nt.py,
+// profiles/r4_gemm_nt_diag_branch_between_mfmas.txt, tools/gpu/probe/mfma_branch.hip) - the loop bodies are branch-free.
+template <bool RS, class Issue, class Multiply>
+__device__ __forceinline__ void nt_chunk_loop(int nc, Issue& issue, Multiply& multiply) {
+  if (nc > 0) issue(0, 0);
+  for (int c = 0; c < nc; ++c) {
+    SDX_WAIT_VMCNT0();                                  // this wave's pieces of chunk c have landed ...
+    __syncthreads();                                    // ... everybody's have, and everybody is done reading the other stage
+    if (c + 1 < nc) issue(c + 1, (c + 1) & 1);
+    multiply(c & 1, std::integral_constant<bool, RS>{});
+  }
+}
+template <class Issue, class Multiply>
+__device__ __forceinline__ void nt_chunks(bool row_sums, int nc, Issue& issue, Multiply& multiply) {
+  if (row_sums) nt_chunk_loop<true>(nc, issue, multiply); else nt_chunk_loop<false>(nc, issue, multiply);   // (workgroup-uniform: every wave of a workgroup runs the same copy)
+}
+
+// ---- split partial of a weight gradient (k_gemm_nt<.., EPI_TN, ..>, k_gemm_tt): the accumulators of the wave at (wm, wn) of the tile go
+// straight to Cf + zs cz (small; 128-byte runs), and with do_rs the row sums rs[u] of the wave's two 32-row blocks to rowsum: lanes l
+// and l + 32 hold the two halves of row (l & 31)'s sum over this split's reduction range
+template <int WTN>
+__device__ __forceinline__ void nt_store_partial(const NtArgs& g, int zs, int i0, int j0, int wave, int lane, int wm, int wn, bool do_rs, const float (&rs)[2],
+                                                 const f32x16 (&acc)[2][WTN]) {
+  if (do_rs) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const float t = rs[u] + __shfl_xor(rs[u], 32, 64);
+      const int row = i0 + wm + 32 * u + (lane & 31);
+      if ((wave & 1) == 0 && lane < 32 && row < g.M) g.rowsum[(size_t)zs * g.cz + row] = t;
+    }
+  }
+  float* Cf = g.Cf + (size_t)zs * g.cz;
+#pragma unroll
+  for (int v = 0; v < WTN; ++v) {
+    const int col = j0 + wn + 32 * v + (lane & 31);
+    if (col >= g.N) continue;
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = mfma_cd_row(i0 + wm + 32 * u, r, lane);
+        if (row < g.M) Cf[(size_t)row * g.ldc + col] = acc[u][v][r];
+      }
+  }
+}
+
 template <int BF, int EPI, int WTN>
 __global__ __launch_bounds__(256, 2) void k_gemm_nt(NtBatch nb, int nx, int ny) {
   typedef typename std::conditional<BF != 0, __bf16, float>::type elem_t;
@@ -113,22 +183,13 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(NtBatch nb, int nx, int ny) 
   constexpr int STAGE = (TM + TN) * 128;             // bytes per LDS stage
   constexpr int NA = TM / 32, NB = TN / 32;          // global_load_lds instructions per wave per chunk (8 rows each)
   extern __shared__ __attribute__((aligned(16))) char smem[];      // the ONLY LDS object of the kernel: [2][TM + TN][128 B], reused by the epilogue
-  // ---- workgroup -> tile.  The dispatcher hands consecutive workgroup ids to the 8 XCDs in turn (MI355X_MICROARCH.md; a speed
-  // assumption only); the remap below gives every XCD one contiguous run of tile indices, x fastest, so that the workgroups that
-  // share an A row band (and, over a few bands, the B column bands) meet in ONE L2 instead of fetching it eight times.
-  const int total = (int)gridDim.x;
-  int wg;
-  {
-    const int id = (int)blockIdx.x, q = total >> 3, r = total & 7, xcd = id & 7;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
-  }
-  const int bx = wg % nx, by = (wg / nx) % ny, bz = wg / (nx * ny);
-  const NtArgs& g = nb.a[bz / nb.splits];
-  const int zs = bz % nb.splits;
+  const NtTile tile = nt_tile(nx, ny);
+  const NtArgs& g = nb.a[tile.bz / nb.splits];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int i0 = by * TM, j0 = bx * TN;
+  const int i0 = tile.by * TM, j0 = tile.bx * TN;
   if (i0 >= g.M || j0 >= g.N) return;                // the grid covers the largest problem of the batch
+  const int zs = tile.bz % nb.splits;
   const int kbeg = zs * g.kchunk, kend = min(g.K, kbeg + g.kchunk);
   const int nc = (kend - kbeg) / KC;
   const int wm = (wave >> 1) * 64, wn = (wave & 1) * (32 * WTN);
@@ -157,98 +218,52 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(NtBatch nb, int nx, int ny) 
       __builtin_amdgcn_global_load_lds(SDX_AS_GLOBAL(gb[p] + (size_t)c * 128), SDX_AS_LDS(sa + TM * 128 + (wave * NB + p) * 1024), 16, 0, 0);
   };
   f32x16 acc[2][WTN];
-#pragma unroll
-  for (int u = 0; u < 2; ++u)
-#pragma unroll
-    for (int v = 0; v < WTN; ++v)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[u][v][i] = 0.0f;
-  // EPI_TN: the workgroups of the first column block also sum the rows of A (the bias gradient of a dY^T X product): VALU adds of the
-  // fragments the MFMAs consume anyway (v_dot2c_f32_bf16 against ones for bf16) - beside the matrix pipe, not on it.  The choice is made
-  // ONCE, outside the reduction loop, between two copies of the loop: with a branch between the MFMAs of a 2-accumulator wave (the
-  // 128 x 64 tile in fp32) the waves that skipped the extra work got wrong sums on gfx950 (tools/diag_gemm_nt.py,
-  // profiles/r4_gemm_nt_diag_branch_between_mfmas.txt) - the loop bodies are branch-free.
+  mfma_zero(acc);
+  // EPI_TN: the workgroups of the first column block also sum the rows of A, with frag_sum (v_dot2c_f32_bf16 against ones for bf16), in
+  // their own copy of the loop (nt_chunks)
   float rs[2] = {0.0f, 0.0f};
-  const bool do_rs = EPI == EPI_TN && bx == 0;
+  const bool do_rs = EPI == EPI_TN && tile.bx == 0;
   // fragment addresses: row (l & 31) of a 32-row block, piece (2 t + (l >> 5)) ^ key, key = ((l & 31) >> 1) & 7 (block bases are multiples of 32)
   const int roff = (lane & 31) * 128;
   const int off0 = ((lane >> 5) ^ ((lane >> 1) & 7)) << 4;
-  auto chunks = [&](auto rs_tag) {
-    constexpr bool RS = decltype(rs_tag)::value;
-    if (nc > 0) issue(0, 0);
-    for (int c = 0; c < nc; ++c) {
-      SDX_WAIT_VMCNT0();                                // this wave's pieces of chunk c have landed ...
-      __syncthreads();                                  // ... everybody's have, and everybody is done reading the other stage
-      if (c + 1 < nc) issue(c + 1, (c + 1) & 1);
-      const char* sa = smem + (c & 1) * STAGE + wm * 128 + roff;
-      const char* sb = smem + (c & 1) * STAGE + TM * 128 + wn * 128 + roff;
-      // all fragments of the chunk are requested before the first MFMA: one LDS latency per chunk instead of one per 16-wide step
-      frag_t a[4][2], b[4][WTN];
+  auto multiply = [&](int s, auto rs_tag) {
+    const char* sa = smem + s * STAGE + wm * 128 + roff;
+    const char* sb = smem + s * STAGE + TM * 128 + wn * 128 + roff;
+    // all fragments of the chunk are requested before the first MFMA: one LDS latency per chunk instead of one per 16-wide step
+    frag_t a[4][2], b[4][WTN];
 #pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int off = off0 ^ (t << 5);
+    for (int t = 0; t < 4; ++t) {
+      const int off = off0 ^ (t << 5);
 #pragma unroll
-        for (int u = 0; u < 2; ++u) a[t][u] = *reinterpret_cast<const frag_t*>(sa + u * 4096 + off);
+      for (int u = 0; u < 2; ++u) a[t][u] = *reinterpret_cast<const frag_t*>(sa + u * 4096 + off);
 #pragma unroll
-        for (int v = 0; v < WTN; ++v) b[t][v] = *reinterpret_cast<const frag_t*>(sb + v * 4096 + off);
-      }
+      for (int v = 0; v < WTN; ++v) b[t][v] = *reinterpret_cast<const frag_t*>(sb + v * 4096 + off);
+    }
 #pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        if constexpr (BF != 0) {
+    for (int t = 0; t < 4; ++t) {
+      if constexpr (BF != 0) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+          for (int v = 0; v < WTN; ++v) acc[u][v] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[t][u], b[t][v], acc[u][v], 0, 0, 0);
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
 #pragma unroll
           for (int u = 0; u < 2; ++u)
 #pragma unroll
-            for (int v = 0; v < WTN; ++v) acc[u][v] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[t][u], b[t][v], acc[u][v], 0, 0, 0);
-        } else {
+            for (int v = 0; v < WTN; ++v) acc[u][v] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t][u][q], b[t][v][q], acc[u][v], 0, 0, 0);
+      }
+      if constexpr (decltype(rs_tag)::value) {
 #pragma unroll
-          for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-              for (int v = 0; v < WTN; ++v) acc[u][v] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t][u][q], b[t][v][q], acc[u][v], 0, 0, 0);
-        }
-#ifdef SDX_GEMM_NT_BRANCHY          // diagnostic build only: the round-4 form with a (workgroup-uniform) branch between the MFMAs of a k step
-        if (do_rs) {
-#pragma unroll
-          for (int u = 0; u < 2; ++u) rs[u] += frag_sum(a[t][u]);
-        }
-#else
-        if constexpr (RS) {
-#pragma unroll
-          for (int u = 0; u < 2; ++u) rs[u] += frag_sum(a[t][u]);
-        }
-#endif
+        for (int u = 0; u < 2; ++u) rs[u] += frag_sum(a[t][u]);
       }
     }
   };
-#ifdef SDX_GEMM_NT_BRANCHY
-  chunks(std::false_type{});
-#else
-  if (do_rs) chunks(std::true_type{}); else chunks(std::false_type{});   // (workgroup-uniform: every wave of a workgroup runs the same copy)
-#endif
-  // ---- epilogue.  C/D layout: lane l holds column (l & 31), rows (r & 3) + 8 (r >> 2) + 4 (l >> 5), r = 0..15, of each 32 x 32 block
+  nt_chunks(do_rs, nc, issue, multiply);
+  // ---- epilogue.  C/D layout: lane l holds column (l & 31) and the rows mfma_cd_row(first row, r, l), r = 0..15, of each 32 x 32 block
   if constexpr (EPI == EPI_TN) {
-    if (do_rs) {                                     // lanes l and l + 32 hold the two halves of row (l & 31)'s sum over this split's k range
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const float t = rs[u] + __shfl_xor(rs[u], 32, 64);
-        const int row = i0 + wm + 32 * u + (lane & 31);
-        if ((wave & 1) == 0 && lane < 32 && row < g.M) g.rowsum[(size_t)zs * g.cz + row] = t;
-      }
-    }
-    float* Cf = g.Cf + (size_t)zs * g.cz;            // split partials: small, written straight from the accumulators (128-byte runs)
-#pragma unroll
-    for (int v = 0; v < WTN; ++v) {
-      const int col = j0 + wn + 32 * v + (lane & 31);
-      if (col >= g.N) continue;
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = i0 + wm + 32 * u + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-          if (row < g.M) Cf[(size_t)row * g.ldc + col] = acc[u][v][r];
-        }
-    }
+    nt_store_partial<WTN>(g, zs, i0, j0, wave, lane, wm, wn, do_rs, rs, acc);
     return;
   } else {
     // Both copies leave through LDS so that every global access of the epilogue is a 16-byte piece of a long contiguous run (straight
@@ -275,7 +290,9 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt(NtBatch nb, int nx, int ny) 
     constexpr int EPP = 16 / ES;                     // elements per 16-byte piece of an element-type array
     SDX_LDS_BARRIER();                               // every wave is done with the operand stages (LDS-only barriers from here on: sdx_common.h)
     if (Cf || Cn) {
-      // normal orientation: fp32 tile [TM][TN] in LDS (64 KB for the 128 x 128 tile = both stages); 8 consecutive columns per thread
+      // normal orientation: fp32 tile [TM][TN] in LDS (64 KB for the 128 x 128 tile = both stages); 8 consecutive columns per thread.
+      // (The row of register r is mfma_cd_row's rule written out, here and in the transposed image below: through the function the
+      // compiler gave these two epilogues other code than they had.)
       float* T = reinterpret_cast<float*>(smem);
 #pragma unroll
       for (int v = 0; v < WTN; ++v)
@@ -468,19 +485,13 @@ __global__ __launch_bounds__(256, 2) void k_gemm_tt(NtBatch nb, int nx, int ny, 
   constexpr int NA = ASTAGE / 1024 / 4, NB = BSTAGE / 1024 / 4;          // global_load_lds instructions per wave per chunk
   constexpr int RPB = 1024 / (TN * 4);                                    // B rows per instruction (2 for the 128-wide tile, 4 for 64)
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int total = (int)gridDim.x;
-  int wg;
-  {
-    const int id = (int)blockIdx.x, q = total >> 3, r = total & 7, xcd = id & 7;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
-  }
-  const int bx = wg % nx, by = (wg / nx) % ny, bz = wg / (nx * ny);
-  const NtArgs& g = nb.a[bz / nb.splits];
-  const int zs = bz % nb.splits;
+  const NtTile tile = nt_tile(nx, ny);
+  const NtArgs& g = nb.a[tile.bz / nb.splits];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int i0 = by * TM, j0 = bx * TN;
-  if (i0 >= g.M || j0 >= g.N) return;
+  const int i0 = tile.by * TM, j0 = tile.bx * TN;
+  if (i0 >= g.M || j0 >= g.N) return;                // the grid covers the largest problem of the batch
+  const int zs = tile.bz % nb.splits;
   const int rbeg = zs * g.kchunk, rend = min(g.K, rbeg + g.kchunk);
   const int nc = (rend - rbeg + RC - 1) / RC;
   const int wm = (wave >> 1) * 64, wn = (wave & 1) * (32 * WTN);
@@ -512,67 +523,35 @@ __global__ __launch_bounds__(256, 2) void k_gemm_tt(NtBatch nb, int nx, int ny, 
     }
   };
   f32x16 acc[2][WTN];
-#pragma unroll
-  for (int u = 0; u < 2; ++u)
-#pragma unroll
-    for (int v = 0; v < WTN; ++v)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[u][v][i] = 0.0f;
+  mfma_zero(acc);
   float rs[2] = {0.0f, 0.0f};
-  const bool do_rs = bx == 0;
+  const bool do_rs = tile.bx == 0;
   const int foff = ((lane >> 5) * TM + wm + (lane & 31)) * 4, goff = ((lane >> 5) * TN + wn + (lane & 31)) * 4;
-  auto chunks = [&](auto rs_tag) {
-    constexpr bool RS = decltype(rs_tag)::value;
-    if (nc > 0) issue(0, 0);
-    for (int c = 0; c < nc; ++c) {
-      SDX_WAIT_VMCNT0();
-      __syncthreads();
-      if (c + 1 < nc) issue(c + 1, (c + 1) & 1);
-      const char* sa = smem + (c & 1) * STAGE + foff;
-      const char* sb = smem + (c & 1) * STAGE + ASTAGE + goff;
-      float a[16][2], b[16][WTN];
+  auto multiply = [&](int s, auto rs_tag) {
+    const char* sa = smem + s * STAGE + foff;
+    const char* sb = smem + s * STAGE + ASTAGE + goff;
+    float a[16][2], b[16][WTN];
 #pragma unroll
-      for (int t = 0; t < 16; ++t) {
+    for (int t = 0; t < 16; ++t) {
 #pragma unroll
-        for (int u = 0; u < 2; ++u) a[t][u] = *reinterpret_cast<const float*>(sa + t * (2 * TM * 4) + u * 128);
+      for (int u = 0; u < 2; ++u) a[t][u] = *reinterpret_cast<const float*>(sa + t * (2 * TM * 4) + u * 128);
 #pragma unroll
-        for (int v = 0; v < WTN; ++v) b[t][v] = *reinterpret_cast<const float*>(sb + t * (2 * TN * 4) + v * 128);
-      }
+      for (int v = 0; v < WTN; ++v) b[t][v] = *reinterpret_cast<const float*>(sb + t * (2 * TN * 4) + v * 128);
+    }
 #pragma unroll
-      for (int t = 0; t < 16; ++t) {
+    for (int t = 0; t < 16; ++t) {
 #pragma unroll
-        for (int u = 0; u < 2; ++u)
+      for (int u = 0; u < 2; ++u)
 #pragma unroll
-          for (int v = 0; v < WTN; ++v) acc[u][v] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t][u], b[t][v], acc[u][v], 0, 0, 0);
-        if constexpr (RS) {
+        for (int v = 0; v < WTN; ++v) acc[u][v] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t][u], b[t][v], acc[u][v], 0, 0, 0);
+      if constexpr (decltype(rs_tag)::value) {
 #pragma unroll
-          for (int u = 0; u < 2; ++u) rs[u] += a[t][u];
-        }
+        for (int u = 0; u < 2; ++u) rs[u] += a[t][u];
       }
     }
   };
-  if (do_rs) chunks(std::true_type{}); else chunks(std::false_type{});
-  if (do_rs) {                                       // lanes l and l + 32 hold the sums over the even / odd rows of column (l & 31)
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const float t = rs[u] + __shfl_xor(rs[u], 32, 64);
-      const int row = i0 + wm + 32 * u + (lane & 31);
-      if ((wave & 1) == 0 && lane < 32 && row < g.M) g.rowsum[(size_t)zs * g.cz + row] = t;
-    }
-  }
-  float* Cf = g.Cf + (size_t)zs * g.cz;
-#pragma unroll
-  for (int v = 0; v < WTN; ++v) {
-    const int col = j0 + wn + 32 * v + (lane & 31);
-    if (col >= g.N) continue;
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = i0 + wm + 32 * u + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (row < g.M) Cf[(size_t)row * g.ldc + col] = acc[u][v][r];
-      }
-  }
+  nt_chunks(do_rs, nc, issue, multiply);
+  nt_store_partial<WTN>(g, zs, i0, j0, wave, lane, wm, wn, do_rs, rs, acc);   // (rs: lanes l and l + 32 hold the sums over the even / odd rows of column (l & 31) of A)
 }
 
 // ---- staging: src fp32 [R][K] (row stride lds) -> dn [R][ldn] in the element type with columns K .. Kp zeroed, and / or its transpose

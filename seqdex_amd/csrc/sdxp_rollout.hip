@@ -4,8 +4,7 @@
 // head kernel = mu / value / Gaussian sample / neglogp (RC:1697-1723,2114-2126), reward bookkeeping, GAE and advantage normalisation.
 #include "sdxp_device.h"
 #include "sdxp_launch.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "sdx_mfma.h"
 
 // ------------------------------------------------------------------------------------------------ rollout GEMM
 // Y[M,N] = act(X[M,K] W[N,K]^T + b[N]); act = ELU when elu_flag.  X may be normalised on the fly with (mean, rstd)
@@ -155,7 +154,7 @@ __global__ __launch_bounds__(256 * KS) void k_linear_mfma(LinBatch lb) {
     for (int u = 0; u < WTM; ++u)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm + 32 * u + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int row = mfma_cd_row(m0 + wm + 32 * u, r, lane);
         if (row < M) {
           const float v = acc[u][r] + bias;
           g.Y[(size_t)row * N + col] = g.elu ? elu(v) : v;
@@ -309,7 +308,7 @@ __global__ __launch_bounds__(256 * KS) void k_linear_glds(LinBatch lb) {
     const float bias = g.b[col];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+      const int row = mfma_cd_row(m0 + wm, r, lane);
       if (row < M) {
         const float v = acc[r] + bias;
         g.Y[(size_t)row * N + col] = g.elu ? elu(v) : v;

@@ -7,10 +7,25 @@ tests/test_gpu_gemm_products.py through sdxpk_gemm_nt_launch / sdxpk_gemm_tt_lau
 
 and leaves the results in the numpy arrays of the problems.  tile: 0 = the launcher's choice, 1 = 128 x 64, 2 = 128 x 128.  The reference
 is numpy in float64; for bf16 the operands ARE bf16 values, so products are exact and only the fp32 accumulation rounds."""
+import ctypes as C
+
 import numpy as np
 import torch
 
 EPI_FWD, EPI_NN, EPI_TN = 1, 3, 4
+
+
+class NtArgs(C.Structure):      # sdx_gemm_nt.h
+    _fields_ = [("A", C.c_void_p), ("lda", C.c_int), ("B", C.c_void_p), ("ldb", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
+                ("kchunk", C.c_int), ("Cf", C.c_void_p), ("ldc", C.c_int), ("cz", C.c_size_t), ("Cn", C.c_void_p), ("ldn", C.c_int),
+                ("Ct", C.c_void_p), ("ldt", C.c_int), ("bias", C.c_void_p), ("H", C.c_void_p), ("ldh", C.c_int), ("Ht", C.c_void_p), ("ldht", C.c_int),
+                ("rowsum", C.c_void_p)]
+
+
+def nt_args(g, address):
+    """the NtArgs of Problem g; address(name): where the backend keeps the array g.<name> (None for a null pointer)"""
+    return NtArgs(address("A"), g.lda, address("B"), g.ldb, g.M, g.N, g.K, g.kchunk, address("Cf"), g.ldc, g.cz, address("Cn"), g.ldn, address("Ct"), g.ldt,
+                  address("bias"), address("H"), g.ldh, address("Ht"), g.ldht, None if g.rowsum_off is None else address("Cf") + 4 * g.rowsum_off)
 
 BF = [0, 1]
 FORWARD_SHAPES = [(128, 128, 128), (200, 150, 192), (70, 36, 64)]
@@ -100,28 +115,41 @@ def narrow_tile_shape(backend, bf, tile=1):
     np.testing.assert_allclose(from_elems(Ct, bf)[:, :M], Cf.astype(np.float64).T, rtol=8e-3 if bf else 0)
 
 
-def wide_tile_shape_all_copies(backend, bf, epi, M, tile=2):
+def wide_tile_shape_all_copies(backend, bf, epi, M, tile=2, odd=False):
     """the 128 x 128 tile: two passes of the transposed epilogue (64 columns each), 19 workgroups through the XCD remap, ragged edges
-    (M = 270) and whole 16-byte pieces along the rows (M = 272)"""
+    (M = 270) and whole 16-byte pieces along the rows (M = 272).  odd: every leading dimension of the epilogue is odd in 16-byte pieces
+    (ldc = ldn = ldh = N + 1, ldt = ldht = Mp + 2), so that every piece of H / Ht is loaded and every piece of Cf / Cn / Ct stored
+    element by element; else they are whole pieces and the copy's row stride differs from the fp32 result's"""
     rng = np.random.default_rng(17 + bf + epi)
     N, K = 300, 128
     A, Av = elems(rng.standard_normal((M, K)) * 0.4, bf)
     B, Bv = elems(rng.standard_normal((N, K)) * 0.4, bf)
     bias = rng.standard_normal(N).astype(np.float32)
-    H, Hv = elems(rng.standard_normal((M, N)), bf)
-    Mp = 320
-    Ht = np.zeros((N, Mp), H.dtype); Ht[:, :M] = H.T                         # the layer output's transposed copy, as the forward product leaves it
-    Cf = np.full((M, N), np.nan, np.float32)
-    Cn = np.zeros((M, N + 4), np.int16 if bf else np.float32)               # the copy's row stride differs from the fp32 result's
+    Hd, Hv = elems(rng.standard_normal((M, N)), bf)
+    ldc, ldn, ldh, Mp = (N + 1, N + 1, N + 1, 322) if odd else (N, N + 4, N, 320)
+    H = np.zeros((M, ldh), Hd.dtype); H[:, :N] = Hd
+    Ht = np.zeros((N, Mp), Hd.dtype); Ht[:, :M] = Hd.T                       # the layer output's transposed copy, as the forward product leaves it
+    Cf = np.full((M, ldc), np.nan, np.float32)
+    Cn = np.zeros((M, ldn), np.int16 if bf else np.float32)
     Ct = np.zeros((N, Mp), np.int16 if bf else np.float32)
-    backend.nt(bf, epi, tile, 1, [Problem(A, K, B, K, M, N, K, K, Cf if epi == EPI_FWD else None, N, 0, Cn, N + 4, Ct, Mp, bias, H, N, Ht, Mp)])
+    backend.nt(bf, epi, tile, 1, [Problem(A, K, B, K, M, N, K, K, Cf if epi == EPI_FWD else None, ldc, 0, Cn, ldn, Ct, Mp, bias, H, ldh, Ht, Mp)])
     want = elu(Av @ Bv.T + bias) if epi == EPI_FWD else (Av @ Bv.T) * np.where(Hv > 0, 1.0, Hv + 1.0)
     if epi == EPI_FWD:
-        np.testing.assert_allclose(Cf, want, rtol=1e-5, atol=2e-5)
+        np.testing.assert_allclose(Cf[:, :N], want, rtol=1e-5, atol=2e-5)
+    else:
+        assert np.isnan(Cf).all()                                            # a product without an fp32 result writes none
+    if odd:
+        assert np.isnan(Cf[:, N:]).all()                                     # the padding column of every row stays as it was
     np.testing.assert_allclose(from_elems(Cn, bf)[:, :N], want, rtol=8e-3 if bf else 1e-5, atol=1e-3 if bf else 2e-5)
     assert not from_elems(Cn, bf)[:, N:].any()
     np.testing.assert_array_equal(from_elems(Ct, bf)[:, :M], from_elems(Cn, bf)[:, :N].T)
     assert not from_elems(Ct, bf)[:, M:].any()
+
+
+def wide_tile_shape_odd_leading_dimensions(backend, bf, epi, M, tile=2):
+    """wide_tile_shape_all_copies where no row of H, Ht, Cf, Cn or Ct but the first begins on a 16-byte piece: the scalar fallbacks of
+    the epilogue's piece loads and stores, whole and ragged, in both orientations"""
+    wide_tile_shape_all_copies(backend, bf, epi, M, tile, odd=True)
 
 
 def data_gradient_product(backend, bf, tile=0):

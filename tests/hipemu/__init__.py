@@ -73,7 +73,7 @@ def build_gemm(force=False):
     """seqdex_amd/csrc/sdx_gemm_nt.h (k_gemm_nt, k_stage) on the emulator: MFMA as a wave collective, global_load_lds as a per-lane copy"""
     srcs = [os.path.join(HERE, "hipemu.cpp"), os.path.join(HERE, "gemm_driver.cpp")]
     deps = srcs + [os.path.abspath(__file__), os.path.join(HERE, "include", "hip", "hip_runtime.h"), os.path.join(HERE, "include", "hipemu_mfma.h")] + \
-        [os.path.join(CSRC, f) for f in ("sdx_gemm_nt.h", "sdx_gemm.h", "sdx_common.h")]
+        [os.path.join(CSRC, f) for f in ("sdx_gemm_nt.h", "sdx_gemm.h", "sdx_mfma.h", "sdx_common.h")]
     if not force and os.path.exists(_GEMM_SO) and all(os.path.getmtime(_GEMM_SO) >= os.path.getmtime(d) for d in deps):
         return _GEMM_SO
     objs = []

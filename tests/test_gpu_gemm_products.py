@@ -24,11 +24,7 @@ pytestmark = pytest.mark.gpu
 import gemm_nt_cases as GC  # noqa: E402
 
 
-class NtArgs(C.Structure):      # sdx_gemm_nt.h
-    _fields_ = [("A", C.c_void_p), ("lda", C.c_int), ("B", C.c_void_p), ("ldb", C.c_int), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
-                ("kchunk", C.c_int), ("Cf", C.c_void_p), ("ldc", C.c_int), ("cz", C.c_size_t), ("Cn", C.c_void_p), ("ldn", C.c_int),
-                ("Ct", C.c_void_p), ("ldt", C.c_int), ("bias", C.c_void_p), ("H", C.c_void_p), ("ldh", C.c_int), ("Ht", C.c_void_p), ("ldht", C.c_int),
-                ("rowsum", C.c_void_p)]
+NtArgs = GC.NtArgs              # sdx_gemm_nt.h
 
 
 class GemmArgs(C.Structure):    # sdx_gemm.h
@@ -65,9 +61,7 @@ class Compiled:
         arr = (NtArgs * 3)()
         for q, g in enumerate(problems):
             t = {k: torch.from_numpy(getattr(g, k)).cuda() for k in ("A", "B", "Cf", "Cn", "Ct", "bias", "H", "Ht") if getattr(g, k) is not None}
-            p = lambda k: t[k].data_ptr() if k in t else None
-            arr[q] = NtArgs(p("A"), g.lda, p("B"), g.ldb, g.M, g.N, g.K, g.kchunk, p("Cf"), g.ldc, g.cz, p("Cn"), g.ldn, p("Ct"), g.ldt, p("bias"),
-                            p("H"), g.ldh, p("Ht"), g.ldht, None if g.rowsum_off is None else t["Cf"].data_ptr() + 4 * g.rowsum_off)
+            arr[q] = GC.nt_args(g, lambda k: t[k].data_ptr() if k in t else None)
             dev.append(t)
             outs += [(getattr(g, k), t[k]) for k in ("Cf", "Cn", "Ct") if k in t]
         assert call(arr, len(problems)) == 0
@@ -116,6 +110,14 @@ def test_narrow_tile_shape(gpu, bf, tile):
 @pytest.mark.parametrize("M", GC.WIDE_M)
 def test_wide_tile_shape_all_copies(gpu, bf, epi, M, tile):
     GC.wide_tile_shape_all_copies(gpu, bf, epi, M, tile)
+
+
+@pytest.mark.parametrize("tile", TILES)
+@pytest.mark.parametrize("bf", GC.BF)
+@pytest.mark.parametrize("epi", GC.WIDE_EPIS)
+@pytest.mark.parametrize("M", GC.WIDE_M)
+def test_wide_tile_shape_odd_leading_dimensions(gpu, bf, epi, M, tile):
+    GC.wide_tile_shape_odd_leading_dimensions(gpu, bf, epi, M, tile)
 
 
 @pytest.mark.parametrize("tile", TILES)

@@ -15,7 +15,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 import gemm_nt_cases as GC  # noqa: E402
-from gemm_nt_cases import EPI_FWD, EPI_TN, elems as _elems, from_elems as _from_elems  # noqa: E402
+from gemm_nt_cases import elems as _elems, from_elems as _from_elems  # noqa: E402
 
 pytestmark = pytest.mark.skipif(not os.path.exists("/opt/rocm/lib/llvm/bin/clang++"), reason="needs ROCm's clang++ for the host build")
 
@@ -25,11 +25,9 @@ def lib():
     from tests import hipemu
     l = C.CDLL(hipemu.build_gemm())
     vp, i, fp = C.c_void_p, C.c_int, C.c_void_p
-    l.emu_gemm_nt.argtypes = [i, i, vp, i, vp, i, i, i, i, i, i, fp, i, C.c_longlong, vp, i, vp, i, fp, vp, i, vp, i, fp]
-    l.emu_gemm_nt_narrow.argtypes = [i, vp, i, vp, i, i, i, i, fp, i, vp, i, fp]
+    l.emu_gemm_nt.argtypes = [i, i, C.POINTER(GC.NtArgs), i, i, i]
+    l.emu_gemm_tt.argtypes = [C.POINTER(GC.NtArgs), i, i, i]
     l.emu_stage.argtypes = [i, fp, i, i, i, i, vp, i, vp, i]
-    l.emu_gemm_nt_wide.argtypes = [i, i, vp, i, vp, i, i, i, i, fp, i, vp, i, vp, i, fp, vp, i, vp, i]
-    l.emu_gemm_tt.argtypes = [vp, i, vp, i, i, i, i, i, i, fp, i, C.c_longlong, vp, i]
     return l
 
 
@@ -38,31 +36,20 @@ def _p(a):
 
 
 class Emulated:
-    """backend of gemm_nt_cases: one product per launch through the entry points of tests/hipemu/gemm_driver.cpp.  tile 0: the launcher
-    (emu_gemm_nt); a forced tile of k_gemm_nt has an entry of its own (emu_gemm_nt_narrow: forward, no element copy;
-    emu_gemm_nt_wide: forward / data gradient)"""
+    """backend of gemm_nt_cases: 1..3 products per launch, at any tile, through the header's launchers (tests/hipemu/gemm_driver.cpp)"""
 
     def __init__(self, lib):
         self.lib = lib
 
+    @staticmethod
+    def _args(problems):
+        return (GC.NtArgs * len(problems))(*[GC.nt_args(g, lambda k: None if getattr(g, k) is None else getattr(g, k).ctypes.data) for g in problems])
+
     def nt(self, bf, epi, tile, splits, problems):
-        (g,) = problems
-        rowsum = None if g.rowsum_off is None else C.c_void_p(g.Cf.ctypes.data + 4 * g.rowsum_off)
-        if tile == 0:
-            self.lib.emu_gemm_nt(bf, epi, _p(g.A), g.lda, _p(g.B), g.ldb, g.M, g.N, g.K, g.kchunk, splits, _p(g.Cf), g.ldc, g.cz, _p(g.Cn), g.ldn,
-                                 _p(g.Ct), g.ldt, _p(g.bias), _p(g.H), g.ldh, _p(g.Ht), g.ldht, rowsum)
-        elif tile == 1:
-            assert epi == EPI_FWD and splits == 1 and g.Cn is None and g.kchunk == g.K
-            self.lib.emu_gemm_nt_narrow(bf, _p(g.A), g.lda, _p(g.B), g.ldb, g.M, g.N, g.K, _p(g.Cf), g.ldc, _p(g.Ct), g.ldt, _p(g.bias))
-        else:
-            assert epi != EPI_TN and splits == 1 and g.kchunk == g.K
-            self.lib.emu_gemm_nt_wide(bf, epi, _p(g.A), g.lda, _p(g.B), g.ldb, g.M, g.N, g.K, _p(g.Cf), g.ldc, _p(g.Cn), g.ldn, _p(g.Ct), g.ldt,
-                                      _p(g.bias), _p(g.H), g.ldh, _p(g.Ht), g.ldht)
+        self.lib.emu_gemm_nt(bf, epi, self._args(problems), len(problems), splits, tile)
 
     def tt(self, tile, splits, problems):
-        (g,) = problems
-        self.lib.emu_gemm_tt(_p(g.A), g.lda, _p(g.B), g.ldb, g.M, g.N, g.K, g.kchunk, splits, _p(g.Cf), g.ldc, g.cz,
-                             C.c_void_p(g.Cf.ctypes.data + 4 * g.rowsum_off), tile)
+        self.lib.emu_gemm_tt(self._args(problems), len(problems), splits, tile)
 
 
 @pytest.fixture(scope="module")
@@ -122,3 +109,59 @@ def test_stage_kernel(lib, bf):
 @pytest.mark.parametrize("R,Nl,Kl,ldb,splits", GC.TT_SHAPES)
 def test_weight_gradient_from_row_major_operands(emu, tile, R, Nl, Kl, ldb, splits):
     GC.weight_gradient_from_row_major_operands(emu, tile, R, Nl, Kl, ldb, splits)
+
+
+# ---- the cases above at the tiles they do not name, and the ones with three products per launch: what tests/test_gpu_gemm_products.py
+# runs on the compiled kernels (tile 1 = 128 x 64, 2 = 128 x 128)
+TILES = [1, 2]
+
+
+@pytest.mark.parametrize("tile", TILES)
+@pytest.mark.parametrize("bf", GC.BF)
+@pytest.mark.parametrize("M,N,K", GC.FORWARD_SHAPES)
+def test_forward_product_all_outputs_at_tile(emu, bf, M, N, K, tile):
+    GC.forward_product_all_outputs(emu, bf, M, N, K, tile)
+
+
+@pytest.mark.parametrize("tile", TILES)
+@pytest.mark.parametrize("bf", GC.BF)
+def test_forward_products_of_three_shapes_in_one_launch(emu, bf, tile):
+    GC.forward_products_of_three_shapes_in_one_launch(emu, bf, tile)
+
+
+@pytest.mark.parametrize("bf", GC.BF)
+def test_narrow_tile_shape_at_wide_tile(emu, bf):
+    GC.narrow_tile_shape(emu, bf, 2)
+
+
+@pytest.mark.parametrize("bf", GC.BF)
+@pytest.mark.parametrize("epi", GC.WIDE_EPIS)
+@pytest.mark.parametrize("M", GC.WIDE_M)
+def test_wide_tile_shape_all_copies_at_narrow_tile(emu, bf, epi, M):
+    GC.wide_tile_shape_all_copies(emu, bf, epi, M, 1)
+
+
+@pytest.mark.parametrize("tile", TILES)
+@pytest.mark.parametrize("bf", GC.BF)
+@pytest.mark.parametrize("epi", GC.WIDE_EPIS)
+@pytest.mark.parametrize("M", GC.WIDE_M)
+def test_wide_tile_shape_odd_leading_dimensions(emu, bf, epi, M, tile):
+    GC.wide_tile_shape_odd_leading_dimensions(emu, bf, epi, M, tile)
+
+
+@pytest.mark.parametrize("tile", TILES)
+@pytest.mark.parametrize("bf", GC.BF)
+def test_data_gradient_product_at_tile(emu, bf, tile):
+    GC.data_gradient_product(emu, bf, tile)
+
+
+@pytest.mark.parametrize("tile", TILES)
+@pytest.mark.parametrize("bf", GC.BF)
+@pytest.mark.parametrize("splits", GC.SPLITS)
+def test_weight_gradient_product_with_row_sums_at_tile(emu, bf, splits, tile):
+    GC.weight_gradient_product_with_row_sums(emu, bf, splits, tile)
+
+
+@pytest.mark.parametrize("tile", TILES)
+def test_weight_gradients_of_three_shapes_in_one_launch(emu, tile):
+    GC.weight_gradients_of_three_shapes_in_one_launch(emu, tile)
