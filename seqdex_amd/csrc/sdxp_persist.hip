@@ -12,6 +12,10 @@
 // (Phase A's shadow holds Adam of layer 1 alone.  The Gram of the layer-0 inputs, which stood in it, does not depend on the step - the
 // inputs are dataset rows: k_input_grams at the end of this file forms every minibatch's once per epoch, behind the pre-normalisation,
 // and the step fetches its 32 floats with its rows.)
+// (What closes a phase on one wave or one thread while the other waves stand at its barrier - the publish tails of forward L0 / L1 / L2 on wave 0,
+// the value rows and the bias tail of the head forward on waves 7 and 0, the statistics / learning-rate thread of the dY1 shadow - asks LDS for
+// all its operands in ONE round trip, and a publish tail forms one (network, sample, row) per lane, the three networks of a word meeting in the
+// storing lane by cross-lane moves: sdxp_persist_tails.h.)
 //
 // Ownership (shipped network 396/564 -> 1024 -> 512 -> 256 -> 23/1, minibatch 4):
 //   W0 rows      : CU g, wave w owns half (w&1) of row 4g+(w>>1) of actor, critic and central value
@@ -33,6 +37,7 @@
 #include "sdxp_persist_exchange.h"   // lq_* / ll_* tagged words between the CUs
 #include "sdxp_persist_sums.h"       // row / wave / block sums, Gram accumulators
 #include "sdxp_persist_adam.h"       // adam1, adam1p, opaque, SDX_PIN*
+#include "sdxp_persist_tails.h"      // fwd_tail, stats_lr_once: the one-wave / one-thread pieces that close a phase
 
 // dataset-row helpers
 __device__ __forceinline__ const float* obs_rows(const SdxpDev& D, int mb) { return D.mb_obs + (size_t)mb * MB * D.obs_dim; }
@@ -318,13 +323,10 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
         fpart_store(S, u, wave, lane);
       }
       __syncthreads();
-      if (tid < MB * 4) {   // (sample s, owned row r): the three networks' outputs in one packed word
-        const int s = tid / 4, r = tid % 4;
+      if (wave == 0) {   // wave 0: lane (net, sample s, owned row r) < 48 forms one output, lane (s, r) < 16 stores the three networks' in one packed word (fwd_tail)
         float y[3];
-#pragma unroll
-        for (int net = 0; net < 3; ++net)
-          y[net] = elu(S.fpart[(net * MB + s) * NWV + 2 * r] + S.fpart[(net * MB + s) * NWV + 2 * r + 1] + S.bias[BIAS_L0 + net * 4 + r]);
-        lq_store(LQ, LQ_X1 + (unsigned)s * U0 + 4 * g + r, y[0], y[1], y[2], tag);
+        fwd_tail<0>(S, lane, y);
+        if (tid < MB * 4) lq_store(LQ, LQ_X1 + (unsigned)(tid / 4) * U0 + 4 * g + tid % 4, y[0], y[1], y[2], tag);
       }
       TS(2)
       // (the Gram of the layer-0 inputs that stood here, in the shadow of the x1 exchange, does not depend on the step: it arrives from the
@@ -371,15 +373,10 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
         fpart_store(S, u, wave, lane);
       }
       __syncthreads();
-      if (tid < MB * 2) {
-        const int s = tid / 2, r = tid % 2;
+      if (wave == 0) {   // wave 0: lane (net, s, r) < 24 forms one output, lane (s, r) < 8 stores the word (fwd_tail)
         float y[3];
-#pragma unroll
-        for (int net = 0; net < 3; ++net) {
-          const float* q = &S.fpart[(net * MB + s) * NWV + 4 * r];
-          y[net] = elu(q[0] + q[1] + q[2] + q[3] + S.bias[BIAS_L1 + net * 2 + r]);
-        }
-        lq_store(LQ, LQ_X2 + (unsigned)s * U1 + 2 * g + r, y[0], y[1], y[2], tag);
+        fwd_tail<1>(S, lane, y);
+        if (tid < MB * 2) lq_store(LQ, LQ_X2 + (unsigned)(tid / 2) * U1 + 2 * g + tid % 2, y[0], y[1], y[2], tag);
       }
       TS(5)
       // (the Gram of x1 used to sit here: this shadow was 2.7 us against an edge of 2.1; it now shares ONE block reduction with the
@@ -480,18 +477,10 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       fwd2_store(S, u, wave, lane);
     }
     __syncthreads();
-    if (tid < MB) {
-      const int s = tid;
+    if (wave == 0) {   // wave 0: lane (net, s) < 12 forms one output, lane s < 4 stores the word (fwd_tail)
       float y[3];
-#pragma unroll
-      for (int net = 0; net < 3; ++net) {
-        const float* q = &S.fpart[(net * MB + s) * NWV];
-        float t = S.bias[BIAS_L2 + net];
-#pragma unroll
-        for (int w = 0; w < NWV; ++w) t += q[w];
-        y[net] = elu(t);
-      }
-      lq_store(LQ, LQ_X3 + (unsigned)s * U2 + g, y[0], y[1], y[2], tag);
+      fwd_tail<2>(S, lane, y);
+      if (tid < MB) lq_store(LQ, LQ_X3 + (unsigned)tid * U2 + g, y[0], y[1], y[2], tag);
     }
     TS(8)
     // (this minibatch's actions and old (mu, sigma) go to LDS before the Grams: three registers fewer across the 60-value reduction)
@@ -597,67 +586,8 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     }
     TS(10)
     __syncthreads();
-    // head forward: wave per row
-    {
-      // rows wave, wave + 8, wave + 16 (< 23: actor rows, except row 23 = the critic's value on wave 7) and wave + 24 (only wave 0: row 24,
-      // the central value): the actor rows of a wave share ONE set of x3 loads
-      float q[HR * MB], u[HR], xa[MB][4];   // value MB j + s: lane s < 4 ends with sample s of the wave's rows
-#pragma unroll
-      for (int s = 0; s < MB; ++s)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) xa[s][e] = S.x3[0][s][lane + 64 * e];
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int s = 0; s < MB; ++s) {
-          float t = 0.0f;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) t += wh[j][e] * xa[s][e];
-          q[MB * j + s] = t;
-        }
-      if (wave == NWV - 1) {          // row 23: critic value (net 1)
-#pragma unroll
-        for (int s = 0; s < MB; ++s) {
-          float t = 0.0f;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) t += wh[2][e] * S.x3[1][s][lane + 64 * e];
-          q[MB * 2 + s] = t;
-        }
-      } else {
-#pragma unroll
-        for (int s = 0; s < MB; ++s) {
-          float t = 0.0f;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) t += wh[2][e] * xa[s][e];
-          q[MB * 2 + s] = t;
-        }
-      }
-      if (wave == 0) {                // row 24: central value (net 2), the fourth quad of a 16-wide butterfly on this wave only
-#pragma unroll
-        for (int s = 0; s < MB; ++s) {
-          float t = 0.0f;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) t += wh[3][e] * S.x3[2][s][lane + 64 * e];
-          q[MB * 3 + s] = t;
-        }
-        wave_sums<HR * MB>(q, u, lane);
-      } else {
-        float q3[3 * MB], u3[3];
-#pragma unroll
-        for (int i = 0; i < 3 * MB; ++i) q3[i] = q[i];
-        wave_sums<3 * MB>(q3, u3, lane);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) u[j] = u3[j];
-        u[3] = 0.0f;
-      }
-      if (lane < MB) {                // sample s = lane: one bias per row
-#pragma unroll
-        for (int j = 0; j < HR; ++j) {
-          const int row = wave + 8 * j;
-          if (row < A + 2) { const float y = u[j] + S.bias[BIAS_HEAD + row]; if (row < A) S.mu[lane][row] = y; else S.val[row - A][lane] = y; }
-        }
-      }
-    }
+    // head forward: wave per row (head_forward: the value rows' operands and the rows' biases are requested with the actor rows')
+    head_forward(S, wh, wave, lane);
     __syncthreads();
     TS(11)
     // Column view of the head words (this lane's column c2n, rows 13 c2c .. 13 c2c + 12; first used by the heads' backward): requested
@@ -860,24 +790,8 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
         S.scal[SC_CV_LR_BC1] = C.cv_lr / (float)(1.0 - C.cv_b1); S.scal[SC_CV_ISQ] = 1.0f / sqrtf((float)(1.0 - C.cv_b2));
       }
     }
-    auto stats_and_lr = [&]() {
-    if (tid == T_STATS) {
-      PLds::Ctl& C = S.ctl;
-      float t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0, t6 = 0;
-      for (int s = 0; s < MB; ++s) { t1 += S.stat[s][STAT_ACTOR]; t2 += S.stat[s][STAT_CRITIC]; t3 += S.stat[s][STAT_BOUNDS]; t4 += S.stat[s][STAT_KL]; t5 += S.stat[s][STAT_CV]; t6 += S.stat[s][STAT_ENTROPY]; }
-      const float kl = t4 * invM;
-      C.sum_a += t1 * invM; C.sum_c += t2 * invM; C.sum_b += t3 * invM; C.sum_kl += kl; C.sum_cv += t5 * invM; C.sum_ent += t6 * invM;
-      C.last_kl = kl;
-      if (D.adaptive_lr) {         // legacy schedule: after every minibatch (PS:306-312)
-        // (the two thresholds are formed HERE from an opaque copy: hoisted out of the step loop they cost two registers for the whole launch,
-        // and with the first look at the norm words in flight one of them was spilled and reloaded - a scratch load and a vmcnt(0) - in this shadow)
-        float klt = D.kl_threshold;
-        SDX_OPAQUE(klt);
-        if (kl > 2.0f * klt) C.ac_lr = fmaxf(C.ac_lr / 1.5f, 1e-6f);
-        if (kl < 0.5f * klt) C.ac_lr = fminf(C.ac_lr * 1.5f, 1e-2f);
-      }
-    }
-    };
+    // (everything the thread reads from LDS is requested at once, the arithmetic is that of the serial loop: stats_lr_once)
+    auto stats_and_lr = [&]() { if (tid == T_STATS) stats_lr_once(S, invM, D.adaptive_lr, D.kl_threshold); };
     if constexpr (SINGLE) { SDX_LDS_BARRIER(); stats_and_lr(); }   // (one minibatch: no reduction here whose barrier the statistics could share)
     if constexpr (!SINGLE) {
       // Round 6: the Gram of x3 (waves 0..3, unit = tid) and the Gram of dY2 (waves 4..7, unit = tid - 256; it used to wait for the dY0 shadow, whose

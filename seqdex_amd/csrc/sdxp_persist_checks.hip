@@ -1,10 +1,11 @@
-// sdxp_persist_checks.hip — test entries for the machinery of the persistent PPO update (sdxp_persist_sums.h, sdxp_persist_adam.h): each runs the
+// sdxp_persist_checks.hip — test entries for the machinery of the persistent PPO update (sdxp_persist_sums.h, sdxp_persist_adam.h, sdxp_persist_tails.h): each runs the
 // helper k_update_persistent uses beside the form it stands for, in one workgroup, and hands both results back.  Built with the flags of
 // sdxp_persist.hip (Makefile), so that the helpers are compiled here as they are inside the kernel.
 #include "sdx_common.h"
 #include "sdxp_launch.h"
 #include "sdxp_persist_sums.h"
 #include "sdxp_persist_adam.h"
+#include "sdxp_persist_tails.h"
 
 // Test entry (tests/test_gpu_wave_sums.py): one workgroup of NTH threads, in / ref / got are [N][NTH].  ref[i][t] = wave_sum of value i in t's
 // wave, on every lane; got[i][t] = what wave_sums<N> left in lane t for value i - written by the lanes with (t & 3) == (i & 3), the others'
@@ -276,5 +277,228 @@ __global__ __launch_bounds__(NTH) void k_ordered_sum_check(const float* rows, fl
 extern "C" int sdxpk_ordered_sum_check(const float* rows, float* ref, float* got, hipStream_t st) {
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_ordered_sum_check), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PLds)) != hipSuccess) return -1;
   hipLaunchKernelGGL(k_ordered_sum_check, dim3(1), dim3(NTH), sizeof(PLds), st, rows, ref, got);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// Test entry (tests/test_gpu_persist_forward_tails.py): the publish tails of forward L0 / L1 / L2, one workgroup of NTH threads per case.  fpart
+// [n][3 MB NWV] goes into S.fpart, bias [n][64] into S.bias.  ref [n][16][3]: the three networks' outputs the storing lanes (tid < 16 / 8 / 4) would
+// publish, in the form the epoch kernel had before fwd_tail - one lane per (sample, row) forms the three networks one after the other - kept here
+// verbatim as the reference; got [n][16][3]: fwd_tail on the same LDS image (slots of lanes that do not store are not touched); pre [n][48]: the
+// pre-activation of lane (net, sample, row) < 48 / 24 / 12 (fwd_tail_pre).
+template <int L>
+__global__ __launch_bounds__(NTH) void k_forward_tail_check(const float* fpart, const float* bias, float* ref, float* got, float* pre) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  PLds& S = *reinterpret_cast<PLds*>(smem_raw);
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const size_t c = blockIdx.x;
+  if (tid < 3 * MB * NWV) S.fpart[tid] = fpart[c * 3 * MB * NWV + tid];
+  if (tid < 64) S.bias[tid] = bias[c * 64 + tid];
+  __syncthreads();
+  float* rc = ref + c * 48;
+  if constexpr (L == 0) {
+    if (tid < MB * 4) {   // (sample s, owned row r): the three networks' outputs in one packed word
+      const int s = tid / 4, r = tid % 4;
+      float y[3];
+#pragma unroll
+      for (int net = 0; net < 3; ++net)
+        y[net] = elu(S.fpart[(net * MB + s) * NWV + 2 * r] + S.fpart[(net * MB + s) * NWV + 2 * r + 1] + S.bias[BIAS_L0 + net * 4 + r]);
+      rc[tid * 3] = y[0]; rc[tid * 3 + 1] = y[1]; rc[tid * 3 + 2] = y[2];
+    }
+  } else if constexpr (L == 1) {
+    if (tid < MB * 2) {
+      const int s = tid / 2, r = tid % 2;
+      float y[3];
+#pragma unroll
+      for (int net = 0; net < 3; ++net) {
+        const float* q = &S.fpart[(net * MB + s) * NWV + 4 * r];
+        y[net] = elu(q[0] + q[1] + q[2] + q[3] + S.bias[BIAS_L1 + net * 2 + r]);
+      }
+      rc[tid * 3] = y[0]; rc[tid * 3 + 1] = y[1]; rc[tid * 3 + 2] = y[2];
+    }
+  } else {
+    if (tid < MB) {
+      const int s = tid;
+      float y[3];
+#pragma unroll
+      for (int net = 0; net < 3; ++net) {
+        const float* q = &S.fpart[(net * MB + s) * NWV];
+        float t = S.bias[BIAS_L2 + net];
+#pragma unroll
+        for (int w = 0; w < NWV; ++w) t += q[w];
+        y[net] = elu(t);
+      }
+      rc[tid * 3] = y[0]; rc[tid * 3 + 1] = y[1]; rc[tid * 3 + 2] = y[2];
+    }
+  }
+  if (wave == 0) {
+    float y[3];
+    fwd_tail<L>(S, lane, y);
+    if (tid < FwdTail<L>::STORING) { got[c * 48 + tid * 3] = y[0]; got[c * 48 + tid * 3 + 1] = y[1]; got[c * 48 + tid * 3 + 2] = y[2]; }
+    if (lane < FwdTail<L>::LANES) pre[c * 48 + lane] = fwd_tail_pre<L>(S, lane);
+  }
+}
+extern "C" int sdxpk_forward_tail_check(int layer, const float* fpart, const float* bias, int n, float* ref, float* got, float* pre, hipStream_t st) {
+  if (n < 1 || layer < 0 || layer > 2) return -1;
+  const void* k = layer == 0 ? reinterpret_cast<const void*>(k_forward_tail_check<0>) : layer == 1 ? reinterpret_cast<const void*>(k_forward_tail_check<1>) : reinterpret_cast<const void*>(k_forward_tail_check<2>);
+  if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PLds)) != hipSuccess) return -1;
+  if (layer == 0) hipLaunchKernelGGL(k_forward_tail_check<0>, dim3(n), dim3(NTH), sizeof(PLds), st, fpart, bias, ref, got, pre);
+  else if (layer == 1) hipLaunchKernelGGL(k_forward_tail_check<1>, dim3(n), dim3(NTH), sizeof(PLds), st, fpart, bias, ref, got, pre);
+  else hipLaunchKernelGGL(k_forward_tail_check<2>, dim3(n), dim3(NTH), sizeof(PLds), st, fpart, bias, ref, got, pre);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// Test entry (tests/test_gpu_persist_head_forward.py): the head forward of phase D, one workgroup of NTH threads per case.  x3 [n][3][MB][U2] goes
+// into S.x3, hb [n][ACT + 2] into S.bias[BIAS_HEAD ..], hw [n][ACT + 2][U2] into the registers wh[j][e] = row wave + 8 j, column lane + 64 e (zero
+// past the last row, as the kernel's gather leaves them).  out [n][2][MB ACT + 2 MB]: mu [MB][ACT] then val [2][MB] of [0] the form the epoch kernel
+// had before head_forward - the value rows' operands read inside their fma chains, the biases behind the wave sums - kept here verbatim as the
+// reference, and of [1] head_forward on the same inputs.
+__global__ __launch_bounds__(NTH) void k_head_forward_check(const float* x3, const float* hw, const float* hb, float* out) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  PLds& S = *reinterpret_cast<PLds*>(smem_raw);
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const size_t c = blockIdx.x;
+  constexpr int A = ACT, NO = MB * ACT + 2 * MB;
+  for (int i = tid; i < 3 * MB * U2; i += NTH) (&S.x3[0][0][0])[i] = x3[c * 3 * MB * U2 + i];
+  if (tid < A + 2) S.bias[BIAS_HEAD + tid] = hb[c * (A + 2) + tid];
+  float wh[HR][4];
+#pragma unroll
+  for (int j = 0; j < HR; ++j)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { const int row = wave + 8 * j; wh[j][e] = row < A + 2 ? hw[(c * (A + 2) + row) * U2 + lane + 64 * e] : 0.0f; }
+  auto clear = [&]() {
+    if (tid < MB * 32) S.mu[tid / 32][tid % 32] = __builtin_nanf("");
+    if (tid < 2 * MB) S.val[tid / MB][tid % MB] = __builtin_nanf("");
+    __syncthreads();
+  };
+  auto copy_out = [&](float* o) {
+    __syncthreads();
+    if (tid < MB * A) o[tid] = S.mu[tid / A][tid % A];
+    else if (tid >= 128 && tid < 128 + 2 * MB) o[MB * A + tid - 128] = S.val[(tid - 128) / MB][(tid - 128) % MB];
+    __syncthreads();
+  };
+  clear();
+  {
+    // rows wave, wave + 8, wave + 16 (< 23: actor rows, except row 23 = the critic's value on wave 7) and wave + 24 (only wave 0: row 24,
+    // the central value): the actor rows of a wave share ONE set of x3 loads
+    float q[HR * MB], u[HR], xa[MB][4];   // value MB j + s: lane s < 4 ends with sample s of the wave's rows
+#pragma unroll
+    for (int s = 0; s < MB; ++s)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) xa[s][e] = S.x3[0][s][lane + 64 * e];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int s = 0; s < MB; ++s) {
+        float t = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) t += wh[j][e] * xa[s][e];
+        q[MB * j + s] = t;
+      }
+    if (wave == NWV - 1) {          // row 23: critic value (net 1)
+#pragma unroll
+      for (int s = 0; s < MB; ++s) {
+        float t = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) t += wh[2][e] * S.x3[1][s][lane + 64 * e];
+        q[MB * 2 + s] = t;
+      }
+    } else {
+#pragma unroll
+      for (int s = 0; s < MB; ++s) {
+        float t = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) t += wh[2][e] * xa[s][e];
+        q[MB * 2 + s] = t;
+      }
+    }
+    if (wave == 0) {                // row 24: central value (net 2), the fourth quad of a 16-wide butterfly on this wave only
+#pragma unroll
+      for (int s = 0; s < MB; ++s) {
+        float t = 0.0f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) t += wh[3][e] * S.x3[2][s][lane + 64 * e];
+        q[MB * 3 + s] = t;
+      }
+      wave_sums<HR * MB>(q, u, lane);
+    } else {
+      float q3[3 * MB], u3[3];
+#pragma unroll
+      for (int i = 0; i < 3 * MB; ++i) q3[i] = q[i];
+      wave_sums<3 * MB>(q3, u3, lane);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) u[j] = u3[j];
+      u[3] = 0.0f;
+    }
+    if (lane < MB) {                // sample s = lane: one bias per row
+#pragma unroll
+      for (int j = 0; j < HR; ++j) {
+        const int row = wave + 8 * j;
+        if (row < A + 2) { const float y = u[j] + S.bias[BIAS_HEAD + row]; if (row < A) S.mu[lane][row] = y; else S.val[row - A][lane] = y; }
+      }
+    }
+  }
+  copy_out(out + c * 2 * NO);
+  clear();
+  head_forward(S, wh, wave, lane);
+  copy_out(out + c * 2 * NO + NO);
+}
+extern "C" int sdxpk_head_forward_check(const float* x3, const float* hw, const float* hb, int n, float* out, hipStream_t st) {
+  if (n < 1) return -1;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_head_forward_check), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PLds)) != hipSuccess) return -1;
+  hipLaunchKernelGGL(k_head_forward_check, dim3(n), dim3(NTH), sizeof(PLds), st, x3, hw, hb, out);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// Test entry (tests/test_gpu_persist_stats_thread.py): the statistics / learning-rate thread of the dY1 shadow, one workgroup of NTH threads per
+// case (thread T_STATS does the work, as in the kernel).  in [n][40]: S.stat [MB][8] (columns STAT_ACTOR .. STAT_ENTROPY are read), the six running
+// sums (a, c, b, kl, cv, ent), ac_lr, kl_threshold; adaptive [n]: the adaptive_lr flag.  out [n][2][8]: the six sums, last_kl, ac_lr of [0] the
+// serial loop the epoch kernel ran before stats_lr_once - every S.stat pair and every running sum read behind the arithmetic in front of it - kept
+// here verbatim as the reference, and of [1] stats_lr_once on the same inputs.
+__global__ __launch_bounds__(NTH) void k_stats_thread_check(const float* in, const int* adaptive, float* out) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  PLds& S = *reinterpret_cast<PLds*>(smem_raw);
+  const int tid = threadIdx.x;
+  const size_t c = blockIdx.x;
+  const float* ic = in + c * 40;
+  const int adaptive_lr = adaptive[c];
+  const float kl_threshold = ic[39];
+  const float invM = 1.0f / (float)MB;
+  auto fill = [&]() {
+    if (tid < MB * 8) S.stat[tid / 8][tid % 8] = ic[tid];
+    if (tid == 0) {
+      PLds::Ctl& C = S.ctl;
+      C.sum_a = ic[32]; C.sum_c = ic[33]; C.sum_b = ic[34]; C.sum_kl = ic[35]; C.sum_cv = ic[36]; C.sum_ent = ic[37]; C.ac_lr = ic[38]; C.last_kl = __builtin_nanf("");
+    }
+    __syncthreads();
+  };
+  auto copy_out = [&](float* o) {
+    __syncthreads();
+    if (tid == 0) {
+      const PLds::Ctl& C = S.ctl;
+      o[0] = C.sum_a; o[1] = C.sum_c; o[2] = C.sum_b; o[3] = C.sum_kl; o[4] = C.sum_cv; o[5] = C.sum_ent; o[6] = C.last_kl; o[7] = C.ac_lr;
+    }
+    __syncthreads();
+  };
+  fill();
+  if (tid == T_STATS) {
+    PLds::Ctl& C = S.ctl;
+    float t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0, t6 = 0;
+    for (int s = 0; s < MB; ++s) { t1 += S.stat[s][STAT_ACTOR]; t2 += S.stat[s][STAT_CRITIC]; t3 += S.stat[s][STAT_BOUNDS]; t4 += S.stat[s][STAT_KL]; t5 += S.stat[s][STAT_CV]; t6 += S.stat[s][STAT_ENTROPY]; }
+    const float kl = t4 * invM;
+    C.sum_a += t1 * invM; C.sum_c += t2 * invM; C.sum_b += t3 * invM; C.sum_kl += kl; C.sum_cv += t5 * invM; C.sum_ent += t6 * invM;
+    C.last_kl = kl;
+    if (adaptive_lr) {         // legacy schedule: after every minibatch (PS:306-312)
+      float klt = kl_threshold;
+      SDX_OPAQUE(klt);
+      if (kl > 2.0f * klt) C.ac_lr = fmaxf(C.ac_lr / 1.5f, 1e-6f);
+      if (kl < 0.5f * klt) C.ac_lr = fminf(C.ac_lr * 1.5f, 1e-2f);
+    }
+  }
+  copy_out(out + c * 16);
+  fill();
+  if (tid == T_STATS) stats_lr_once(S, invM, adaptive_lr, kl_threshold);
+  copy_out(out + c * 16 + 8);
+}
+extern "C" int sdxpk_stats_thread_check(const float* in, const int* adaptive, int n, float* out, hipStream_t st) {
+  if (n < 1) return -1;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_stats_thread_check), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PLds)) != hipSuccess) return -1;
+  hipLaunchKernelGGL(k_stats_thread_check, dim3(n), dim3(NTH), sizeof(PLds), st, in, adaptive, out);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
