@@ -38,6 +38,7 @@
 #include "sdxp_persist_sums.h"       // row / wave / block sums, Gram accumulators
 #include "sdxp_persist_adam.h"       // adam1, adam1p, opaque, SDX_PIN*
 #include "sdxp_persist_tails.h"      // fwd_tail, stats_lr_once: the one-wave / one-thread pieces that close a phase
+#include "sdxp_persist_phase_d.h"    // loss_request / loss_front / loss_back, head_backward: the on-chain pieces of phase D behind the head forward
 
 // dataset-row helpers
 __device__ __forceinline__ const float* obs_rows(const SdxpDev& D, int mb) { return D.mb_obs + (size_t)mb * MB * D.obs_dim; }
@@ -445,7 +446,11 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     float pf_adv = 0.0f, pf_nlp = 0.0f, pf_ret = 0.0f, pf_val = 0.0f;   // per-sample scalars, held by the lane that forms the sample's losses
     if (tid < MB * 32 && (tid % 32) == 31) {
       const size_t i = r0 + tid / 32;
-      pf_adv = D.adv[i]; pf_nlp = D.mb_neglogp[i]; pf_ret = D.returns[i]; pf_val = D.mb_values[i];
+      pf_adv = D.adv[i]; pf_nlp = D.mb_neglogp[i];
+    }
+    if (tid >= T_VLOSS && tid < T_VLOSS + 2 * MB) {   // (the value-head loss lanes (j, s): loss_front)
+      const size_t i = r0 + (tid - T_VLOSS) % MB;
+      pf_ret = D.returns[i]; pf_val = D.mb_values[i];
     }
     if (tid < MB * 32 && (tid % 32) < A) {
       const size_t i = (r0 + tid / 32) * A + tid % 32;
@@ -598,6 +603,10 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     // merge the compiler's counter model waits for everything outstanding at the next use of any loaded register - that use would be
     // pf_adv in the loss phase, i.e. the column loads' whole round trip: 0.6 us on the chain)
     SDX_OPAQUE(pf_adv); SDX_OPAQUE(pf_nlp); SDX_OPAQUE(pf_ret); SDX_OPAQUE(pf_val);
+    // (the z chain's four LDS operands are asked for HERE, in front of the column view's address arithmetic and loads: loss_request)
+    ZOps zo;
+    loss_request(S, tid, zo);
+    __builtin_amdgcn_sched_barrier(0);
     float wc[13];      // (row 25 = 13 + 12 does not exist: its slot repeats row 24 and is never used)
     if (step == 0) {
 #pragma unroll
@@ -611,62 +620,21 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       }
     }
     const float invM = 1.0f / (float)MB;
-    // (the loss phase restates sdxp_ppo_terms.h in place: calling its functions here changed this kernel's register allocation and schedule)
+    // (the loss phase restates sdxp_ppo_terms.h: loss_front / loss_back, sdxp_persist_phase_d.h.  Only what the gradients need: the KL, bounds and
+    // entropy terms of the statistics are formed in the dY1 shadow, on waves 5 and 7)
     {
-      // (only what the gradients need: the KL, bounds and entropy terms of the statistics are formed in the dY1 shadow, on waves 5 and 7)
-      float r_nlp = 0.0f;
-      if (tid < MB * 32) {
+      const LossCfg lc = {D.e_clip, D.critic_coef, D.bounds_coef, (bool)D.clip_value};
+      float q, bt;
+      loss_front(S, lc, tid, zo, pf_adv, pf_nlp, pf_ret, pf_val, invM, q, bt);
+      SDX_LDS_BARRIER();   // LDS traffic only: the column view's loads stay in flight (a __syncthreads() would wait for them)
+      loss_back(S, tid, q, bt, invM);
+      if (g == 0 && tid < MB * 32 && tid % 32 < A) {   // update_mu_sigma (RC:1358), CU 0 only
         const int s = tid / 32, a = tid % 32;
-        // z of (sample s, action a): formed by the thread that uses it here; S.z is only for the dmu / dlogstd lanes after the barrier below
-        const float zz = (a < A) ? (S.act[s][a] - S.mu[s][a]) / S.sgm[a] : 0.0f;
-        S.z[s][a] = zz;
-        if (a < A) r_nlp = 0.5f * zz * zz + S.ls[a];
+        __hip_atomic_store(&D.mb_mus[(r0 + s) * A + a], S.mu[s][a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&D.mb_sigmas[(r0 + s) * A + a], S.sgm[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
-      r_nlp = half_sum(r_nlp);
-      if (tid < MB * 32 && (tid % 32) == 31) {
-        const int s = tid / 32;
-        const float nlp = r_nlp + 0.5f * 1.8378770664093453f * (float)A;
-        const float adv = pf_adv;
-        const float ratio = expf(pf_nlp - nlp);
-        const float L1 = -adv * ratio, L2 = -adv * clampf(ratio, 1.0f - D.e_clip, 1.0f + D.e_clip);
-        const bool inr = ratio >= 1.0f - D.e_clip && ratio <= 1.0f + D.e_clip;
-        S.gnlp[s] = (L1 > L2 || inr) ? adv * ratio : 0.0f;
-        const float R = pf_ret, vo = pf_val;
-        float closs[2];
-        for (int j = 0; j < 2; ++j) {
-          const float v = S.val[j][s];
-          const float vc = vo + clampf(v - vo, -D.e_clip, D.e_clip);
-          const float c1v = (v - R) * (v - R), c2v = (vc - R) * (vc - R);
-          float d;
-          if (D.clip_value) {
-            closs[j] = fmaxf(c1v, c2v);
-            const bool inv = fabsf(v - vo) <= D.e_clip;
-            d = (c1v > c2v || inv) ? 2.0f * (v - R) : 0.0f;
-          } else { closs[j] = c1v; d = 2.0f * (v - R); }
-          S.dv[j][s] = (j == 0 ? 0.5f * D.critic_coef : 1.0f) * d * invM;
-        }
-        S.stat[s][STAT_ACTOR] = fmaxf(L1, L2); S.stat[s][STAT_CRITIC] = closs[0]; S.stat[s][STAT_CV] = closs[1];
-      }
+      SDX_LDS_BARRIER();   // LDS traffic only: the column view's loads stay in flight (a __syncthreads() would wait for them)
     }
-    SDX_LDS_BARRIER();   // LDS traffic only: the column view's loads stay in flight (a __syncthreads() would wait for them)
-    if (tid < MB * 32) {
-      const int s = tid / 32, a = tid % 32;
-      float dmu = 0.0f;
-      if (a < A) {
-        const float sg = S.sgm[a], mu = S.mu[s][a];
-        const float hi = fmaxf(mu - 1.1f, 0.0f), lo = fminf(mu + 1.1f, 0.0f);
-        dmu = S.gnlp[s] * (-(S.z[s][a] / sg)) * invM + D.bounds_coef * (2.0f * hi + 2.0f * lo) * invM;
-        if (g == 0) { __hip_atomic_store(&D.mb_mus[(r0 + s) * A + a], mu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(&D.mb_sigmas[(r0 + s) * A + a], sg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }   // update_mu_sigma (RC:1358)
-      }
-      S.dmu[s][a] = dmu;
-    }
-    if (tid >= T_LS && tid < T_LS + 32) {
-      const int a = tid - T_LS;
-      float dls = 0.0f;
-      if (a < A) for (int s = 0; s < MB; ++s) dls += S.gnlp[s] * (1.0f - S.z[s][a] * S.z[s][a]) * invM;
-      S.dls[a] = dls;
-    }
-    SDX_LDS_BARRIER();   // LDS traffic only: the column view's loads stay in flight (a __syncthreads() would wait for them)
     TS(12)
     refresh();   // (c2n / c2c and the addresses formed from them are derived HERE: formed in front of the head forward they were spilled across it)
     // backward through the heads: lane (column k = c2n, row half c2c) forms its part of dX3[.][k]; the two halves of a column are lanes l and
@@ -679,23 +647,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     // stores below sit in front of block_sum's barriers, their readers - the Gram of dY2, dyown[.][.][DY_L2], the next step's Adam of layer 2 -
     // behind them.)
     float d2[3][MB];
-    {
-      const int k = c2n, jr = 13 * c2c;
-      float a0[MB], a1[MB], a2[MB];
-#pragma unroll
-      for (int s = 0; s < MB; ++s) a0[s] = 0.0f;
-#pragma unroll
-      for (int j = 0; j < 13; ++j)
-#pragma unroll
-        for (int s = 0; s < MB; ++s) a0[s] += S.dmu[s][jr + j] * wc[j];
-#pragma unroll
-      for (int s = 0; s < MB; ++s) {
-        a1[s] = c2c ? S.dv[0][s] * wc[A - 13] : 0.0f; a2[s] = c2c ? S.dv[1][s] * wc[A - 12] : 0.0f;
-        d2[0][s] = pair_sum(a0[s]) * elu_g(S.x3[0][s][k]);
-        d2[1][s] = pair_sum(a1[s]) * elu_g(S.x3[1][s][k]);
-        d2[2][s] = pair_sum(a2[s]) * elu_g(S.x3[2][s][k]);
-      }
-    }
+    head_backward(S, wc, c2c, c2n, d2);   // (its LDS operands requested ahead of the chains: sdxp_persist_phase_d.h)
     TS(13)
     // backward L2 with the column copy: dY1[net][s][2g+c] = (sum_n dY2[net][s][n] W2[n][2g+c]) * elu'(x2[net][s][2g+c])
     {

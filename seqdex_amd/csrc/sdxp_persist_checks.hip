@@ -1,4 +1,4 @@
-// sdxp_persist_checks.hip — test entries for the machinery of the persistent PPO update (sdxp_persist_sums.h, sdxp_persist_adam.h, sdxp_persist_tails.h): each runs the
+// sdxp_persist_checks.hip — test entries for the machinery of the persistent PPO update (sdxp_persist_sums.h, sdxp_persist_adam.h, sdxp_persist_tails.h, sdxp_persist_phase_d.h): each runs the
 // helper k_update_persistent uses beside the form it stands for, in one workgroup, and hands both results back.  Built with the flags of
 // sdxp_persist.hip (Makefile), so that the helpers are compiled here as they are inside the kernel.
 #include "sdx_common.h"
@@ -6,6 +6,7 @@
 #include "sdxp_persist_sums.h"
 #include "sdxp_persist_adam.h"
 #include "sdxp_persist_tails.h"
+#include "sdxp_persist_phase_d.h"
 
 // Test entry (tests/test_gpu_wave_sums.py): one workgroup of NTH threads, in / ref / got are [N][NTH].  ref[i][t] = wave_sum of value i in t's
 // wave, on every lane; got[i][t] = what wave_sums<N> left in lane t for value i - written by the lanes with (t & 3) == (i & 3), the others'
@@ -500,5 +501,183 @@ extern "C" int sdxpk_stats_thread_check(const float* in, const int* adaptive, in
   if (n < 1) return -1;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_stats_thread_check), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PLds)) != hipSuccess) return -1;
   hipLaunchKernelGGL(k_stats_thread_check, dim3(n), dim3(NTH), sizeof(PLds), st, in, adaptive, out);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// Test entry (tests/test_gpu_persist_head_backward.py): the backward through the heads of phase D, one workgroup of NTH threads per case.  dmu [n][MB][32]
+// goes into S.dmu, dv [n][2][MB] into S.dv, x3 [n][3][MB][U2] into S.x3; hw [n][ACT + 2][U2] is the head matrix, of which lane (column c2n, row half c2c)
+// holds wc[j] = row min(13 c2c + j, ACT + 1), as the kernel's column view leaves it.  out [n][2][3 MB][NTH]: d2[net][s] per thread of [0] the block the
+// epoch kernel had before head_backward - the S.dv values read behind a lane condition, one branch with a read and a drained wait per value, the S.x3
+// operands read sample by sample between the chains - kept here verbatim as the reference, and of [1] head_backward on the same inputs.
+__global__ __launch_bounds__(NTH) void k_head_backward_check(const float* dmu, const float* dv, const float* x3, const float* hw, float* out) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  PLds& S = *reinterpret_cast<PLds*>(smem_raw);
+  const int tid = threadIdx.x;
+  const size_t c = blockIdx.x;
+  constexpr int A = ACT;
+  if (tid < MB * 32) S.dmu[tid / 32][tid % 32] = dmu[c * MB * 32 + tid];
+  if (tid < 2 * MB) S.dv[tid / MB][tid % MB] = dv[c * 2 * MB + tid];
+  for (int i = tid; i < 3 * MB * U2; i += NTH) (&S.x3[0][0][0])[i] = x3[c * 3 * MB * U2 + i];
+  const int c2c = (tid >> 5) & 1, c2n = 32 * (tid >> 6) + (tid & 31);
+  float wc[13];
+#pragma unroll
+  for (int j = 0; j < 13; ++j) wc[j] = hw[(c * (A + 2) + min(13 * c2c + j, A + 1)) * U2 + c2n];
+  __syncthreads();
+  float* o = out + c * 2 * 3 * MB * NTH;
+  {
+    float d2[3][MB];
+    {
+      const int k = c2n, jr = 13 * c2c;
+      float a0[MB], a1[MB], a2[MB];
+#pragma unroll
+      for (int s = 0; s < MB; ++s) a0[s] = 0.0f;
+#pragma unroll
+      for (int j = 0; j < 13; ++j)
+#pragma unroll
+        for (int s = 0; s < MB; ++s) a0[s] += S.dmu[s][jr + j] * wc[j];
+#pragma unroll
+      for (int s = 0; s < MB; ++s) {
+        a1[s] = c2c ? S.dv[0][s] * wc[A - 13] : 0.0f; a2[s] = c2c ? S.dv[1][s] * wc[A - 12] : 0.0f;
+        d2[0][s] = pair_sum(a0[s]) * elu_g(S.x3[0][s][k]);
+        d2[1][s] = pair_sum(a1[s]) * elu_g(S.x3[1][s][k]);
+        d2[2][s] = pair_sum(a2[s]) * elu_g(S.x3[2][s][k]);
+      }
+    }
+#pragma unroll
+    for (int net = 0; net < 3; ++net)
+#pragma unroll
+      for (int s = 0; s < MB; ++s) o[(net * MB + s) * NTH + tid] = d2[net][s];
+  }
+  {
+    float d2[3][MB];
+    head_backward(S, wc, c2c, c2n, d2);
+#pragma unroll
+    for (int net = 0; net < 3; ++net)
+#pragma unroll
+      for (int s = 0; s < MB; ++s) o[(3 * MB + net * MB + s) * NTH + tid] = d2[net][s];
+  }
+}
+extern "C" int sdxpk_head_backward_check(const float* dmu, const float* dv, const float* x3, const float* hw, int n, float* out, hipStream_t st) {
+  if (n < 1) return -1;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_head_backward_check), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PLds)) != hipSuccess) return -1;
+  hipLaunchKernelGGL(k_head_backward_check, dim3(n), dim3(NTH), sizeof(PLds), st, dmu, dv, x3, hw, out);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// Test entry (tests/test_gpu_persist_loss_phase.py): the loss phase of phase D, one workgroup of NTH threads per case.  in [n][LOSS_IN]: act [MB][32], mu [MB][32],
+// ls [32], sgm [32], val [2][MB], then per sample adv, old -log p, return, old value ([4][MB]), then e_clip, critic_coef, bounds_coef, clip_value.
+// out [n][2][LOSS_OUT]: gnlp [MB], dv [2][MB], dmu [MB][32], dls [32], stat [MB][3] (actor, critic, central value), z [MB][32] of [0] the block the epoch
+// kernel had before loss_request / loss_front / loss_back - lane (s, 31) forms both value-head losses behind the ratio, the dmu thread reads z, sigma, mu and
+// gnlp behind the first barrier and divides there - kept here verbatim as the reference, and of [1] the three helpers on the same inputs.
+constexpr int LOSS_IN = 2 * MB * 32 + 64 + 2 * MB + 4 * MB + 4, LOSS_OUT = MB + 2 * MB + MB * 32 + 32 + MB * 3 + MB * 32;
+__global__ __launch_bounds__(NTH) void k_loss_phase_check(const float* in, float* out) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  PLds& S = *reinterpret_cast<PLds*>(smem_raw);
+  const int tid = threadIdx.x;
+  const size_t c = blockIdx.x;
+  constexpr int A = ACT;
+  const float* ic = in + c * LOSS_IN;
+  const float* ps = ic + 2 * MB * 32 + 64 + 2 * MB;   // [4][MB]
+  const float* cf = ps + 4 * MB;
+  struct { float e_clip, critic_coef, bounds_coef; int clip_value; } D = {cf[0], cf[1], cf[2], cf[3] != 0.0f};
+  const float invM = 1.0f / (float)MB;
+  auto fill = [&]() {
+    if (tid < MB * 32) { S.act[tid / 32][tid % 32] = ic[tid]; S.mu[tid / 32][tid % 32] = ic[MB * 32 + tid]; }
+    if (tid < 32) { S.ls[tid] = ic[2 * MB * 32 + tid]; S.sgm[tid] = ic[2 * MB * 32 + 32 + tid]; }
+    if (tid < 2 * MB) S.val[tid / MB][tid % MB] = ic[2 * MB * 32 + 64 + tid];
+    const float nan = __builtin_nanf("");
+    if (tid < MB * 32) { S.dmu[tid / 32][tid % 32] = nan; S.z[tid / 32][tid % 32] = nan; }
+    if (tid < 32) S.dls[tid] = nan;
+    if (tid < MB) { S.gnlp[tid] = nan; S.dv[0][tid] = nan; S.dv[1][tid] = nan; S.stat[tid][STAT_ACTOR] = nan; S.stat[tid][STAT_CRITIC] = nan; S.stat[tid][STAT_CV] = nan; }
+    __syncthreads();
+  };
+  auto copy_out = [&](float* o) {
+    __syncthreads();
+    if (tid < MB) { o[tid] = S.gnlp[tid]; o[MB + tid] = S.dv[0][tid]; o[2 * MB + tid] = S.dv[1][tid]; }
+    if (tid < MB * 32) { o[3 * MB + tid] = S.dmu[tid / 32][tid % 32]; o[3 * MB + MB * 32 + 32 + MB * 3 + tid] = S.z[tid / 32][tid % 32]; }
+    if (tid < 32) o[3 * MB + MB * 32 + tid] = S.dls[tid];
+    if (tid < MB * 3) o[3 * MB + MB * 32 + 32 + tid] = S.stat[tid / 3][tid % 3 == 0 ? STAT_ACTOR : tid % 3 == 1 ? STAT_CRITIC : STAT_CV];
+    __syncthreads();
+  };
+  fill();
+  {
+    float pf_adv = 0.0f, pf_nlp = 0.0f, pf_ret = 0.0f, pf_val = 0.0f;
+    if (tid < MB * 32 && (tid % 32) == 31) { const int i = tid / 32; pf_adv = ps[i]; pf_nlp = ps[MB + i]; pf_ret = ps[2 * MB + i]; pf_val = ps[3 * MB + i]; }
+    SDX_OPAQUE(pf_adv); SDX_OPAQUE(pf_nlp); SDX_OPAQUE(pf_ret); SDX_OPAQUE(pf_val);
+    {
+      // (only what the gradients need: the KL, bounds and entropy terms of the statistics are formed in the dY1 shadow, on waves 5 and 7)
+      float r_nlp = 0.0f;
+      if (tid < MB * 32) {
+        const int s = tid / 32, a = tid % 32;
+        // z of (sample s, action a): formed by the thread that uses it here; S.z is only for the dmu / dlogstd lanes after the barrier below
+        const float zz = (a < A) ? (S.act[s][a] - S.mu[s][a]) / S.sgm[a] : 0.0f;
+        S.z[s][a] = zz;
+        if (a < A) r_nlp = 0.5f * zz * zz + S.ls[a];
+      }
+      r_nlp = half_sum(r_nlp);
+      if (tid < MB * 32 && (tid % 32) == 31) {
+        const int s = tid / 32;
+        const float nlp = r_nlp + 0.5f * 1.8378770664093453f * (float)A;
+        const float adv = pf_adv;
+        const float ratio = expf(pf_nlp - nlp);
+        const float L1 = -adv * ratio, L2 = -adv * clampf(ratio, 1.0f - D.e_clip, 1.0f + D.e_clip);
+        const bool inr = ratio >= 1.0f - D.e_clip && ratio <= 1.0f + D.e_clip;
+        S.gnlp[s] = (L1 > L2 || inr) ? adv * ratio : 0.0f;
+        const float R = pf_ret, vo = pf_val;
+        float closs[2];
+        for (int j = 0; j < 2; ++j) {
+          const float v = S.val[j][s];
+          const float vc = vo + clampf(v - vo, -D.e_clip, D.e_clip);
+          const float c1v = (v - R) * (v - R), c2v = (vc - R) * (vc - R);
+          float d;
+          if (D.clip_value) {
+            closs[j] = fmaxf(c1v, c2v);
+            const bool inv = fabsf(v - vo) <= D.e_clip;
+            d = (c1v > c2v || inv) ? 2.0f * (v - R) : 0.0f;
+          } else { closs[j] = c1v; d = 2.0f * (v - R); }
+          S.dv[j][s] = (j == 0 ? 0.5f * D.critic_coef : 1.0f) * d * invM;
+        }
+        S.stat[s][STAT_ACTOR] = fmaxf(L1, L2); S.stat[s][STAT_CRITIC] = closs[0]; S.stat[s][STAT_CV] = closs[1];
+      }
+    }
+    SDX_LDS_BARRIER();   // LDS traffic only: the column view's loads stay in flight (a __syncthreads() would wait for them)
+    if (tid < MB * 32) {
+      const int s = tid / 32, a = tid % 32;
+      float dmu = 0.0f;
+      if (a < A) {
+        const float sg = S.sgm[a], mu = S.mu[s][a];
+        const float hi = fmaxf(mu - 1.1f, 0.0f), lo = fminf(mu + 1.1f, 0.0f);
+        dmu = S.gnlp[s] * (-(S.z[s][a] / sg)) * invM + D.bounds_coef * (2.0f * hi + 2.0f * lo) * invM;
+      }
+      S.dmu[s][a] = dmu;
+    }
+    if (tid >= T_LS && tid < T_LS + 32) {
+      const int a = tid - T_LS;
+      float dls = 0.0f;
+      if (a < A) for (int s = 0; s < MB; ++s) dls += S.gnlp[s] * (1.0f - S.z[s][a] * S.z[s][a]) * invM;
+      S.dls[a] = dls;
+    }
+    SDX_LDS_BARRIER();   // LDS traffic only: the column view's loads stay in flight (a __syncthreads() would wait for them)
+  }
+  copy_out(out + c * 2 * LOSS_OUT);
+  fill();
+  {
+    float pf_adv = 0.0f, pf_nlp = 0.0f, pf_ret = 0.0f, pf_val = 0.0f;
+    if (tid < MB * 32 && (tid % 32) == 31) { const int i = tid / 32; pf_adv = ps[i]; pf_nlp = ps[MB + i]; }
+    if (tid >= T_VLOSS && tid < T_VLOSS + 2 * MB) { const int i = (tid - T_VLOSS) % MB; pf_ret = ps[2 * MB + i]; pf_val = ps[3 * MB + i]; }
+    SDX_OPAQUE(pf_adv); SDX_OPAQUE(pf_nlp); SDX_OPAQUE(pf_ret); SDX_OPAQUE(pf_val);
+    ZOps zo;
+    loss_request(S, tid, zo);
+    const LossCfg lc = {D.e_clip, D.critic_coef, D.bounds_coef, (bool)D.clip_value};
+    float q, bt;
+    loss_front(S, lc, tid, zo, pf_adv, pf_nlp, pf_ret, pf_val, invM, q, bt);
+    SDX_LDS_BARRIER();
+    loss_back(S, tid, q, bt, invM);
+    SDX_LDS_BARRIER();
+  }
+  copy_out(out + c * 2 * LOSS_OUT + LOSS_OUT);
+}
+extern "C" int sdxpk_loss_phase_check(const float* in, int n, float* out, hipStream_t st) {
+  if (n < 1) return -1;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_loss_phase_check), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PLds)) != hipSuccess) return -1;
+  hipLaunchKernelGGL(k_loss_phase_check, dim3(n), dim3(NTH), sizeof(PLds), st, in, out);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
