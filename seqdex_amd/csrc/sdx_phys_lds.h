@@ -7,7 +7,7 @@
 #define HP 24                 // padded row stride of the 23x23 matrices in LDS
 #define MAXC SDX_MAXC
 #define MAXP SDX_MAXP
-#define GL 4                  // gather lanes per brick
+#define GL 4                  // lane spacing of the bricks' bK owners (solve: pass_setup()); the gather's lanes per brick are chosen per solve (gtab)
 #define NBODY (NF + NL + 1)   // bricks, links, the static world
 #define BODY_W (NF + NL)      // body id of the static world inside the kernel (SDX_BODY_STATIC = 255 outside)
 // link frame origins / twists are rows NF.. of the body table: S.bp[NF + k], S.bv[NF + k], S.bw[NF + k]
@@ -130,7 +130,7 @@ struct PhysLds {
 //        |                       |                         | the contact normals                       |                                              |                   |
 // ent    | -                     | -                       | S_CKEY: identity of contact c             | S_CKEY read at entry; then the sorted CSR    | CSR entries       | -
 //
-// W: the link-inertia stages of the set-up (T, U, Lam, path dofs: solve()) run through all three P rows once the CSR fill list is dead.
+// W: the link-inertia stages of the set-up (T, U, Lam, path dofs: link_inertia() in sdx_phys_solve.h) run through all three P rows once the CSR fill list is dead.
 // The contact rows are dead between the solve and the next substep's collide: that is when waves 1.. set the bits of S_BMASK.
 #define S_T(S) (reinterpret_cast<float (*)[HP]>(&(S).P[0][0]))                       // L^-1 (mass matrix phase)
 #define S_PAIRS(S) (reinterpret_cast<uint32_t*>(&(S).P[2][0]))                       // candidate body pairs (collide)

@@ -307,10 +307,3 @@ __device__ __forceinline__ int pair_contacts(const PhysLds& S, const Box& A, con
 __device__ __forceinline__ f3 point_vel(const PhysLds& S, int id, f3 p) {   // id: row of the body table (static world = zeros)
   return ld3(S.bv[id]) + cross(ld3(S.bw[id]), p - ld3(S.bp[id]));
 }
-
-__device__ __forceinline__ float brick_w(const PhysLds& S, int i, f3 p, f3 d) {
-  const f3 rxd = cross(p - ld3(S.bp[i]), d);
-  const f3 l = qrot(qconj(ld4(S.bq[i])), rxd);
-  const float* ii = S.tii[S.btype[i]];   // mass / principal inertia of the type: inverse inertia = inverse mass x that
-  return S.bim[i] * (1.0f + l.x * l.x * ii[0] + l.y * l.y * ii[1] + l.z * l.z * ii[2]);
-}

@@ -1,59 +1,35 @@
-// sdx_phys_solve.h - private to sdx_physics.hip (included by it only, in its fixed order): robot row weights and the contact solver
+// sdx_phys_solve.h - private to sdx_physics.hip (included by it only, in its fixed order): the contact solver, solve(), as the list of its stages
 #pragma once
 
 // ---------------------------------------------------------------- E: solver
-// row weight of a robot-side contact: w = J Hinv J^T with J[j] = (a_j x (p - p_j)) . d over the <= 11 dofs on the link's path.  Hinv is
-// symmetric: every off-diagonal entry is loaded once.  ONE instance per kernel (the caller loops over the three row directions at run
-// time): three unrolled copies side by side cost the solver loop its registers (33 scratch reloads per iteration).
-__device__ __forceinline__ float robot_w(const PhysLds& S, int k, f3 p, f3 d) {
-  float Jp[11];
-  int idx[11];
-  uint32_t m = S.anc[k];
-#pragma unroll
-  for (int q = 0; q < 11; ++q) {
-    const int j = m ? __ffs(m) - 1 : ND;      // exhausted path: the padding dof (zero axis)
-    m &= m - 1;
-    idx[q] = j < ND ? j : 0;
-    Jp[q] = dot(cross(ld3(S.la[j + 1]), p - ld3(S.bp[NF + j + 1])), d);
-  }
-  float acc = 0.0f;
-#pragma unroll
-  for (int q = 0; q < 11; ++q) {
-    float t = 0.5f * S.A[idx[q]][idx[q]] * Jp[q];
-#pragma unroll
-    for (int r = q + 1; r < 11; ++r) t += S.A[idx[q]][idx[r]] * Jp[r];
-    acc += Jp[q] * t;
-  }
-  return 2.0f * acc;
-}
+// solve() at the end of this file calls the stages below in order, one phase-clock stamp (SSTAMP, tools/time_physics.py) between two of
+// them.  Every stage says what it reads and writes and which aliased row of PhysLds it owns while it runs; the rows' whole life is the
+// ownership table in sdx_phys_lds.h.  SSTAMP / SCOUNT / LMAX / ABL expand to uses of `dbg` and `abl_bits`: a stage that uses them takes
+// parameters of those names.
+constexpr int NB = NF + NL;   // bodies with a CSR list: bricks 0..71, links 72..95
+constexpr int LL = 8;         // gather lanes per link (tid = LL * link + sub): the lanes that also run the robot section
+constexpr int GU = 4;         // entries per lane and trip of the gather
+static_assert((NL * LL) % 64 == 0, "the link lanes (gather and robot section) are whole waves");
 
-template <int NT, bool WARM, bool DR = false>
-// Warm start (DESIGN.md section 3.E; oracle: solve()): wcount / wkey / wlam are THIS env's impulse cache in HBM.  A contact that existed
-// in the previous solve (same pair, direction and sample) starts from sc.warm_start x the impulses it ended with; iteration -1 of the
-// loop below spreads those impulses over the bodies with the gather machinery of a normal iteration.  WARM is a template parameter:
-// the default (cold) solver carries none of this code (it cost 2.6 % of the kernel as a run-time switch).
-__device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, float h, bool last_substep, long long* dbg,
-                                      int32_t* wcount, uint32_t* wkey, float* wlam, int abl_bits, const float* bfr = nullptr, const float* lfr = nullptr) {
-  constexpr int CPT = MAXC / NT;   // contact rows owned by one lane
-  constexpr int NB = NF + NL;      // bodies with a CSR list: bricks 0..71, links 72..95
-  static_assert(CPT * NT == MAXC, "NT must divide SDX_MAXC");
-  static_assert(CPT * 11 <= 64 && MAXC < 0x7ff, "11-bit cache positions of a lane's contacts in one 64-bit word");
-  const sdx_scene_desc& sc = C->sc;
-  const int nc = S.nc;
-  const float mu = sc.friction, relax = sc.jacobi_relax;
-  SSTAMP(16);
-  // ---- what stays in registers for the whole solve: body ids (rows of the body table), target normal velocity, accumulated
-  // impulses, un-split inverse masses of both sides
-  int ab[CPT];
-  float vtgt[CPT];
-  float muq[CPT];   // DR: friction of each contact = mean of its two bodies' coefficients (PhysX's default combine mode)
-  uint32_t ckey[CPT];
-  const float beta = sc.warm_start;
-  const float inv_age = sc.warm_age > 0.0f ? 1.0f / sc.warm_age : 1e30f;
-  // depth gate expressed on the velocity target the lane keeps anyway: sep < -WARM_DEPTH * offset <=> vtgt > baumgarte * depth / h
-  const float wdeep = sc.baumgarte * (WARM_DEPTH * sc.contact_offset) / h;
-  int nold = WARM ? *wcount : 0;   // block-uniform
-  if (nold > MAXC) nold = MAXC;
+// What a lane keeps in registers for the whole solve about its CPT = MAXC / NT contact rows c = tid + q * NT
+template <int CPT>
+struct SolveRows {
+  int ab[CPT];          // body a | body b << 8 (rows of the body table); from loop_registers() on their active-count slots in bits 16..31
+  float vtgt[CPT];      // target normal velocity
+  float muq[CPT];       // DR: friction of each contact = mean of its two bodies' coefficients (PhysX's default combine mode)
+  uint32_t ckey[CPT];   // WARM: identity of the contact (pair, direction, sample)
+  float lam[CPT][3];    // accumulated impulses (normal, two tangents); born in row_weights()
+  float wA[CPT][3], wB[CPT][3];   // un-split inverse effective masses of both sides; born in row_weights()
+};
+
+// ---- set-up, stamps 16 -> 23: contact rows -> lane registers
+// Reads the narrowphase's staging rows (separation in P[0], body ids in P[1], keys in S_CKEY = ent); writes R.ab, R.vtgt, R.ckey and, WARM,
+// the previous solve's keys (wkey, HBM) into P[2], whose pair list is dead.  The staging rows are free after the barrier of csr_clear().
+template <int NT, bool WARM, int CPT>
+__device__ __forceinline__ void load_rows(const sdx_scene_desc& sc, PhysLds& S, int tid, int nc, float h, int nold, const uint32_t* wkey, SolveRows<CPT>& R) {
+  int (&ab)[CPT] = R.ab;
+  float (&vtgt)[CPT] = R.vtgt;
+  uint32_t (&ckey)[CPT] = R.ckey;
 #pragma unroll
   for (int q = 0; q < CPT; ++q) {
     const int c = tid + q * NT;
@@ -69,17 +45,27 @@ __device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, fl
   }
   // the previous solve's keys into the free third impulse row (the pair list that lived there is dead)
   if (WARM) for (int i = tid; i < nold; i += NT) S.P[2][i] = __int_as_float((int)wkey[i]);
-  SSTAMP(23);
-  // ---- CSR of contact sides per body (bricks AND robot links), ascending contact index inside a body
+}
+
+// ---- CSR of contact sides per body (bricks AND robot links), ascending contact index inside a body: csr_clear() .. csr_rank()
+// stamps 23 -> 24, first part: zero the counts (and, in the last substep, the links' net contact impulses cf)
+template <int NT>
+__device__ __forceinline__ void csr_clear(PhysLds& S, int tid, bool last_substep) {
   for (int i = tid; i < NB; i += NT) { S.ecount[i] = 0; S.efill[i] = 0; }
   if (last_substep) for (int i = tid; i < NL * 3; i += NT) (&S.cf[0][0])[i] = 0.0f;
   __syncthreads();   // also: every lane has read its (separation, ids, key) out of the staging rows, which the fill list reuses below
-  // warm-start match: the old keys ascend in their pair part (bits 6..27: body pair rank, box pair), so the pair's first old contact is a lower bound away; the
-  // <= 4 contacts of a pair are then compared exactly.  wmatch packs the matched positions (11 bits each, 0x7ff = none); the
-  // impulses themselves are fetched where the lam registers are born.  The new keys replace the old ones in HBM right away (the
-  // old ones are in LDS now; the old impulses stay untouched until the end of this solve).
-  uint64_t wmatch = ~0ull;
-  uint32_t wage = 0;   // 8 bits per contact: consecutive solves it has existed (0: new in this solve)
+}
+
+// ---- stamps 23 -> 24, between csr_clear() and csr_count(): warm-start match
+// The old keys ascend in their pair part (bits 6..27: body pair rank, box pair), so the pair's first old contact is a lower bound away; the
+// <= 4 contacts of a pair are then compared exactly.  wmatch packs the matched positions (11 bits each, 0x7ff = none); the
+// impulses themselves are fetched where the lam registers are born.  The new keys replace the old ones in HBM right away (the
+// old ones are in LDS now; the old impulses stay untouched until the end of this solve).
+// Reads the old keys in P[2] (theirs until csr_offsets_and_packing() clears S_LANEMAP there) and ckey; writes wkey (HBM).  Yields wmatch, wage.
+template <int NT, bool WARM, int CPT>
+__device__ __forceinline__ void warm_match(PhysLds& S, int tid, int nc, int nold, const uint32_t (&ckey)[CPT], uint32_t* wkey, uint64_t& wmatch, uint32_t& wage) {
+  wmatch = ~0ull;
+  wage = 0;   // 8 bits per contact: consecutive solves it has existed (0: new in this solve)
   // lower bound of every slot's pair part among the old keys: a branch-free bisection whose trip count depends on nold only, so the lane's
   // CPT searches advance together - one LDS round trip per halving for all of them (round 6; one search after the other was 10 dependent
   // round trips per slot)
@@ -123,6 +109,11 @@ __device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, fl
       wkey[c] = key | ((age < 15u ? age : 15u) << 28);   // bits 28..31: the number of consecutive solves this contact has existed before (saturating at 15: the ramp is over after warm_age <= 16 solves)
     }
   }
+}
+
+// ---- stamps 23 -> 24, last part: sides per body (integer atomics on ecount)
+template <int NT, int CPT>
+__device__ __forceinline__ void csr_count(PhysLds& S, int tid, int nc, const int (&ab)[CPT]) {
 #pragma unroll
   for (int q = 0; q < CPT; ++q)
     if (tid + q * NT < nc) {
@@ -131,7 +122,13 @@ __device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, fl
       if (b != BODY_W) atomicAdd(&S.ecount[b], 1);
     }
   __syncthreads();
-  SSTAMP(24);
+}
+
+// ---- stamps 24 -> 25: offsets (eoff) on wave 0 beside the balanced-gather packing (gtab) on wave 1
+// Reads ecount; writes eoff, gtab and zeroes S_LANEMAP, which takes P[2] over from the old warm-start keys (dead since the barrier of
+// csr_count()).
+template <int NT>
+__device__ __forceinline__ void csr_offsets_and_packing(PhysLds& S, int tid) {
   if (tid < 64) {   // exclusive prefix over the 96 bodies on wave 0: two per lane, shuffle scan
     const int i0 = 2 * tid, i1 = 2 * tid + 1;
     const int c0 = i0 < NB ? S.ecount[i0] : 0, c1 = i1 < NB ? S.ecount[i1] : 0;
@@ -185,7 +182,12 @@ __device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, fl
   }
   S_LANEMAP(S)[tid] = 0;   // (wave 0 and 1 after their work: the row of the old warm-start keys is free since the barrier above)
   __syncthreads();
-  SSTAMP(25);
+}
+
+// ---- stamps 25 -> 26: lane map of the chosen packing and the unsorted fill
+// Owns S_LANEMAP (P[2]), S_ENT2 (P[0]) and S_EBODY2 (P[1]): a side of body `a` goes to entry eoff[a] + (its order of arrival).
+template <int NT, int CPT>
+__device__ __forceinline__ void csr_fill(PhysLds& S, int tid, int nc, const int (&ab)[CPT]) {
   if (tid < NF) {   // lane -> (brick, lane of the brick, last lane?) of the chosen packing
     const uint32_t w = S.gtab[tid];
     const int start = w & 511, L = w >> 9;
@@ -201,53 +203,59 @@ __device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, fl
     }
   }
   __syncthreads();
-  SSTAMP(26);
-  const int rbeg = S.eoff[NF], nrob = S.eoff[NB] - rbeg;   // the robot's sides: entries [rbeg, rbeg + nrob), grouped by link
-  const bool has_robot = nrob > 0;                          // block-uniform
-  // this lane's slice of a brick's list (balanced gather): brick | lane of the brick << 7 | last lane << 11 | first entry << 12 | entries << 24;
-  // 0 = none.  (Read here: the row that holds the lane map is rewritten by the link-inertia stages below.)
+}
+
+// ---- stamps 26 -> 27, first part: this lane's slice of a brick's list (balanced gather):
+// brick | lane of the brick << 7 | last lane << 11 | first entry << 12 | entries << 24; 0 = none.
+// Reads S_LANEMAP, gtab, ecount, eoff.  (Read here: link_inertia() rewrites the row that holds the lane map.)
+__device__ __forceinline__ uint32_t gather_slice(PhysLds& S, int tid) {
   uint32_t cdesc = 0;
-  {
-    const uint32_t lm = S_LANEMAP(S)[tid];
-    if (lm & 0x8000u) {
-      const int b = lm & 0x7f, j = (lm >> 7) & 15;
-      const int L = (int)(S.gtab[b] >> 9), n = S.ecount[b];
-      const int c = (n + L - 1) / L;                      // entries per lane of this brick
-      int cnt = n - j * c;
-      cnt = cnt < 0 ? 0 : (cnt > c ? c : cnt);
-      cdesc = (lm & 0xfffu) | ((uint32_t)(S.eoff[b] + j * c) << 12) | ((uint32_t)cnt << 24);
-    }
+  const uint32_t lm = S_LANEMAP(S)[tid];
+  if (lm & 0x8000u) {
+    const int b = lm & 0x7f, j = (lm >> 7) & 15;
+    const int L = (int)(S.gtab[b] >> 9), n = S.ecount[b];
+    const int c = (n + L - 1) / L;                      // entries per lane of this brick
+    int cnt = n - j * c;
+    cnt = cnt < 0 ? 0 : (cnt > c ? c : cnt);
+    cdesc = (lm & 0xfffu) | ((uint32_t)(S.eoff[b] + j * c) << 12) | ((uint32_t)cnt << 24);
   }
-  if (tid == 0) S.nrob = nrob;
-  SCOUNT(52, nc); SCOUNT(53, S.eoff[NB]); SCOUNT(54, nrob);
-  // rank pass: entry -> position = number of entries of the same body with a smaller contact index (a contact touches a body at
-  // most once, so indices are distinct) => every body's list is in ascending contact order, deterministically
-  {
-    const int total = S.eoff[NB];
-    for (int i = tid; i < total; i += NT) {
-      const int body = S_EBODY2(S)[i];
-      const int o = S.eoff[body], n = S.eoff[body + 1] - o;
-      const unsigned short v = S_ENT2(S)[i];
-      const int key = v & 0x7fff;
-      int rank = 0;
-      if (ABL(64)) rank = i - o;
-      else
+  return cdesc;
+}
+
+// ---- stamps 26 -> 27: rank pass: entry -> position = number of entries of the same body with a smaller contact index (a contact touches
+// a body at most once, so indices are distinct) => every body's list is in ascending contact order, deterministically
+// Reads the fill (S_ENT2, S_EBODY2); writes ent, which stops being S_CKEY here.  The fill rows P[0], P[1] are dead after its barrier.
+template <int NT>
+__device__ __forceinline__ void csr_rank(PhysLds& S, int tid, int abl_bits) {
+  const int total = S.eoff[NB];
+  for (int i = tid; i < total; i += NT) {
+    const int body = S_EBODY2(S)[i];
+    const int o = S.eoff[body], n = S.eoff[body + 1] - o;
+    const unsigned short v = S_ENT2(S)[i];
+    const int key = v & 0x7fff;
+    int rank = 0;
+    if (ABL(64)) rank = i - o;
+    else
 #pragma unroll 4
-      for (int j = 0; j < n; ++j) rank += (S_ENT2(S)[o + j] & 0x7fff) < key;
-      S.ent[o + rank] = v;
-    }
+    for (int j = 0; j < n; ++j) rank += (S_ENT2(S)[o + j] & 0x7fff) < key;
+    S.ent[o + rank] = v;
   }
   __syncthreads();   // rank pass complete (ent final); the fill list in the P rows is dead from here on
-  SSTAMP(27);
-  SSTAMP(28);
-  // ---- robot: operational-space inverse inertia of every link that carries a contact, Lam_k = J_k Hinv J_k^T (6 x 6, symmetric, about
-  // the link origin o_k; J_k = the link's geometric Jacobian over the <= 11 dofs of its path), built by the whole block in three stages
-  // through the (free) impulse rows.  A robot-side row weight is then g^T Lam_k g with g = (d, (p - o_k) x d): no per-contact walk over
-  // the path, no exchange between the lanes that own a contact and the lanes that own a link.
-  uint32_t touched = 0;   // links that carry contacts in this substep (block-uniform)
+}
+
+// ---- stamps 28 -> 29: link inertia
+// Robot: operational-space inverse inertia of every link that carries a contact, Lam_k = J_k Hinv J_k^T (6 x 6, symmetric, about
+// the link origin o_k; J_k = the link's geometric Jacobian over the <= 11 dofs of its path), built by the whole block in three stages
+// through the (free) impulse rows.  A robot-side row weight is then g^T Lam_k g with g = (d, (p - o_k) x d): no per-contact walk over
+// the path, no exchange between the lanes that own a contact and the lanes that own a link.
+// Owns W = all three P rows; Lam (W_L) stays there for row_weights().  Yields `touched`: the links that carry contacts in this substep
+// (block-uniform).
+constexpr int W_T = 0, W_U = NL * 66, W_L = 2 * NL * 66, W_J = 2 * NL * 66 + NL * 21;   // T = J_k [6][11], U = J_k Hinv_sub [6][11], Lam [21], path dofs [11]
+static_assert(W_J + NL * 11 <= 3 * MAXC, "the three stages fit the impulse rows");
+template <int NT>
+__device__ __forceinline__ uint32_t link_inertia(PhysLds& S, int tid, bool has_robot) {
+  uint32_t touched = 0;
   float* const W = &S.P[0][0];
-  constexpr int W_T = 0, W_U = NL * 66, W_L = 2 * NL * 66, W_J = 2 * NL * 66 + NL * 21;   // T = J_k [6][11], U = J_k Hinv_sub [6][11], Lam [21], path dofs [11]
-  static_assert(W_J + NL * 11 <= 3 * MAXC, "the three stages fit the impulse rows");
   if (has_robot) {
     for (int k = 0; k < NL; ++k) if (S.eoff[NF + k + 1] > S.eoff[NF + k]) touched |= 1u << k;
     // stage 1: lane = (link k, dof j on its path): column of J_k and the dof's slot
@@ -314,10 +322,20 @@ __device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, fl
     }
     __syncthreads();
   }
-  SSTAMP(29);
-  // (the per-lane impulse / weight registers are born only here)
-  float lam[CPT][3], wA[CPT][3], wB[CPT][3];
-  // ---- un-split inverse effective masses of both sides (owner lanes); zero accumulated impulses
+  return touched;
+}
+
+// ---- stamps 29 -> 30: row weights and initial impulses
+// Writes R.wA, R.wB, R.lam (the per-lane impulse / weight registers are born only here): both brick sides together, robot sides from Lam
+// (W_L in the P rows, read-only here), then the warm-start gate on the body table's (v, w) and the cached impulses wlam (HBM): a matched contact
+// starts from beta x its cached impulse, ramped over its age (inv_age), unless it is deeper than wdeep or moving.
+template <int NT, bool WARM, int CPT>
+__device__ __forceinline__ void row_weights(const PhysLds& S, int tid, int nc, bool has_robot, uint64_t wmatch, uint32_t wage, const float* wlam,
+                                            float beta, float inv_age, float wdeep, SolveRows<CPT>& R, int abl_bits) {
+  const int (&ab)[CPT] = R.ab;
+  const float (&vtgt)[CPT] = R.vtgt;
+  float (&lam)[CPT][3] = R.lam, (&wA)[CPT][3] = R.wA, (&wB)[CPT][3] = R.wB;
+  const float* const W = &S.P[0][0];
 #pragma unroll
   for (int q = 0; q < CPT; ++q) {
     const int c = tid + q * NT;
@@ -329,9 +347,10 @@ __device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, fl
     tangents(n, &t1, &t2);
     const f3 dir[3] = {n, t1, t2};
     {
-      // brick_w() x 6 compiled to ~7 dependent LDS round trips per call (position, orientation, type -> inertia ratios, inverse mass, one
-      // after the other: 40 in a row per contact).  Here both sides' rows are loaded together, then the type rows, then the six weights are
-      // plain arithmetic - the same expressions as brick_w.  A side that is not a brick reads brick 0 and is discarded.
+      // One brick side's weight is bim * (1 + l . (tii * l)) with l = R^T ((p - x) x d) (oracle: brick_w()).  As a function called six times
+      // it compiled to ~7 dependent LDS round trips per call (position, orientation, type -> inertia ratios, inverse mass, one after the
+      // other: 40 in a row per contact).  Here both sides' rows are loaded together, then the type rows, then the six weights are plain
+      // arithmetic.  A side that is not a brick reads brick 0 and is discarded.
       const bool ba = on && a < NF, bb = on && b < NF;
       const int ia = ba ? a : 0, ib = bb ? b : 0;
       f3 xa = ld3(S.bp[ia]), xb = ld3(S.bp[ib]);
@@ -395,23 +414,21 @@ __device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, fl
       }
     }
   }
-  SSTAMP(30);
-  // gather lanes.  Links: LL = 8 per link (tid = 8 * link + sub: the same lanes run the robot section; only when the hand touches something),
-  // lane sub sums entries sub, sub + 8, ... of its link's list.  Bricks: the slice of cdesc (balanced gather, above) - kept in gbeg.
-  // (The old fixed map - GL = 4 lanes per brick after the link lanes - still decides which lane computes a brick's bK below.)
-  constexpr int LL = 8;
-#ifndef SDX_GU
-#define SDX_GU 4
-#endif
-  constexpr int GU = SDX_GU;   // entries per lane and trip of the gather
-  static_assert(NF * GL + NL * LL <= NT, "gather lanes");
-  const bool llane = tid < NL * LL;
-  const int gbody = llane ? NF + tid / LL : (tid - NL * LL) / GL, gsub = llane ? tid % LL : (tid - NL * LL) % GL;
-  const bool glane = llane || gbody < NF;
-  int gbeg = 0, gend = 0;
-  if (glane) {
-    gbeg = S.eoff[gbody] + gsub; gend = S.eoff[gbody + 1];
-    if (gbody < NF && gsub == 0) {
+}
+
+// ---- stamps 30 -> 17: pass set-up
+// Yields the gather lanes' coordinates (gbeg, gend) and the robot section's path dofs tjp; writes bK, acount, rsync and turns the body
+// table to (u, w).  Gather lanes.  Links: LL = 8 per link (only when the hand touches something), lane sub sums entries sub, sub + 8, ...
+// of its link's list [gbeg, gend).  Every other lane: the slice of cdesc (balanced gather) - the descriptor itself in gbeg.
+template <int NT>
+__device__ __forceinline__ void pass_setup(PhysLds& S, int tid, bool has_robot, int nrob, uint32_t cdesc, int& gbeg, int& gend, int& tjp) {
+  static_assert(NL * LL + NF * GL <= NT, "one lane per brick for bK behind the link lanes");
+  if (has_robot && tid < NL * LL) { gbeg = S.eoff[NF + tid / LL] + tid % LL; gend = S.eoff[NF + tid / LL + 1]; }
+  else { gbeg = (int)cdesc; gend = (int)(((cdesc >> 12) & 0xfffu) + (cdesc >> 24)); }
+  // world inverse inertia of the substep: lane NL * LL + GL * b computes brick b's bK
+  {
+    const int gbody = (tid - NL * LL) / GL;
+    if (tid >= NL * LL && (tid - NL * LL) % GL == 0 && gbody < NF) {
       const f4 q = ld4(S.bq[gbody]);
       const f3 ex = qrot(q, F3(1, 0, 0)), ey = qrot(q, F3(0, 1, 0)), ez = qrot(q, F3(0, 0, 1));   // columns of R
       const float* ii = S.tii[S.btype[gbody]];
@@ -424,9 +441,8 @@ __device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, fl
       S.bK[gbody][5] = i0 * ex.y * ex.z + i1 * ey.y * ey.z + i2 * ez.y * ez.z;
     }
   }
-  if (!(has_robot && llane)) { gbeg = (int)cdesc; gend = (int)(((cdesc >> 12) & 0xfffu) + (cdesc >> 24)); }
   // robot section lanes (8 per link): the rs-th and (rs + 8)-th dof on the path base -> link rj (ND = none)
-  int tjp = ND | (ND << 8);
+  tjp = ND | (ND << 8);
   {
     const int rj = tid / 8, rs = tid % 8;
     if (rj < NL) {
@@ -448,15 +464,21 @@ __device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, fl
     S.acount[1][i] = 0;
   }
   if (tid == 0) S.rsync = 0;
-  __syncthreads();   // every lane has read what it needs of v / w in the body table (warm-start gate above)
+  __syncthreads();   // every lane has read what it needs of v / w in the body table (warm-start gate of row_weights())
   // body table -> (u, w): u = v - w x x.  Link rows too (their twists are those of the drive phase until the robot section rewrites them)
   for (int i = tid; i < NBODY; i += NT) st3(S.bv[i], ld3(S.bv[i]) - cross(ld3(S.bw[i]), ld3(S.bp[i])));
-  int qpar = 0;   // robot section: joint velocities are read from S.qd (0) / S.qdb (1) and written to the other
   __syncthreads();
-  SSTAMP(17);
+}
 
+// ---- after stamp 17: what the loop keeps in registers
+// The sides' active-count slots into bits 16..31 of R.ab; DR: R.muq from the per-body coefficients bfr / lfr (HBM).
+template <bool DR, int CPT>
+__device__ __forceinline__ void loop_registers(const sdx_scene_desc& sc, const float* bfr, const float* lfr, SolveRows<CPT>& R, int& gbeg, int& gend, int& tjp) {
+  int (&ab)[CPT] = R.ab;
+  float (&vtgt)[CPT] = R.vtgt, (&muq)[CPT] = R.muq;
+  float (&lam)[CPT][3] = R.lam, (&wA)[CPT][3] = R.wA, (&wB)[CPT][3] = R.wB;
 #pragma unroll
-  for (int q = 0; q < CPT; ++q) {   // the sides' active-count slots into bits 16..31 of ab: a brick's own, NF = the whole robot, NF + 1 = the static world
+  for (int q = 0; q < CPT; ++q) {   // a brick's own slot, NF = the whole robot, NF + 1 = the static world
     const int a = ab[q] & 0xff, b = (ab[q] >> 8) & 0xff;
     const int sa = a < NF ? a : (a != BODY_W ? NF : NF + 1), sb = b < NF ? b : (b != BODY_W ? NF : NF + 1);
     ab[q] = (ab[q] & 0xffff) | (sa << 16) | (sb << 24);
@@ -475,240 +497,260 @@ __device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, fl
     for (int r = 0; r < 3; ++r) { SDX_OPAQUE(lam[q][r]); SDX_OPAQUE(wA[q][r]); SDX_OPAQUE(wB[q][r]); }
   }
   SDX_OPAQUE(gbeg); SDX_OPAQUE(gend); SDX_OPAQUE(tjp);
-  const int it0 = (WARM && nold > 0) ? -1 : 0;
-  for (int it = it0; it < (ABL(4) ? 1 : sc.solver_iters); ++it) {   // it = -1: only the gather of the warm-start impulses
-#ifdef SDX_PHASE_CLOCK
-    if (it == 1) dbg = nullptr;
-#endif
-    SSTAMP(18);
-    const int cur = it & 1, nxt = cur ^ 1;
-    LCLOCK(lc_ac0);
-    // ---- [AC] lane = contact: relative velocity from the current body table, active flag -> counted for the NEXT iteration (integer
-    // atomics), Jacobi update with the counts of the previous iteration; impulse P (on body A) to LDS, zero when inactive
+}
+
+// isa_check: loop stage begin (tools/isa_check.py counts the lines from here to the matching end with the lines of the loop itself)
+// ---- [AC] lane = contact: relative velocity from the current body table, active flag -> counted for the NEXT iteration (integer
+// atomics), Jacobi update with the counts of the previous iteration; impulse P (on body A) to LDS, zero when inactive
+// Reads the body table, cp / cn, acount[cur]; writes R.lam, acount[nxt] and the P rows, from here on the impulses of this pass.
+template <int NT, bool WARM, bool DR, int CPT>
+__device__ __forceinline__ void contact_update(PhysLds& S, int tid, int nc, int it, float mu, float relax, SolveRows<CPT>& R, long long* dbg, int abl_bits) {
+  const int (&ab)[CPT] = R.ab;
+  const float (&vtgt)[CPT] = R.vtgt, (&muq)[CPT] = R.muq;
+  float (&lam)[CPT][3] = R.lam;
+  const float (&wA)[CPT][3] = R.wA, (&wB)[CPT][3] = R.wB;
+  const int cur = it & 1, nxt = cur ^ 1;
+  LCLOCK(lc_ac0);
 #pragma unroll
-    for (int q = 0; q < CPT; ++q) {
-      int abq = ab[q], ct = tid;
-      SDX_OPAQUE(abq); SDX_OPAQUE(ct);
-      const int c = ct + q * NT;
-      f3 P = F3(0, 0, 0);
-      if (c < nc && !ABL(2)) {
-        const f3 n = F3(S.cn[0][c], S.cn[1][c], S.cn[2][c]);
-        f3 t1, t2;
-        tangents(n, &t1, &t2);
-        if (WARM && it < 0) {                      // warm start: the whole initial impulse
-          if (lam[q][0] > 0.0f) P = n * lam[q][0] + t1 * lam[q][1] + t2 * lam[q][2];
-        } else {
-          // (bits 16..31 of ab: the two sides' slots in the active-count sets, fixed for the solve - decoding them per iteration cost 28
-          // VALU instructions per contact; the counts of the previous iteration are loaded with the geometry, not after the velocity test:
-          // one LDS round trip less on the path of every active contact)
-          const int a = abq & 0xff, b = (abq >> 8) & 0xff, sa = (abq >> 16) & 0xff, sb = (abq >> 24) & 0xff;
-          const f3 p = F3(S.cp[0][c], S.cp[1][c], S.cp[2][c]);
-          // (the four body rows in flight together: the plain expression loads side A, waits, then side B into the same registers)
-          f3 ua = ld3v(S.bv[a]), wa = ld3v(S.bw[a]), ub = ld3v(S.bv[b]), wb = ld3v(S.bw[b]);
-          SDX_PIN3x4(ua, wa, ub, wb);
-          const f3 vr = (ua + cross(wa, p)) - (ub + cross(wb, p));
-          const float vn = dot(vr, n);
-          const float lam0 = lam[q][0], lam1 = lam[q][1], lam2 = lam[q][2];
-          if (lam0 > 0.0f || vn < vtgt[q]) {
-            if (a != BODY_W) atomicAdd(&S.acount[nxt][sa], 1);
-            if (b != BODY_W) atomicAdd(&S.acount[nxt][sb], 1);
-            const int ca = S.acount[cur][sa], cb = S.acount[cur][sb];
-            const float na = a != BODY_W ? (float)(ca > 1 ? ca : 1) : 0.0f;
-            const float nb = b != BODY_W ? (float)(cb > 1 ? cb : 1) : 0.0f;
-            const float w0 = na * wA[q][0] + nb * wB[q][0];
-            const float w1 = na * wA[q][1] + nb * wB[q][1];
-            const float w2 = na * wA[q][2] + nb * wB[q][2];
-            const float ln = fmaxf(0.0f, lam0 - relax * (vn - vtgt[q]) * SDX_RCP(w0));
-            const float lim = (DR ? muq[q] : mu) * ln;
-            float l1 = lam1 - relax * dot(vr, t1) * SDX_RCP(w1);
-            l1 = fminf(lim, fmaxf(-lim, l1));
-            float l2 = lam2 - relax * dot(vr, t2) * SDX_RCP(w2);
-            l2 = fminf(lim, fmaxf(-lim, l2));
-            lam[q][0] = ln; lam[q][1] = l1; lam[q][2] = l2;
-            P = n * (ln - lam0) + t1 * (l1 - lam1) + t2 * (l2 - lam2);
-          }
-        }
-        S.P[0][c] = P.x; S.P[1][c] = P.y; S.P[2][c] = P.z;
-      }
-    }
-#ifdef SDX_LANE_CLOCK
-    { LCLOCK(lc_ac1); LMAX(55, lc_ac1 - lc_ac0); if (tid == NT - 1) LMAX(56, lc_ac1 - lc_ac0); }
-#endif
-    __syncthreads();
-    SSTAMP(20);
-    LCLOCK(lc_d0);
-    // ---- [D] gather (LL / GL lanes per body): F = sum(+-P), M = sum(+-(p - x) x P) about the body's reference point x; each lane sums its
-    // slice in ascending contact order, the partial sums are combined in a fixed order (deterministic); inactive contacts carry P = 0.
-    // Bricks: w += Iw^-1 M, u += F / m - dw x x.  Links: the wrench (F, M about the link origin) is projected on the dofs of the link's
-    // path right away (8 lanes, <= 2 dofs each) -> Qc for the robot section below.
-    int td = tid;
-    SDX_OPAQUE(td);   // lane coordinates re-derived per iteration instead of living in registers across the loop
-    const bool d_link = has_robot && td < NL * LL;   // waves 0..2 of an env whose hand touches something: link lanes; every other lane is a brick lane
-    const uint32_t cd = (uint32_t)gbeg;              // (brick lanes: the slice descriptor)
-    const int d_body = d_link ? NF + td / LL : (int)(cd & 0x7fu), d_sub = d_link ? td % LL : 0;
-    const int gstride = d_link ? LL : 1;
-    const int ibeg = d_link ? gbeg : (int)((cd >> 12) & 0xfffu);
-    {
-      float acc[6] = {0, 0, 0, 0, 0, 0};
-      const f3 x = ld3(S.bp[d_body]);
-      // four entries per trip (the index loads, then the payloads, in flight together); not unrolled further: the decoded
-      // addresses of a longer window would be kept in registers across the whole iteration loop
-      // two entries at a time: index loads pinned in front of the 12 payload loads, those in front of the arithmetic (four dependent LDS
-      // round trips per trip of four entries instead of eight; all four at once - SDX_D_BATCH - spills inside the loop)
-#pragma unroll 1
-      for (int i = ibeg; i < (ABL(1) ? ibeg : gend); i += GU * gstride) {
-#pragma unroll
-        for (int h2 = 0; h2 < GU; h2 += 2) {
-          const int i0 = i + h2 * gstride, i1 = i0 + gstride;
-          int e0 = S.ent[i0 < gend ? i0 : i], e1 = S.ent[i1 < gend ? i1 : i];
-          SDX_PIN1(e0); SDX_PIN1(e1);
-          const int c0 = e0 & 0x7fff, c1 = e1 & 0x7fff;
-          f3 P0 = F3(S.P[0][c0], S.P[1][c0], S.P[2][c0]), C0 = F3(S.cp[0][c0], S.cp[1][c0], S.cp[2][c0]);
-          f3 P1 = F3(S.P[0][c1], S.P[1][c1], S.P[2][c1]), C1 = F3(S.cp[0][c1], S.cp[1][c1], S.cp[2][c1]);
-          SDX_PIN3x4(P0, C0, P1, C1);
-          {
-            const float sg = i0 < gend ? ((e0 & 0x8000) ? -1.0f : 1.0f) : 0.0f;
-            const f3 P = P0 * sg;
-            const f3 M = cross(C0 - x, P);
-            acc[0] += P.x; acc[1] += P.y; acc[2] += P.z; acc[3] += M.x; acc[4] += M.y; acc[5] += M.z;
-          }
-          {
-            const float sg = i1 < gend ? ((e1 & 0x8000) ? -1.0f : 1.0f) : 0.0f;
-            const f3 P = P1 * sg;
-            const f3 M = cross(C1 - x, P);
-            acc[0] += P.x; acc[1] += P.y; acc[2] += P.z; acc[3] += M.x; acc[4] += M.y; acc[5] += M.z;
-          }
-        }
-      }
-#ifdef SDX_LANE_CLOCK
-      { LCLOCK(lc_d1); LMAX(57, lc_d1 - lc_d0); LMAX(58, (gend - ibeg + gstride - 1) / gstride); }
-#endif
-      // the brick update's operands (inverse inertia, inverse mass, u, w: 13 numbers) are requested BEFORE the lane reductions and pinned
-      // after them: their LDS round trip runs under the DPP adds instead of after them (every lane loads: the branch comes later)
-      const int tb = d_link ? 0 : d_body;
-      float K_[6], imb_ = S.bim[tb];
-#pragma unroll
-      for (int r = 0; r < 6; ++r) K_[r] = S.bK[tb][r];
-      f3 u_ = ld3(S.bv[tb]), w_ = ld3(S.bw[tb]);
-      if (d_link) {
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-          acc[r] = sum4(acc[r]);
-          acc[r] += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc[r]), 0x141, 0xF, 0xF, true));
-        }
+  for (int q = 0; q < CPT; ++q) {
+    int abq = ab[q], ct = tid;
+    SDX_OPAQUE(abq); SDX_OPAQUE(ct);
+    const int c = ct + q * NT;
+    f3 P = F3(0, 0, 0);
+    if (c < nc && !ABL(2)) {
+      const f3 n = F3(S.cn[0][c], S.cn[1][c], S.cn[2][c]);
+      f3 t1, t2;
+      tangents(n, &t1, &t2);
+      if (WARM && it < 0) {                      // warm start: the whole initial impulse
+        if (lam[q][0] > 0.0f) P = n * lam[q][0] + t1 * lam[q][1] + t2 * lam[q][2];
       } else {
-        // the slices of a brick sit on consecutive lanes of one 16-lane row: inclusive segmented scan (row_shr 1, 2, 4, 8; lane `so` of the
-        // brick adds the value `sh` lanes back while that lane still belongs to the brick), after which the brick's LAST lane holds the
-        // sums - slices in ascending contact order, combined in the scan's fixed tree (deterministic)
-        const int so = (int)((cd >> 7) & 15u);
-#define SDX_SEG_STEP(sh)                                                                                                  \
-        {                                                                                                                 \
-          const bool take = so >= (sh);                                                                                   \
-          _Pragma("unroll") for (int r = 0; r < 6; ++r) {                                                                 \
-            const float t = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc[r]), 0x110 + (sh), 0xF, 0xF, true)); \
-            acc[r] += take ? t : 0.0f;                                                                                    \
-          }                                                                                                               \
+        // (bits 16..31 of ab: the two sides' slots in the active-count sets, fixed for the solve - decoding them per iteration cost 28
+        // VALU instructions per contact; the counts of the previous iteration are loaded with the geometry, not after the velocity test:
+        // one LDS round trip less on the path of every active contact)
+        const int a = abq & 0xff, b = (abq >> 8) & 0xff, sa = (abq >> 16) & 0xff, sb = (abq >> 24) & 0xff;
+        const f3 p = F3(S.cp[0][c], S.cp[1][c], S.cp[2][c]);
+        // (the four body rows in flight together: the plain expression loads side A, waits, then side B into the same registers)
+        f3 ua = ld3v(S.bv[a]), wa = ld3v(S.bw[a]), ub = ld3v(S.bv[b]), wb = ld3v(S.bw[b]);
+        SDX_PIN3x4(ua, wa, ub, wb);
+        const f3 vr = (ua + cross(wa, p)) - (ub + cross(wb, p));
+        const float vn = dot(vr, n);
+        const float lam0 = lam[q][0], lam1 = lam[q][1], lam2 = lam[q][2];
+        if (lam0 > 0.0f || vn < vtgt[q]) {
+          if (a != BODY_W) atomicAdd(&S.acount[nxt][sa], 1);
+          if (b != BODY_W) atomicAdd(&S.acount[nxt][sb], 1);
+          const int ca = S.acount[cur][sa], cb = S.acount[cur][sb];
+          const float na = a != BODY_W ? (float)(ca > 1 ? ca : 1) : 0.0f;
+          const float nb = b != BODY_W ? (float)(cb > 1 ? cb : 1) : 0.0f;
+          const float w0 = na * wA[q][0] + nb * wB[q][0];
+          const float w1 = na * wA[q][1] + nb * wB[q][1];
+          const float w2 = na * wA[q][2] + nb * wB[q][2];
+          const float ln = fmaxf(0.0f, lam0 - relax * (vn - vtgt[q]) * SDX_RCP(w0));
+          const float lim = (DR ? muq[q] : mu) * ln;
+          float l1 = lam1 - relax * dot(vr, t1) * SDX_RCP(w1);
+          l1 = fminf(lim, fmaxf(-lim, l1));
+          float l2 = lam2 - relax * dot(vr, t2) * SDX_RCP(w2);
+          l2 = fminf(lim, fmaxf(-lim, l2));
+          lam[q][0] = ln; lam[q][1] = l1; lam[q][2] = l2;
+          P = n * (ln - lam0) + t1 * (l1 - lam1) + t2 * (l2 - lam2);
         }
-        SDX_SEG_STEP(1) SDX_SEG_STEP(2) SDX_SEG_STEP(4) SDX_SEG_STEP(8)
-#undef SDX_SEG_STEP
       }
-      if (!d_link) {
-        if ((cd >> 11) & 1u) {
-          SDX_PIN4(K_); SDX_PIN1(K_[4]); SDX_PIN1(K_[5]); SDX_PIN1(imb_); SDX_PIN3(u_); SDX_PIN3(w_);
-          const float* K = K_;
-          const f3 dw = F3(K[0] * acc[3] + K[3] * acc[4] + K[4] * acc[5], K[3] * acc[3] + K[1] * acc[4] + K[5] * acc[5],
-                           K[4] * acc[3] + K[5] * acc[4] + K[2] * acc[5]);
-          st3(S.bv[d_body], (u_ + F3(acc[0], acc[1], acc[2]) * imb_) - cross(dw, x));
-          st3(S.bw[d_body], w_ + dw);
-          S.acount[cur][d_body] = 0;   // read by [AC] before the barrier above; it is the set [AC] of the next iteration counts into
-        }
-      } else {
-        const int k = d_body - NF;
-        const int tj0 = tjp & 0xff, tj1 = tjp >> 8;
-        const f3 F = F3(acc[0], acc[1], acc[2]), M = F3(acc[3], acc[4], acc[5]);
-        // generalised impulse on the d_sub-th (and (d_sub + 8)-th) dof of the path: a_j . (M + (o_k - o_j) x F); la[ND + 1] = 0 for "none"
-        S.Qc[k][d_sub] = dot(ld3(S.la[tj0 + 1]), M + cross(x - ld3(S.bp[NF + tj0 + 1]), F));
-        if (d_sub < 4) S.Qc[k][d_sub + 8] = dot(ld3(S.la[tj1 + 1]), M + cross(x - ld3(S.bp[NF + tj1 + 1]), F));
-        if (last_substep && d_sub == 0) { S.cf[k][0] += acc[0]; S.cf[k][1] += acc[1]; S.cf[k][2] += acc[2]; }   // net impulse on the link so far
-      }
-      if (td == NL * LL) { S.acount[cur][NF] = 0; }
+      S.P[0][c] = P.x; S.P[1][c] = P.y; S.P[2][c] = P.z;
     }
-#ifdef SDX_LANE_CLOCK
-    { LCLOCK(lc_d2); LMAX(59, lc_d2 - lc_d0); }
-#endif
-    if (has_robot && !ABL(8)) {
-      // robot section, ONE stage on 8 lanes per link = waves 0..2, which are also the link gather's: they meet at their OWN barrier (an LDS
-      // counter) while waves 3..7 are still gathering the bricks - the section touches nothing those read or write (Qc, qd / qdb, the link
-      // rows of the body table) - and the pass closes with the one workgroup barrier below (round 6; a workgroup barrier in front of this
-      // section made every pass of an env whose hand touches bricks brick gather + robot section long instead of the longer of the two).
-      // Every group sums the generalised impulses of all 23 dofs from the Qc rows of the touched links below each dof (3 dofs per lane),
-      // shares them inside the group lane to lane (ds_bpermute: no LDS space - the impulse rows are still being read by the brick
-      // gather), then qd += Hinv dQ for the (<= 2) path dofs of this lane and the link's twist
-      static_assert((NL * 8) % 64 == 0, "the robot section's lanes are whole waves");
-      int tr = tid;
-      SDX_OPAQUE(tr);
-      if (tr < NL * 8) {
-        // (requested before the waves meet: row `lane` of Hinv as six 16-byte loads and the joint velocity it belongs to)
-        const int li = tr & 63, ri = li < ND ? li : 0;
-        const float* qsrc = qpar ? S.qdb : S.qd;
-        float* qdst = qpar ? S.qd : S.qdb;
-        f4v arow[HP / 4];
-#pragma unroll
-        for (int k4 = 0; k4 < HP / 4; ++k4) arow[k4] = *reinterpret_cast<const f4v*>(&S.A[ri][4 * k4]);
-        const float qi = qsrc[li < ND ? li : ND];   // (qd[ND] = 0)
-        WAVES_BARRIER(&S.rsync, (NL * 8 / 64) * (it - it0 + 1), NL * 8);
-        SSTAMP(21);
-        const int rj = tr / 8, rs = tr % 8;
-        float qa[3];
-#pragma unroll
-        for (int u = 0; u < 3; ++u) {
-          const int j = rs + 8 * u;
-          float acc = 0.0f;
-          if (j < ND) {
-            // the position of dof j in the path of a link below it = the number of dofs above j: the same for every such link
-            const int slot = __popc(S.anc[j + 1] & ((1u << j) - 1u));
-            uint32_t m = S.desc[j] & touched;
-#pragma unroll
-            for (int t = 0; t < 6; ++t) {          // (independent loads: in flight together)
-              const int k = m ? __ffs(m) - 1 : 0;
-              acc += m ? S.Qc[k][slot] : 0.0f;
-              m &= m - 1;
-            }
-            while (m) {
-              const int k = __ffs(m) - 1;
-              m &= m - 1;
-              acc += S.Qc[k][slot];
-            }
-          }
-          qa[u] = acc;
-        }
-        // qd += Hinv dQ, ONCE per wave: lane i < 23 multiplies row i of Hinv with Q, whose entry j every 8-lane group holds in lane j % 8
-        // (v_readlane from the wave's first group: no LDS).  Round 5 had every lane multiply the rows of its (<= 2) path dofs: 46 + 23 LDS
-        // loads per lane in three dependent batches; now 6 + 2.
-        float dq = 0.0f;
-#pragma unroll
-        for (int j = 0; j < ND; ++j) {
-          const f4v a4 = arow[j >> 2];
-          const float aij = (j & 3) == 0 ? a4.x : ((j & 3) == 1 ? a4.y : ((j & 3) == 2 ? a4.z : a4.w));
-          dq += aij * SDX_READLANE(qa[j >> 3], j & 7);
-        }
-        const float qn = li < ND ? qi + dq : 0.0f;
-        if (tr < ND) qdst[tr] = qn;               // the other copy: groups still read the source copy of this pass
-        const int tj0 = tjp & 0xff, tj1 = tjp >> 8;
-        const float q0 = __shfl(qn, tj0, 64), q1 = __shfl(qn, tj1, 64);   // (tj = ND, "no dof": lane ND of the wave holds 0)
-        const f3 pk = ld3(S.bp[NF + rj]);
-        const f3 a0 = ld3(S.la[tj0 + 1]) * q0, a1 = ld3(S.la[tj1 + 1]) * q1;
-        f3 w = a0 + a1;
-        f3 v = cross(a0, pk - ld3(S.bp[NF + tj0 + 1])) + cross(a1, pk - ld3(S.bp[NF + tj1 + 1]));
-        w.x = sum8(w.x); w.y = sum8(w.y); w.z = sum8(w.z);
-        v.x = sum8(v.x); v.y = sum8(v.y); v.z = sum8(v.z);
-        if (rs == 0 && rj > 0) { st3(S.bw[NF + rj], w); st3(S.bv[NF + rj], v - cross(w, pk)); }
-      }
-      qpar ^= 1;
-    }
-    __syncthreads();
-    SSTAMP(22);
   }
+#ifdef SDX_LANE_CLOCK
+  { LCLOCK(lc_ac1); LMAX(55, lc_ac1 - lc_ac0); if (tid == NT - 1) LMAX(56, lc_ac1 - lc_ac0); }
+#endif
+}
+
+// [D], link tail (every lane of link k holds the sums after the reduction; this is its lane d_sub): the wrench (F, M about the link
+// origin x) projected on the dofs of the link's path -> Qc for the robot section; last substep: the net impulse on the link so far -> cf
+__device__ __forceinline__ void gather_link_tail(PhysLds& S, int k, int d_sub, int tjp, f3 x, const float (&acc)[6], bool last_substep) {
+  const int tj0 = tjp & 0xff, tj1 = tjp >> 8;
+  const f3 F = F3(acc[0], acc[1], acc[2]), M = F3(acc[3], acc[4], acc[5]);
+  // generalised impulse on the d_sub-th (and (d_sub + 8)-th) dof of the path: a_j . (M + (o_k - o_j) x F); la[ND + 1] = 0 for "none"
+  S.Qc[k][d_sub] = dot(ld3(S.la[tj0 + 1]), M + cross(x - ld3(S.bp[NF + tj0 + 1]), F));
+  if (d_sub < 4) S.Qc[k][d_sub + 8] = dot(ld3(S.la[tj1 + 1]), M + cross(x - ld3(S.bp[NF + tj1 + 1]), F));
+  if (last_substep && d_sub == 0) { S.cf[k][0] += acc[0]; S.cf[k][1] += acc[1]; S.cf[k][2] += acc[2]; }   // net impulse on the link so far
+}
+
+// [D], brick tail (the brick's LAST lane after the scan): w += Iw^-1 M, u += F / m - dw x x, from the operands gather() requested before the scan
+__device__ __forceinline__ void gather_brick_tail(PhysLds& S, int d_body, f3 x, const float (&acc)[6], float (&K_)[6], float imb_, f3 u_, f3 w_) {
+  SDX_PIN4(K_); SDX_PIN1(K_[4]); SDX_PIN1(K_[5]); SDX_PIN1(imb_); SDX_PIN3(u_); SDX_PIN3(w_);
+  const float* K = K_;
+  const f3 dw = F3(K[0] * acc[3] + K[3] * acc[4] + K[4] * acc[5], K[3] * acc[3] + K[1] * acc[4] + K[5] * acc[5],
+                   K[4] * acc[3] + K[5] * acc[4] + K[2] * acc[5]);
+  st3(S.bv[d_body], (u_ + F3(acc[0], acc[1], acc[2]) * imb_) - cross(dw, x));
+  st3(S.bw[d_body], w_ + dw);
+}
+
+// ---- [D] gather (LL lanes per link, a slice per brick lane): F = sum(+-P), M = sum(+-(p - x) x P) about the body's reference point x; each
+// lane sums its slice in ascending contact order, the partial sums are combined in a fixed order (deterministic); inactive contacts carry
+// P = 0.  Bricks: gather_brick_tail().  Links: gather_link_tail(), right away (8 lanes, <= 2 dofs each) -> Qc for the robot section.
+// Reads ent, the P rows, cp, bp; writes the brick rows of the body table, Qc, cf and zeroes acount[cur] for the pass after the next.
+template <int NT>
+__device__ __forceinline__ void gather(PhysLds& S, int tid, int it, bool has_robot, bool last_substep, int gbeg, int gend, int tjp, long long* dbg, int abl_bits) {
+  const int cur = it & 1;
+  LCLOCK(lc_d0);
+  int td = tid;
+  SDX_OPAQUE(td);   // lane coordinates re-derived per iteration instead of living in registers across the loop
+  const bool d_link = has_robot && td < NL * LL;   // waves 0..2 of an env whose hand touches something: link lanes; every other lane is a brick lane
+  const uint32_t cd = (uint32_t)gbeg;              // (brick lanes: the slice descriptor)
+  const int d_body = d_link ? NF + td / LL : (int)(cd & 0x7fu), d_sub = d_link ? td % LL : 0;
+  const int gstride = d_link ? LL : 1;
+  const int ibeg = d_link ? gbeg : (int)((cd >> 12) & 0xfffu);
+  float acc[6] = {0, 0, 0, 0, 0, 0};
+  const f3 x = ld3(S.bp[d_body]);
+  // four entries per trip (the index loads, then the payloads, in flight together); not unrolled further: the decoded
+  // addresses of a longer window would be kept in registers across the whole iteration loop
+  // two entries at a time: index loads pinned in front of the 12 payload loads, those in front of the arithmetic (four dependent LDS
+  // round trips per trip of four entries instead of eight; all GU = 4 entries of a trip at once spill inside the loop)
+#pragma unroll 1
+  for (int i = ibeg; i < (ABL(1) ? ibeg : gend); i += GU * gstride) {
+#pragma unroll
+    for (int h2 = 0; h2 < GU; h2 += 2) {
+      const int i0 = i + h2 * gstride, i1 = i0 + gstride;
+      int e0 = S.ent[i0 < gend ? i0 : i], e1 = S.ent[i1 < gend ? i1 : i];
+      SDX_PIN1(e0); SDX_PIN1(e1);
+      const int c0 = e0 & 0x7fff, c1 = e1 & 0x7fff;
+      f3 P0 = F3(S.P[0][c0], S.P[1][c0], S.P[2][c0]), C0 = F3(S.cp[0][c0], S.cp[1][c0], S.cp[2][c0]);
+      f3 P1 = F3(S.P[0][c1], S.P[1][c1], S.P[2][c1]), C1 = F3(S.cp[0][c1], S.cp[1][c1], S.cp[2][c1]);
+      SDX_PIN3x4(P0, C0, P1, C1);
+      {
+        const float sg = i0 < gend ? ((e0 & 0x8000) ? -1.0f : 1.0f) : 0.0f;
+        const f3 P = P0 * sg;
+        const f3 M = cross(C0 - x, P);
+        acc[0] += P.x; acc[1] += P.y; acc[2] += P.z; acc[3] += M.x; acc[4] += M.y; acc[5] += M.z;
+      }
+      {
+        const float sg = i1 < gend ? ((e1 & 0x8000) ? -1.0f : 1.0f) : 0.0f;
+        const f3 P = P1 * sg;
+        const f3 M = cross(C1 - x, P);
+        acc[0] += P.x; acc[1] += P.y; acc[2] += P.z; acc[3] += M.x; acc[4] += M.y; acc[5] += M.z;
+      }
+    }
+  }
+#ifdef SDX_LANE_CLOCK
+  { LCLOCK(lc_d1); LMAX(57, lc_d1 - lc_d0); LMAX(58, (gend - ibeg + gstride - 1) / gstride); }
+#endif
+  // the brick update's operands (inverse inertia, inverse mass, u, w: 13 numbers) are requested BEFORE the lane reductions and pinned
+  // after them: their LDS round trip runs under the DPP adds instead of after them (every lane loads: the branch comes later)
+  const int tb = d_link ? 0 : d_body;
+  float K_[6], imb_ = S.bim[tb];
+#pragma unroll
+  for (int r = 0; r < 6; ++r) K_[r] = S.bK[tb][r];
+  f3 u_ = ld3(S.bv[tb]), w_ = ld3(S.bw[tb]);
+  if (d_link) {
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      acc[r] = sum4(acc[r]);
+      acc[r] += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc[r]), 0x141, 0xF, 0xF, true));
+    }
+  } else {
+    // the slices of a brick sit on consecutive lanes of one 16-lane row: inclusive segmented scan (row_shr 1, 2, 4, 8; lane `so` of the
+    // brick adds the value `sh` lanes back while that lane still belongs to the brick), after which the brick's LAST lane holds the
+    // sums - slices in ascending contact order, combined in the scan's fixed tree (deterministic)
+    const int so = (int)((cd >> 7) & 15u);
+#define SDX_SEG_STEP(sh)                                                                                                    \
+    {                                                                                                                       \
+      const bool take = so >= (sh);                                                                                         \
+      _Pragma("unroll") for (int r = 0; r < 6; ++r) {                                                                       \
+        const float t = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc[r]), 0x110 + (sh), 0xF, 0xF, true)); \
+        acc[r] += take ? t : 0.0f;                                                                                          \
+      }                                                                                                                     \
+    }
+    SDX_SEG_STEP(1) SDX_SEG_STEP(2) SDX_SEG_STEP(4) SDX_SEG_STEP(8)
+#undef SDX_SEG_STEP
+  }
+  if (!d_link) {
+    if ((cd >> 11) & 1u) {
+      gather_brick_tail(S, d_body, x, acc, K_, imb_, u_, w_);
+      S.acount[cur][d_body] = 0;   // read by [AC] before the pass's first barrier; it is the set [AC] of the next iteration counts into
+    }
+  } else {
+    gather_link_tail(S, d_body - NF, d_sub, tjp, x, acc, last_substep);
+  }
+  if (td == NL * LL) { S.acount[cur][NF] = 0; }
+#ifdef SDX_LANE_CLOCK
+  { LCLOCK(lc_d2); LMAX(59, lc_d2 - lc_d0); }
+#endif
+}
+
+// ---- robot section, ONE stage on 8 lanes per link = waves 0..2, which are also the link gather's: they meet at their OWN barrier (an LDS
+// counter) while waves 3..7 are still gathering the bricks - the section touches nothing those read or write (Qc, qd / qdb, the link
+// rows of the body table) - and the pass closes with the one workgroup barrier of solve()'s loop (round 6; a workgroup barrier in front of
+// this section made every pass of an env whose hand touches bricks brick gather + robot section long instead of the longer of the two).
+// Every group sums the generalised impulses of all 23 dofs from the Qc rows of the touched links below each dof (3 dofs per lane),
+// shares them inside the group lane to lane (ds_bpermute: no LDS space - the impulse rows are still being read by the brick
+// gather), then qd += Hinv dQ for the (<= 2) path dofs of this lane and the link's twist.
+// `arrivals`: what the waves' own barrier has counted once all of them are here = waves x (passes so far, this one included).  Reads Hinv,
+// Qc and the copy qpar of the joint velocities (0: qd, 1: qdb); writes the other copy and the link rows of the body table.
+template <int NT>
+__device__ __forceinline__ void robot_section(PhysLds& S, int tid, int arrivals, int qpar, uint32_t touched, int tjp, long long* dbg) {
+  int tr = tid;
+  SDX_OPAQUE(tr);
+  if (tr < NL * 8) {
+    // (requested before the waves meet: row `lane` of Hinv as six 16-byte loads and the joint velocity it belongs to)
+    const int li = tr & 63, ri = li < ND ? li : 0;
+    const float* qsrc = qpar ? S.qdb : S.qd;
+    float* qdst = qpar ? S.qd : S.qdb;
+    f4v arow[HP / 4];
+#pragma unroll
+    for (int k4 = 0; k4 < HP / 4; ++k4) arow[k4] = *reinterpret_cast<const f4v*>(&S.A[ri][4 * k4]);
+    const float qi = qsrc[li < ND ? li : ND];   // (qd[ND] = 0)
+    WAVES_BARRIER(&S.rsync, arrivals, NL * 8);
+    SSTAMP(21);
+    const int rj = tr / 8, rs = tr % 8;
+    float qa[3];
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+      const int j = rs + 8 * u;
+      float acc = 0.0f;
+      if (j < ND) {
+        // the position of dof j in the path of a link below it = the number of dofs above j: the same for every such link
+        const int slot = __popc(S.anc[j + 1] & ((1u << j) - 1u));
+        uint32_t m = S.desc[j] & touched;
+#pragma unroll
+        for (int t = 0; t < 6; ++t) {          // (independent loads: in flight together)
+          const int k = m ? __ffs(m) - 1 : 0;
+          acc += m ? S.Qc[k][slot] : 0.0f;
+          m &= m - 1;
+        }
+        while (m) {
+          const int k = __ffs(m) - 1;
+          m &= m - 1;
+          acc += S.Qc[k][slot];
+        }
+      }
+      qa[u] = acc;
+    }
+    // qd += Hinv dQ, ONCE per wave: lane i < 23 multiplies row i of Hinv with Q, whose entry j every 8-lane group holds in lane j % 8
+    // (v_readlane from the wave's first group: no LDS).  Round 5 had every lane multiply the rows of its (<= 2) path dofs: 46 + 23 LDS
+    // loads per lane in three dependent batches; now 6 + 2.
+    float dq = 0.0f;
+#pragma unroll
+    for (int j = 0; j < ND; ++j) {
+      const f4v a4 = arow[j >> 2];
+      const float aij = (j & 3) == 0 ? a4.x : ((j & 3) == 1 ? a4.y : ((j & 3) == 2 ? a4.z : a4.w));
+      dq += aij * SDX_READLANE(qa[j >> 3], j & 7);
+    }
+    const float qn = li < ND ? qi + dq : 0.0f;
+    if (tr < ND) qdst[tr] = qn;               // the other copy: groups still read the source copy of this pass
+    const int tj0 = tjp & 0xff, tj1 = tjp >> 8;
+    const float q0 = __shfl(qn, tj0, 64), q1 = __shfl(qn, tj1, 64);   // (tj = ND, "no dof": lane ND of the wave holds 0)
+    const f3 pk = ld3(S.bp[NF + rj]);
+    const f3 a0 = ld3(S.la[tj0 + 1]) * q0, a1 = ld3(S.la[tj1 + 1]) * q1;
+    f3 w = a0 + a1;
+    f3 v = cross(a0, pk - ld3(S.bp[NF + tj0 + 1])) + cross(a1, pk - ld3(S.bp[NF + tj1 + 1]));
+    w.x = sum8(w.x); w.y = sum8(w.y); w.z = sum8(w.z);
+    v.x = sum8(v.x); v.y = sum8(v.y); v.z = sum8(v.z);
+    if (rs == 0 && rj > 0) { st3(S.bw[NF + rj], w); st3(S.bv[NF + rj], v - cross(w, pk)); }
+  }
+}
+// isa_check: loop stage end
+
+// ---- exit: the joint velocities into qd, the bricks' rows of the body table back to (v, w); WARM: the impulse cache (wlam, wcount: HBM)
+template <int NT, bool WARM, int CPT>
+__device__ __forceinline__ void solve_exit(PhysLds& S, int tid, int nc, int qpar, const float (&lam)[CPT][3], int32_t* wcount, float* wlam) {
   if (qpar && tid < ND) S.qd[tid] = S.qdb[tid];   // (lane tid is also the one that integrates dof tid)
   // body table back to (v, w) for the bricks (the link twists are rebuilt from qd by the next FK pass)
   for (int i = tid; i < NF; i += NT) st3(S.bv[i], ld3(S.bv[i]) + cross(ld3(S.bw[i]), ld3(S.bp[i])));
@@ -723,4 +765,76 @@ __device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, fl
     // no agent-scope fence: the next reader is this workgroup's next substep, many workgroup barriers later on the same CU (the
     // vector L1 is shared by the waves of a workgroup), or the next launch
   }
+}
+
+// Warm start (DESIGN.md section 3.E; oracle: solve()): wcount / wkey / wlam are THIS env's impulse cache in HBM.  A contact that existed
+// in the previous solve (same pair, direction and sample) starts from sc.warm_start x the impulses it ended with; iteration -1 of the
+// loop below spreads those impulses over the bodies with the gather machinery of a normal iteration.  WARM is a template parameter:
+// the default (cold) solver carries none of this code (it cost 2.6 % of the kernel as a run-time switch).
+template <int NT, bool WARM, bool DR = false>
+__device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, float h, bool last_substep, long long* dbg,
+                                      int32_t* wcount, uint32_t* wkey, float* wlam, int abl_bits, const float* bfr = nullptr, const float* lfr = nullptr) {
+  constexpr int CPT = MAXC / NT;   // contact rows owned by one lane
+  static_assert(CPT * NT == MAXC, "NT must divide SDX_MAXC");
+  static_assert(CPT * 11 <= 64 && MAXC < 0x7ff, "11-bit cache positions of a lane's contacts in one 64-bit word");
+  const sdx_scene_desc& sc = C->sc;
+  const int nc = S.nc;
+  const float mu = sc.friction, relax = sc.jacobi_relax;
+  SSTAMP(16);
+  SolveRows<CPT> R;
+  // the warm-start gate's constants (block-uniform; computed here, at the top: born inside row_weights() they cost the randomization
+  // variant 14 more VGPR spills)
+  const float beta = sc.warm_start;
+  const float inv_age = sc.warm_age > 0.0f ? 1.0f / sc.warm_age : 1e30f;
+  // depth gate expressed on the velocity target the lane keeps anyway: sep < -WARM_DEPTH * offset <=> vtgt > baumgarte * depth / h
+  const float wdeep = sc.baumgarte * (WARM_DEPTH * sc.contact_offset) / h;
+  int nold = WARM ? *wcount : 0;   // block-uniform
+  if (nold > MAXC) nold = MAXC;
+  load_rows<NT, WARM>(sc, S, tid, nc, h, nold, wkey, R);
+  SSTAMP(23);
+  csr_clear<NT>(S, tid, last_substep);
+  uint64_t wmatch;
+  uint32_t wage;
+  warm_match<NT, WARM>(S, tid, nc, nold, R.ckey, wkey, wmatch, wage);
+  csr_count<NT>(S, tid, nc, R.ab);
+  SSTAMP(24);
+  csr_offsets_and_packing<NT>(S, tid);
+  SSTAMP(25);
+  csr_fill<NT>(S, tid, nc, R.ab);
+  SSTAMP(26);
+  const int rbeg = S.eoff[NF], nrob = S.eoff[NB] - rbeg;   // the robot's sides: entries [rbeg, rbeg + nrob), grouped by link
+  const bool has_robot = nrob > 0;                          // block-uniform
+  const uint32_t cdesc = gather_slice(S, tid);
+  if (tid == 0) S.nrob = nrob;
+  SCOUNT(52, nc); SCOUNT(53, S.eoff[NB]); SCOUNT(54, nrob);
+  csr_rank<NT>(S, tid, abl_bits);
+  SSTAMP(27);   // (27 closes the rank pass, 28 opens the link inertia: tools/time_physics.py reads both)
+  SSTAMP(28);
+  const uint32_t touched = link_inertia<NT>(S, tid, has_robot);
+  SSTAMP(29);
+  row_weights<NT, WARM>(S, tid, nc, has_robot, wmatch, wage, wlam, beta, inv_age, wdeep, R, abl_bits);
+  SSTAMP(30);
+  int gbeg, gend, tjp;
+  pass_setup<NT>(S, tid, has_robot, nrob, cdesc, gbeg, gend, tjp);
+  SSTAMP(17);
+  loop_registers<DR>(sc, bfr, lfr, R, gbeg, gend, tjp);
+  int qpar = 0;   // robot section: joint velocities are read from S.qd (0) / S.qdb (1) and written to the other
+  const int it0 = (WARM && nold > 0) ? -1 : 0;
+  for (int it = it0; it < (ABL(4) ? 1 : sc.solver_iters); ++it) {   // it = -1: only the gather of the warm-start impulses
+#ifdef SDX_PHASE_CLOCK
+    if (it == 1) dbg = nullptr;
+#endif
+    SSTAMP(18);
+    contact_update<NT, WARM, DR>(S, tid, nc, it, mu, relax, R, dbg, abl_bits);
+    __syncthreads();
+    SSTAMP(20);
+    gather<NT>(S, tid, it, has_robot, last_substep, gbeg, gend, tjp, dbg, abl_bits);
+    if (has_robot && !ABL(8)) {   // (waves 0..2, beside the brick gather of waves 3..7)
+      robot_section<NT>(S, tid, (NL * LL / 64) * (it - it0 + 1), qpar, touched, tjp, dbg);
+      qpar ^= 1;
+    }
+    __syncthreads();
+    SSTAMP(22);
+  }
+  solve_exit<NT, WARM>(S, tid, nc, qpar, R.lam, wcount, wlam);
 }

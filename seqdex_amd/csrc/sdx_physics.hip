@@ -13,9 +13,10 @@
 //   * contact geometry (point, normal) stays in LDS; each lane keeps only what changes or divides per iteration for its 3 contacts in
 //     registers (accumulated impulses, un-split inverse masses of both sides, target velocity, body ids);
 //   * per solver iteration: [AC] relative velocity, active flag -> counted for the NEXT iteration (integer LDS atomics), Jacobi update with
-//     the counts of the previous one, impulse to LDS | barrier | [D] CSR gather per body (8 lanes per link, 4 per brick); links project
-//     their wrench on the dofs of their path | barrier | robot only: every 8-lane group sums the generalised impulses, applies Hinv and
-//     rebuilds its link's twist | barrier;
+//     the counts of the previous one, impulse to LDS | barrier | [D] CSR gather per body (8 lanes per link, 1..16 per brick by the length
+//     of its list); links project their wrench on the dofs of their path | the link lanes' own barrier | robot only: every 8-lane group
+//     sums the generalised impulses, applies Hinv and rebuilds its link's twist | barrier.  The solver is the list of its stages, one
+//     function per phase-clock interval of tools/time_physics.py (sdx_phys_solve.h);
 //   * everything serial (FK levels, Cholesky in registers, drive, twists) runs on wave 0 with wave-synchronous hand-offs instead of
 //     workgroup barriers; the other waves meet it at the next barrier;
 //   * broadphase: every lane tests its strided candidate BODY pairs (bounding boxes) into a bit mask, ONE block scan places all hits; the
@@ -26,11 +27,12 @@
 // may use what the ones before it define; none forward-declares a function of another):
 //   sdx_phys_lds.h      constants, wave hand-offs (WAVE_SYNC, WAVES_BARRIER, WAVE_SIGNAL / WAVES_WAIT), PhysLds and the table of its overlays,
 //                       Box, the clock / ablation macros
-//   sdx_phys_shapes.h   signed distance of a box, compound shapes, dir_setup ... pair_contacts, point_vel, brick_w
+//   sdx_phys_shapes.h   signed distance of a box, compound shapes, dir_setup ... pair_contacts, point_vel
 //   sdx_phys_broad.h    tri_index, block_scan_small, the candidate tests, broad_mask_part
 //   sdx_phys_robot.h    A / B: inertia_mul, twists_wave0, fk_wave0, mass_matrix
 //   sdx_phys_collide.h  D: collide
-//   sdx_phys_solve.h    E: robot_w, solve
+//   sdx_phys_solve.h    E: solve and its stages: load_rows, warm_match, csr_clear .. csr_rank, link_inertia, row_weights, pass_setup,
+//                       loop_registers; per pass contact_update [AC], gather [D], robot_section; solve_exit
 //   this file           write_kinematics, load_constants, k_physics (C the drive and F the integration are in its body), k_order,
 //                       k_kinematics, the launchers
 #include <stdlib.h>

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "seqdex_amd", "csrc")
 _SO = os.path.join(HERE, "libsdx_emu.so")
 _SRCS = [os.path.join(HERE, "hipemu.cpp"), os.path.join(HERE, "physics_driver.cpp"), os.path.join(CSRC, "sdx_physics.hip")]
-# extra g++ flags for every emulator build (e.g. "-DSDX_D_SORT": a compile-time variant of a kernel under test); rebuild with force=True after changing it
+# extra g++ flags for every emulator build (e.g. "-DSOME_SWITCH=1": a compile-time variant of a kernel under test); rebuild with force=True after changing it
 _EXTRA = os.environ.get("SDX_EMU_CXXFLAGS", "").split()
 _lib = None
 # the whole simulator behind the C ABI of include/seqdex.h (sdx_capi + task + physics + camera sources) on the emulator.  sdx_randomize.hip is NOT

@@ -1,6 +1,8 @@
 """Static check of k_physics<512>'s gfx950 code: registers, scratch bytes per lane, and the scratch / LDS / VALU instruction counts of the
-solver's iteration loop (the ISA between the source lines of the loop head and of its closing stamp, via -gline-tables-only).  The loop
-is looked for in sdx_physics.hip and the sdx_phys_*.h it includes; code inlined from other lines of those files is not part of the loop.
+solver's iteration loop (the ISA between the source lines of the loop head and of its closing stamp, via -gline-tables-only) and of the
+per-pass stage functions the loop calls: the lines of the same file between the comments `// isa_check: loop stage begin` and
+`// isa_check: loop stage end` (any number of such ranges).  The loop is looked for in sdx_physics.hip and the sdx_phys_*.h it includes;
+code inlined from any other line of those files is not part of the loop.
 usage: python tools/isa_check.py [--randomize] [extra hipcc flags...]      (cross-compiles; no GPU needed)
 --randomize: the same report for the domain-randomization variant k_physics<512 | SDX_PHYS_DR> (= k_physics<513>)"""
 import os
@@ -23,6 +25,11 @@ LOOPFILE = next(f for f in UNIT if "for (int it = it0;" in open(os.path.join(CSR
 src = open(os.path.join(CSRC, LOOPFILE)).read().split("\n")
 lo = next(i for i, l in enumerate(src) if "for (int it = it0;" in l) + 1
 hi = next(i for i, l in enumerate(src) if "SSTAMP(22);" in l and i > lo) + 1
+# the loop itself, then the marked ranges of the stage functions it calls (1-based, inclusive)
+begins = [i + 1 for i, l in enumerate(src) if "// isa_check: loop stage begin" in l]
+ends = [i + 1 for i, l in enumerate(src) if "// isa_check: loop stage end" in l]
+assert len(begins) == len(ends) and all(b < e for b, e in zip(begins, ends)), "unpaired loop stage markers in " + LOOPFILE
+RANGES = [(lo, hi)] + list(zip(begins, ends))
 with tempfile.TemporaryDirectory() as td:
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-gline-tables-only",
            "-Rpass-analysis=kernel-resource-usage", "-save-temps=obj", "-c", SRC, "-o", os.path.join(td, "p.o")] + sys.argv[1:]
@@ -64,7 +71,7 @@ with tempfile.TemporaryDirectory() as td:
         op = t.split()[0]
         if op.startswith("scratch_"):
             tot_scratch += 1
-        if cur is not None and lo <= cur <= hi:
+        if cur is not None and any(a <= cur <= b for a, b in RANGES):
             loop["total"] += 1
             if op.startswith("scratch_"):
                 loop["scratch"] += 1
@@ -77,4 +84,4 @@ with tempfile.TemporaryDirectory() as td:
             elif op.startswith("s_"):
                 loop["salu"] += 1
     print("scratch instructions in the kernel:", tot_scratch)
-    print("iteration loop (%ssource lines %d-%d):" % ("" if LOOPFILE == "sdx_physics.hip" else LOOPFILE + ", ", lo, hi), loop)
+    print("iteration loop (%ssource lines %s):" % ("" if LOOPFILE == "sdx_physics.hip" else LOOPFILE + ", ", ", ".join("%d-%d" % r for r in RANGES)), loop)
