@@ -420,6 +420,45 @@ int sdx_set_randomization(sdx_handle h, const sdx_dr_desc* desc, void* stream);
  * op(x, o) = x + o (additive) or x o (scaling). */
 int sdx_set_noise(sdx_handle h, const sdx_noise_attr* observations, const sdx_noise_attr* actions, void* stream);
 
+/* External forces and torques on rigid bodies (gym.apply_rigid_body_force_tensors).  forces_dev / torques_dev:
+ * caller-owned device f32 [N, SDX_BODIES, 3], indexed like SDX_T_RB; either may be NULL (no forces / no torques).  The wrench applies to
+ * the NEXT physics launch only - the one of sdx_simulate, or of sdx_step after its pre-physics kernel (not the settling launches of an
+ * Orient / Search reset event) - and is then forgotten.  A second call before that launch REPLACES the pending wrench, both pointers
+ * NULL clears it.  Nothing is enqueued here: the pointers travel by value with that launch, which reads the buffers on ITS stream, so
+ * they must stay alive and unchanged until it has run (`stream` is unused).  space is not SDX_SPACE_ENV / SDX_SPACE_LOCAL: SDX_ERR_INVALID.
+ *   point     the force acts at the body's centre of mass, the torque about it.
+ *   frames    SDX_SPACE_ENV: the env's world axes.  SDX_SPACE_LOCAL: the body's axes, rotated to world ONCE per step with the
+ *             orientation the body has at the start of the step; the world wrench is held constant over the substeps.
+ *   bodies    free bricks (rows SDX_BODY_BRICK0 .. + SDX_NFREE - 1): every substep v += F h / m, w += R diag(1 / I) R^T T h with the mass
+ *             and inertia the solver uses (seg_mass_scale on the target brick, the SDX_T_DR_BRICK factor while randomization is on), no
+ *             gyroscopic term.  Robot links 1 .. SDX_NLINK - 1: tau_j += sum over the links k below dof j of a_j . ((c_k - o_j) x F_k + T_k),
+ *             beside the velocity-product wrenches; the effort limit keeps applying to the drive only.  Rows of bodies that cannot move
+ *             are ignored: link 0, the fixed bricks, the statics, the object and goal actors.
+ *   contacts  SDX_T_CONTACT stays the sum of the contact impulses.
+ *   zero      a body whose force and torque rows are all zero is stepped bit for bit as without the call, negative zeros included. */
+typedef enum { SDX_SPACE_ENV = 0, SDX_SPACE_LOCAL = 1 } sdx_force_space;
+int sdx_apply_rigid_body_forces(sdx_handle h, const float* forces_dev, const float* torques_dev, int32_t space, void* stream);
+
+/* Random pushes on the target brick (the reference's forceScale / forceProbRange / forceDecay / forceDecayInterval, morb.py:1495-1516;
+ * DESIGN.md section 21).  rb_forces_dev f32 [N, SDX_BODIES, 3] and prob_dev f32 [N] are CALLER-OWNED device buffers (the task's rb_forces
+ * and random_force_prob): they are read and written by the launches of the calls that follow, must stay alive while the sampler is on,
+ * and are NOT part of a sim snapshot (copy them beside sdx_state_save_all / restore_all to repeat a run's pushes).  attr NULL or
+ * force_scale <= 0 turns the sampler off.  Independent of sdx_set_randomization.  Checked (SDX_ERR_INVALID with a message): finite
+ * numbers, 0 < prob_lo <= prob_hi <= 1, decay in (0, 1], decay_interval > 0, non-NULL buffers.  On the call itself every env draws
+ * its probability (enqueued on `stream`); rb_forces_dev is left as it is.
+ * While on, sdx_step and sdx_pre_physics launch k_force_perturb once, in this order:
+ *   1 reset  envs that reset in this call (reset_buf, as the randomization sampler reads it): their rows <- 0,
+ *            prob[e] <- exp((log lo - log hi) u + log hi);  sdx_reset_idx does this step for the envs of its mask
+ *   2 decay  rb_forces *= decay^(dt / decay_interval) over the whole tensor (the factor is rounded once from double)
+ *   3 push   where u' < prob[e]: the row of the env's target brick <- z m force_scale, z three standard normals, m the brick's mass as the
+ *            physics sees it (brick_mass x seg_mass_scale, x the SDX_T_DR_BRICK factor while randomization is on)
+ * and (rb_forces_dev, NULL, SDX_SPACE_ENV) becomes the pending wrench of that step's physics launch, REPLACING the caller's own pending
+ * wrench: extra forces are added into rb_forces_dev (they then decay like the pushes).
+ * Random numbers are stateless: hash(seed ^ 0xF0CE, env x 256 + slot, step counter); slot 0: u' (first 24-bit uniform), slot 1: z_x, z_y
+ * (cos, sin of one Box-Muller pair, in double, rounded once), slot 2: z_z (cos), slot 3: u. */
+typedef struct { float force_scale, prob_lo, prob_hi, decay, decay_interval; } sdx_force_perturb_attr;
+int sdx_set_force_perturbation(sdx_handle h, const sdx_force_perturb_attr* attr, float* rb_forces_dev, float* prob_dev, void* stream);
+
 /* View camera: depth, label and colour images of the listed envs from the current SDX_T_ROOT / SDX_T_RB, for
  * looking at the engine; no task's step launches it.  k_seg_camera's pinhole model: f = normalize(target - pos), r = normalize(f x up),
  * u = r x f, ray through pixel centre (row, col) d = f + r px + u py, row 0 on top; since d . f = 1 the depth of a hit is its distance
@@ -452,7 +491,8 @@ int sdx_render_view(sdx_handle h, const sdx_view_desc* view, const int32_t* env_
  * statistics and SDX_T_CONS_SUCCESSES, SDX_T_DR_GRAVITY, SDX_T_DR_FRAME and gravity's draw counter.
  * NOT part of any snapshot: the logs (the harvest, pile and T-value rings with their counts and keys, SDX_T_CONTACT_STATS, SDX_T_DEBUG),
  * the launch-order hints of k_physics, and configuration (loaded piles, T-value weights, the randomization descriptor and whether it is
- * on).  A restore_all rewinds the step counter: ring rows appended afterwards can REPEAT the keys of rows appended before the restore.
+ * on), a pending external wrench and the caller-owned buffers of sdx_set_force_perturbation (the task's rb_forces and
+ * random_force_prob: copy them beside the snapshot).  A restore_all rewinds the step counter: ring rows appended afterwards can REPEAT the keys of rows appended before the restore.
  * Env classes: a row may only be put into an env of the class it came from - env & 7 (the target brick), and additionally env % 3 for
  * InsertSim (the base plate and the insertion site); the RNG keys stay with the destination env.  Each row records its source env.
  * restore and clone never fault on a bad entry: they skip it and count it in sdx_state_stats - [0] env id or row index out of range

@@ -88,6 +88,14 @@ class NoiseAttr(C.Structure):
                 ("range", f32 * 2), ("range_correlated", f32 * 2)]
 
 
+class ForcePerturbAttr(C.Structure):
+    """sdx_force_perturb_attr"""
+    _fields_ = [("force_scale", f32), ("prob_lo", f32), ("prob_hi", f32), ("decay", f32), ("decay_interval", f32)]
+
+
+SPACE_ENV, SPACE_LOCAL = 0, 1         # sdx_force_space
+
+
 class OptState(C.Structure):
     """sdxp_opt_state"""
     _fields_ = [("rms_count", C.c_double), ("ac_t", i32), ("cv_t", i32), ("ac_lr", f32), ("cv_lr", f32)]
@@ -109,7 +117,7 @@ TP = dict(AC_PARAMS=0, AC_GRADS=1, CV_PARAMS=2, CV_GRADS=3, MB_OBS=4, MB_STATES=
 SDX_EXPORTS = ["sdx_create", "sdx_destroy", "sdx_tensor", "sdx_load_initial_states", "sdx_set_tvalue_weights", "sdx_set_retri_tvalue_weights",
                "sdx_step", "sdx_pre_physics", "sdx_simulate", "sdx_post_physics", "sdx_compute_observations",
                "sdx_reset_idx", "sdx_set_indexed", "sdx_refresh_kinematics", "sdx_render_segmentation", "sdx_num_envs", "sdx_last_error",
-               "sdx_set_randomization", "sdx_set_noise", "sdx_render_view",
+               "sdx_set_randomization", "sdx_set_noise", "sdx_render_view", "sdx_apply_rigid_body_forces", "sdx_set_force_perturbation",
                "sdx_state_create", "sdx_state_destroy", "sdx_state_save", "sdx_state_restore", "sdx_state_save_all", "sdx_state_restore_all",
                "sdx_state_clone", "sdx_state_stats",
                "sdxp_create", "sdxp_destroy", "sdxp_tensor", "sdxp_param_count", "sdxp_act", "sdxp_store_rewards",
@@ -146,6 +154,8 @@ def load_library():
     lib.sdx_set_randomization.argtypes = [vp, vp, vp]
     lib.sdx_set_noise.argtypes = [vp, C.POINTER(NoiseAttr), C.POINTER(NoiseAttr), vp]
     lib.sdx_render_view.argtypes = [vp, C.POINTER(ViewDesc), vp, i32, vp, vp, vp, vp]
+    lib.sdx_apply_rigid_body_forces.argtypes = [vp, vp, vp, i32, vp]
+    lib.sdx_set_force_perturbation.argtypes = [vp, C.POINTER(ForcePerturbAttr), vp, vp, vp]
     lib.sdx_state_create.argtypes = [vp, i32, C.POINTER(vp)]
     lib.sdx_state_destroy.argtypes = [vp]
     lib.sdx_state_save.argtypes = [vp, vp, vp, vp, i32, vp]

@@ -44,6 +44,8 @@ def get_args(argv=None):
     p.add_argument("--steps_num", type=int, default=-1)
     p.add_argument("--minibatch_size", type=int, default=-1)
     p.add_argument("--randomize", action="store_true", default=False)
+    p.add_argument("--force_scale", type=float, default=None,
+                   help="override env.forceScale: random pushes on the target brick, force = normal x mass x scale (0 = off; DESIGN.md section 21)")
     p.add_argument("--torch_deterministic", action="store_true", default=False)
     p.add_argument("--algo", type=str, default="lego")
     p.add_argument("--model_dir", type=str, default="")
@@ -118,6 +120,8 @@ def load_cfg(args):
         cfg["env"]["numEnvs"] = args.num_envs
     if args.episode_length > 0:                                                                             # CF:104-105
         cfg["env"]["episodeLength"] = args.episode_length
+    if getattr(args, "force_scale", None) is not None:
+        cfg["env"]["forceScale"] = float(args.force_scale)
     cfg["name"] = args.task
     cfg["headless"] = args.headless
     if "task" in cfg:                                                                                       # CF:111-116

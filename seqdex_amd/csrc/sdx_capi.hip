@@ -25,6 +25,13 @@ struct sdx_sim {
   struct TensorInfo { void* ptr; int64_t shape[4]; int ndim; int dtype; } tinfo[SDX_T_COUNT];
   sdx_dr_desc dr{};           // the randomization in force (meaningful while buf.dr_on != nullptr)
   sdx_noise_attr noise_obs{}, noise_act{};   // sdx_set_noise: distribution SDX_DR_NONE = off (always off while randomization is off)
+  // sdx_apply_rigid_body_forces: the wrench of the next physics launch (the caller's buffers; both nullptr: none pending)
+  const float *ext_force = nullptr, *ext_torque = nullptr;
+  int32_t ext_space = SDX_SPACE_ENV;
+  // sdx_set_force_perturbation: on while fp_forces != nullptr; fp_factor = decay^(dt / decay_interval)
+  sdx_force_perturb_attr fp{};
+  float fp_factor = 1.0f;
+  float *fp_forces = nullptr, *fp_prob = nullptr;
   float* act_pre = nullptr;   // [N,23] the clamped and noised actions of this step (scratch of k_noise -> k_pre_physics)
   SdxStateTab st_tab{};       // what an env's state is (sdx_state.h); d_st_tab: its device copy
   SdxStateTab* d_st_tab = nullptr;
@@ -94,6 +101,23 @@ static const float* noise_actions(sdx_sim* h, const float* actions_dev, int* fla
 static void post_physics_step(sdx_sim* h, hipStream_t st) {
   sdxk_post_physics(h->d_const, &h->buf, 1, st);
   if (h->noise_obs.distribution != SDX_DR_NONE) sdxk_noise(h->d_const, &h->buf, &h->noise_obs, h->buf.obs, h->buf.obs_c, h->buf.obs_w, 0, st);
+}
+
+// the physics launch a pending external wrench applies to (sdx_simulate; sdx_step's own, not the settling launches of a reset event): the
+// caller's pointers travel by value in that launch's copy of the buffer table, and the wrench is forgotten
+static void physics_step(sdx_sim* h, hipStream_t st) {
+  if (!h->ext_force && !h->ext_torque) { sdxk_physics(h->d_const, &h->buf, st); return; }
+  SdxBuf b = h->buf;
+  b.ext_force = h->ext_force; b.ext_torque = h->ext_torque; b.ext_space = h->ext_space;
+  h->ext_force = h->ext_torque = nullptr;
+  sdxk_physics(h->d_const, &b, st);
+}
+// the random pushes of this step (sdx_set_force_perturbation), before the step's resets clear the flags: the task's rb_forces become the
+// pending wrench, replacing the caller's own
+static void force_perturb_step(sdx_sim* h, hipStream_t st) {
+  if (!h->fp_forces) return;
+  sdxk_force_perturb(h->d_const, &h->buf, &h->fp, h->fp_factor, h->fp_forces, h->fp_prob, nullptr, SDX_FP_STEP, st);
+  h->ext_force = h->fp_forces; h->ext_torque = nullptr; h->ext_space = SDX_SPACE_ENV;
 }
 
 // ---------------------------------------------------------------- the buffer table (sdx_buffers.h), walked three times with these names
@@ -530,17 +554,52 @@ extern "C" int sdx_set_noise(sdx_handle h, const sdx_noise_attr* observations, c
   return SDX_OK;
 }
 
+extern "C" int sdx_apply_rigid_body_forces(sdx_handle h, const float* forces_dev, const float* torques_dev, int32_t space, void* stream) {
+  if (!h) return SDX_ERR_INVALID;
+  (void)stream;   // nothing to enqueue: the pointers travel with the next physics launch
+  if (space != SDX_SPACE_ENV && space != SDX_SPACE_LOCAL) { h->err = "sdx_apply_rigid_body_forces: space must be SDX_SPACE_ENV or SDX_SPACE_LOCAL"; return SDX_ERR_INVALID; }
+  h->ext_force = forces_dev;
+  h->ext_torque = torques_dev;
+  h->ext_space = space;
+  return SDX_OK;
+}
+extern "C" int sdx_set_force_perturbation(sdx_handle h, const sdx_force_perturb_attr* attr, float* rb_forces_dev, float* prob_dev, void* stream) {
+  if (!h) return SDX_ERR_INVALID;
+  if (!attr || !(attr->force_scale > 0.0f || std::isnan(attr->force_scale))) {   // off (a NaN scale is an error, below)
+    if (h->fp_forces && h->ext_force == h->fp_forces) h->ext_force = nullptr;
+    h->fp_forces = h->fp_prob = nullptr;
+    return SDX_OK;
+  }
+  const sdx_force_perturb_attr& a = *attr;
+  const char* why = nullptr;
+  if (!std::isfinite(a.force_scale) || !std::isfinite(a.prob_lo) || !std::isfinite(a.prob_hi) || !std::isfinite(a.decay) || !std::isfinite(a.decay_interval))
+    why = "force_scale, the probability range, decay and decay_interval must be finite";
+  else if (!(a.prob_lo > 0.0f && a.prob_lo <= a.prob_hi && a.prob_hi <= 1.0f)) why = "the probability range needs 0 < lo <= hi <= 1";
+  else if (!(a.decay > 0.0f && a.decay <= 1.0f)) why = "decay must lie in (0, 1]";
+  else if (!(a.decay_interval > 0.0f)) why = "decay_interval must be > 0";
+  else if (!rb_forces_dev || !prob_dev) why = "rb_forces_dev and prob_dev must not be NULL";
+  else if ((uintptr_t)rb_forces_dev % 16 != 0) why = "rb_forces_dev must be 16-byte aligned";
+  if (why) { h->err = std::string("sdx_set_force_perturbation: ") + why; return SDX_ERR_INVALID; }
+  h->fp = a;
+  h->fp_factor = (float)std::pow((double)a.decay, (double)h->h_const.sc.dt / (double)a.decay_interval);
+  h->fp_forces = rb_forces_dev;
+  h->fp_prob = prob_dev;
+  sdxk_force_perturb(h->d_const, &h->buf, &h->fp, h->fp_factor, h->fp_forces, h->fp_prob, nullptr, SDX_FP_DRAW, (hipStream_t)stream);
+  return check_launch(h, "sdx_set_force_perturbation");
+}
+
 extern "C" int sdx_pre_physics(sdx_handle h, const float* actions_dev, void* stream) {
   if (!h || !actions_dev) return SDX_ERR_INVALID;
   int flags = 1 | 4;
   const float* act = noise_actions(h, actions_dev, &flags, (hipStream_t)stream);
   if (h->buf.dr_on) sdxk_dr_sample(h->d_const, &h->buf, &h->dr, 0, nullptr, (hipStream_t)stream);   // before this step's resets (BT:229-260 runs inside reset_idx)
+  force_perturb_step(h, (hipStream_t)stream);   // (after the sampler: a push is scaled by the brick's mass factor of this step)
   sdxk_pre_physics(h->d_const, &h->buf, act, nullptr, nullptr, flags, (hipStream_t)stream);
   return check_launch(h, "sdx_pre_physics");
 }
 extern "C" int sdx_simulate(sdx_handle h, void* stream) {
   if (!h) return SDX_ERR_INVALID;
-  sdxk_physics(h->d_const, &h->buf, (hipStream_t)stream);
+  physics_step(h, (hipStream_t)stream);
   return check_launch(h, "sdx_simulate");
 }
 extern "C" int sdx_post_physics(sdx_handle h, void* stream) {
@@ -614,6 +673,7 @@ extern "C" int sdx_step(sdx_handle h, const float* actions_dev, void* stream) {
   int targets = 4;                          // k_pre_physics flags of the action -> targets launch
   const float* act = noise_actions(h, actions_dev, &targets, st);
   if (h->buf.dr_on) sdxk_dr_sample(h->d_const, &h->buf, &h->dr, 0, nullptr, st);   // before any reset physics of this step, Orient's / Search's settling launches included
+  force_perturb_step(h, st);
   // the kind's reset event: Orient and Search run theirs here, on the host's reading of the reset flags; GraspSim and InsertSim reset
   // inside the k_pre_physics launch below (flag 1)
   const int kind = h->h_const.sc.task_kind;
@@ -624,7 +684,7 @@ extern "C" int sdx_step(sdx_handle h, const float* actions_dev, void* stream) {
   else targets |= 1;
   if (rc != SDX_OK) return rc;
   sdxk_pre_physics(h->d_const, &h->buf, act, nullptr, nullptr, targets, st);
-  sdxk_physics(h->d_const, &h->buf, st);   // controlFrequencyInv = 1 (EG:18)
+  physics_step(h, st);   // controlFrequencyInv = 1 (EG:18); with the pending external wrench, if any
   if (kind == SDX_TASK_SEARCH && (float)(p0 + 1) >= h->h_const.sc.max_episode_length - 1.0f) {   // SE:992-1019: park the hand, one more step, render
     sdxk_search_set_hand(h->d_const, &h->buf, nullptr, 1, st);
     sdxk_physics(h->d_const, &h->buf, st);
@@ -643,6 +703,7 @@ extern "C" int sdxk_scripted_grasp_actions(sdx_handle h, float* close_state_dev,
 extern "C" int sdx_reset_idx(sdx_handle h, const uint8_t* env_mask_dev, const int32_t* pile_choice_dev, void* stream) {
   if (!h || !env_mask_dev) return SDX_ERR_INVALID;
   if (h->buf.dr_on) sdxk_dr_sample(h->d_const, &h->buf, &h->dr, 0, env_mask_dev, (hipStream_t)stream);   // reset_idx -> apply_randomizations (GS:1395-1396)
+  if (h->fp_forces) sdxk_force_perturb(h->d_const, &h->buf, &h->fp, h->fp_factor, h->fp_forces, h->fp_prob, env_mask_dev, SDX_FP_RESET, (hipStream_t)stream);
   sdxk_pre_physics(h->d_const, &h->buf, nullptr, env_mask_dev, pile_choice_dev, 2, (hipStream_t)stream);
   return check_launch(h, "sdx_reset_idx");
 }

@@ -80,6 +80,12 @@ struct SdxBuf {
   float* dr_grav;          // [3]
   long long* dr_frame;     // [2] frame (physics launches while on), frame of the last gravity randomization
   int32_t* dr_draw;        // [N + 1] samplings of each env so far, [N] = of gravity (the counter of the RNG)
+  // external wrench of ONE physics launch (include/seqdex.h sdx_apply_rigid_body_forces), read by
+  // k_physics<.. | SDX_PHYS_FORCE> only.  The caller's buffers: set in the copy of SdxBuf that travels with that launch, nullptr in the
+  // simulator's own (both nullptr: no wrench, the kernels without the flag run)
+  const float *ext_force, *ext_torque;   // [N, SDX_BODIES, 3] or nullptr
+  float* ext_world;        // [N, SDX_NFREE + SDX_NLINK, 6] scratch: a SDX_SPACE_LOCAL wrench in world axes, written by the first substep for the later ones
+  int32_t ext_space;       // sdx_force_space
 };
 #define SDX_DR_SLOTS 287   // RNG slots per env: 4 x 23 DOF, 2 x 24 link, 2 x 72 brick quantities (284), gravity in slots 284..286 of env 0
 

@@ -23,6 +23,11 @@ void sdxk_render_view(const SdxConst* C, const SdxBuf* B, const sdx_view_desc* v
 void sdxk_dr_defaults(const SdxConst* C, const SdxBuf* B, hipStream_t st);
 void sdxk_dr_sample(const SdxConst* C, const SdxBuf* B, const sdx_dr_desc* desc, int first, const uint8_t* mask, hipStream_t st);
 void sdxk_noise(const SdxConst* C, const SdxBuf* B, const sdx_noise_attr* attr, const float* src, float* dst, int W, int act, hipStream_t st);
+// mode SDX_FP_STEP: the whole rule for one step (resets from reset_buf); SDX_FP_RESET: rows <- 0 and a new probability for the envs of mask
+// (nullptr: every env); SDX_FP_DRAW: a new probability for every env, rows untouched.  factor: decay^(dt / decay_interval)
+enum { SDX_FP_STEP = 0, SDX_FP_RESET = 1, SDX_FP_DRAW = 2 };
+void sdxk_force_perturb(const SdxConst* C, const SdxBuf* B, const sdx_force_perturb_attr* attr, float factor, float* rb_forces, float* prob,
+                        const uint8_t* mask, int mode, hipStream_t st);
 // sdxp_rollout.hip (the PPO library's MFMA linear layer, which Search's RetriGraspTValue in sdx_task.hip borrows)
 void sdxpk_linear(const float* X, const float* W, const float* b, float* Y, int M, int N, int K, int elu_flag, const double* nmean, const double* nvar, hipStream_t st);
 }

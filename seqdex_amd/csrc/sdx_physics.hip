@@ -130,11 +130,15 @@ __device__ __forceinline__ void load_constants(const SdxConst* C, PhysLds& S, in
 }
 
 // ---------------------------------------------------------------- the step kernel
-// NTD = threads | SDX_PHYS_DR.  k_physics<512 | SDX_PHYS_DR> is the domain-randomization variant: drive gains, joint limits, link / brick
+// NTD = threads | SDX_PHYS_DR | SDX_PHYS_FORCE.  k_physics<512 | SDX_PHYS_DR> is the domain-randomization variant: drive gains, joint limits, link / brick
 // masses, friction and gravity come from this env's rows of SDX_T_DR_* instead of the scene constants.  (The flag rides in the low bit of
 // the thread count so that k_physics<512> keeps its symbol and its code: a second template parameter renames the symbol, a __global__
 // wrapper around a shared body changes the default kernel's register allocation.)
 #define SDX_PHYS_DR 1
+// k_physics<.. | SDX_PHYS_FORCE>: the external wrench of include/seqdex.h sdx_apply_rigid_body_forces acts on the
+// free bricks beside gravity and on the robot links beside their velocity-product wrenches.  A second flag bit, for the same reason.
+#define SDX_PHYS_FORCE 2
+#define SDX_PHYS_FLAGS (SDX_PHYS_DR | SDX_PHYS_FORCE)
 // k_physics<.. | SDX_PHYS_DR>: row e of one of the SDX_T_DR_* tensors, addressed from an opaque copy of e at the point of use (nothing is
 // hoisted to the kernel's entry and kept alive over the substeps)
 __device__ __forceinline__ const float* dr_row(const float* base, int e, int width, int off) {
@@ -142,10 +146,39 @@ __device__ __forceinline__ const float* dr_row(const float* base, int e, int wid
   SDX_OPAQUE_S(ee);
   return base + (size_t)ee * width + off;
 }
+// k_physics<.. | SDX_PHYS_FORCE>: the world wrench (F, T) on one body in this substep; false: its rows are all zero and the body is stepped
+// as without the feature (x + 0 would turn a -0 into +0).  body: its row of the caller's tensors [N, SDX_BODIES, 3]; slot: its row of
+// B.ext_world (bricks 0.., links NF..); q: its orientation at the start of the step, used by the first substep of a SDX_SPACE_LOCAL
+// wrench, which leaves the rotated rows in B.ext_world for the later ones (the same lane reads what it wrote).  Addressed like DR_ROW:
+// nothing is kept over the substeps.
+__device__ __forceinline__ bool ext_wrench(const SdxBuf& B, int e, int body, int slot, f4 q, bool first, f3& F, f3& T) {
+  int ee = e;
+  SDX_OPAQUE_S(ee);
+  F = F3(0, 0, 0);
+  T = F3(0, 0, 0);
+  const bool local = B.ext_space == SDX_SPACE_LOCAL;
+  float* w = B.ext_world + ((size_t)ee * (NF + NL) + slot) * 6;
+  if (local && !first) {
+    F = ld3(w);
+    T = ld3(w + 3);
+  } else {
+    const size_t at = ((size_t)ee * SDX_BODIES + body) * 3;
+    if (B.ext_force) F = ld3(B.ext_force + at);
+    if (B.ext_torque) T = ld3(B.ext_torque + at);
+    if (local) {
+      F = qrot(q, F);
+      T = qrot(q, T);
+      st3(w, F);
+      st3(w + 3, T);
+    }
+  }
+  return F.x != 0.0f || F.y != 0.0f || F.z != 0.0f || T.x != 0.0f || T.y != 0.0f || T.z != 0.0f;
+}
 template <int NTD>
-__global__ __launch_bounds__(NTD & ~SDX_PHYS_DR, 2 * (NTD & ~SDX_PHYS_DR) / 256) void k_physics(const SdxConst* __restrict__ C, SdxBuf B) {
-  constexpr int NT = NTD & ~SDX_PHYS_DR;
+__global__ __launch_bounds__(NTD & ~SDX_PHYS_FLAGS, 2 * (NTD & ~SDX_PHYS_FLAGS) / 256) void k_physics(const SdxConst* __restrict__ C, SdxBuf B) {
+  constexpr int NT = NTD & ~SDX_PHYS_FLAGS;
   constexpr bool DR = (NTD & SDX_PHYS_DR) != 0;
+  constexpr bool FORCE = (NTD & SDX_PHYS_FORCE) != 0;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   PhysLds& S = *reinterpret_cast<PhysLds*>(smem);
   // launch order: B.order lists the envs by the cost of their previous step, longest first (k_order below)
@@ -225,6 +258,13 @@ __global__ __launch_bounds__(NTD & ~SDX_PHYS_DR, 2 * (NTD & ~SDX_PHYS_DR) / 256)
       if (tl >= 64) { broad_mask_part<NT>(Cs, S, tl, 0); broad_mask_part<NT>(Cs, S, tl, 1); }
     } else if (tl < 64) {
       if (sub != 0) { fk_wave0(Cs, S, tl, false, true, nullptr, DR); WAVE_SIGNAL(&S.fkflag, sub); }   // (the robot boxes are placed: part 1 of the mask may start)
+      if (FORCE) {   // the external wrench of link tl enters where its inertial wrench does: (lF, lN) -= (F, T); nothing but the drive below reads them
+        if (tl > 0 && tl < NL) {
+          f3 F, T;
+          if (ext_wrench(B, e, tl, NF + tl, ld4(S.lq[tl]), sub == 0, F, T)) { st3(S.lF[tl], ld3(S.lF[tl]) - F); st3(S.lN[tl], ld3(S.lN[tl]) - T); }
+        }
+        WAVE_SYNC();
+      }
       if (tl < ND) {
         const float* drow = DR_ROW(dr_dof, 4 * ND, 0);
         const float t = DR ? drow[tl] * (S.tgt[tl] - S.q[tl]) - (drow[ND + tl] + h * drow[tl]) * S.qd[tl]   // (drow: kp, kd rows)
@@ -267,6 +307,16 @@ __global__ __launch_bounds__(NTD & ~SDX_PHYS_DR, 2 * (NTD & ~SDX_PHYS_DR) / 256)
           S.bv[i][0] += g0 * h; S.bv[i][1] += g1 * h; S.bv[i][2] += g2 * h;
         }
         else { S.bv[i][0] += scl.gravity[0] * h; S.bv[i][1] += scl.gravity[1] * h; S.bv[i][2] += scl.gravity[2] * h; }
+        if (FORCE) {   // v += F h / m, w += R diag(1 / I) R^T T h: the solver's inverse mass, and its inverse inertia bim x tii at this substep's orientation
+          const f4 q = ld4(S.bq[i]);
+          f3 F, T;
+          if (ext_wrench(B, e, SDX_BODY_BRICK0 + i, i, q, sub == 0, F, T)) {
+            const float s = S.bim[i] * h;
+            const f3 ii = ld3(S.tii[S.btype[i]]), l = qrot(qconj(q), T);
+            st3(S.bv[i], ld3(S.bv[i]) + F * s);
+            st3(S.bw[i], ld3(S.bw[i]) + qrot(q, F3(l.x * ii.x, l.y * ii.y, l.z * ii.z) * s));
+          }
+        }
       }
       // later substeps: both parts of the broadphase mask beside wave 0's FK + drive (the first substep had them beside FK and the factorisation)
       if (sub != 0 && !ABL(32)) {
@@ -432,13 +482,18 @@ static void physics_init() {
     done = true;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_physics<512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PhysLds));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_physics<512 | SDX_PHYS_DR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PhysLds));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_physics<512 | SDX_PHYS_FORCE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PhysLds));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_physics<512 | SDX_PHYS_DR | SDX_PHYS_FORCE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PhysLds));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_kinematics), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PhysLds));
   }
 }
 extern "C" int sdxk_physics_threads() { return 512; }
 extern "C" void sdxk_physics(const SdxConst* C, const SdxBuf* B, hipStream_t st) {
   physics_init();
-  if (B->dr_on) hipLaunchKernelGGL(k_physics<512 | SDX_PHYS_DR>, dim3(B->N), dim3(512), sizeof(PhysLds), st, C, *B);   // domain randomization on
+  const bool force = B->ext_force || B->ext_torque;   // an external wrench rides with this launch (sdx_apply_rigid_body_forces)
+  if (force && B->dr_on) hipLaunchKernelGGL(k_physics<512 | SDX_PHYS_DR | SDX_PHYS_FORCE>, dim3(B->N), dim3(512), sizeof(PhysLds), st, C, *B);
+  else if (force) hipLaunchKernelGGL(k_physics<512 | SDX_PHYS_FORCE>, dim3(B->N), dim3(512), sizeof(PhysLds), st, C, *B);
+  else if (B->dr_on) hipLaunchKernelGGL(k_physics<512 | SDX_PHYS_DR>, dim3(B->N), dim3(512), sizeof(PhysLds), st, C, *B);   // domain randomization on
   else hipLaunchKernelGGL(k_physics<512>, dim3(B->N), dim3(512), sizeof(PhysLds), st, C, *B);
   if (B->order && B->cost) hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, st, *B);
 }

@@ -1,5 +1,6 @@
 // sdx_randomize.hip — the samplers of domain randomization and of observation / action noise (include/seqdex.h sdx_set_randomization,
-// sdx_set_noise): kernels with pinned numerics and their launchers.  Argument checks and call order: sdx_capi.hip.
+// sdx_set_noise) and of the random pushes on the target brick (sdx_set_force_perturbation; section 21): kernels with
+// pinned numerics and their launchers.  Argument checks and call order: sdx_capi.hip.
 #include "sdx_kernels.h"
 
 // ---------------------------------------------------------------- domain randomization (include/seqdex.h sdx_set_randomization,
@@ -226,4 +227,77 @@ __global__ __launch_bounds__(256) void k_noise(const SdxConst* __restrict__ C, S
 extern "C" void sdxk_noise(const SdxConst* C, const SdxBuf* B, const sdx_noise_attr* attr, const float* src, float* dst, int W, int act, hipStream_t st) {
   const long long threads = (long long)B->N * ((W + 3) / 4);
   hipLaunchKernelGGL(k_noise, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, C, *B, *attr, src, dst, W, act);
+}
+
+// ---------------------------------------------------------------- random pushes on the target brick (include/seqdex.h
+// sdx_set_force_perturbation): the reference's rule (morb.py:1495-1516) on the caller's rb_forces [N, SDX_BODIES, 3] and
+// prob [N].  Stateless draws: sdx_hash(seed ^ SDX_FORCE_TAG, env * 256 + slot, step_count); slot 0 the push decision, 1 z_x / z_y, 2 z_z,
+// 3 the probability.
+#define SDX_FORCE_TAG 0xF0CEull
+#define SDX_FORCE_ROW (SDX_BODIES * 3)
+__device__ __forceinline__ uint64_t force_hash(uint64_t seed, int e, int slot, uint64_t step) {
+  return sdx_hash(seed ^ SDX_FORCE_TAG, (uint64_t)e * 256 + (uint64_t)slot, step);
+}
+// exp((log lo - log hi) u + log hi) (GS:1519-1520), in double, rounded once
+__device__ __forceinline__ float force_prob(const sdx_force_perturb_attr& a, uint64_t seed, int e, uint64_t step) {
+#pragma clang fp contract(off)
+  const double llo = log((double)a.prob_lo), lhi = log((double)a.prob_hi);
+  const double t = (llo - lhi) * (double)dr_u(force_hash(seed, e, 3, step), 0);
+  return (float)exp(t + lhi);
+}
+// One thread per group of 4 consecutive floats of the flat tensor (a group may span two envs: 495 floats per env): one 16-byte load and
+// store per thread, the last group of an N x 495 that is no multiple of 4 goes float by float.  Per element, in the rule's order: reset
+// (-> 0), decay (x factor), push (the three elements of the target brick's row: the decision is the same hash for all three).  The
+// element (e, 0) also writes prob[e] when env e draws a new one; only envs that do NOT draw read prob[e].
+__global__ __launch_bounds__(256) void k_force_perturb(const SdxConst* __restrict__ C, SdxBuf B, sdx_force_perturb_attr a, float factor,
+                                                       float* __restrict__ F, float* __restrict__ prob, const uint8_t* __restrict__ mask, int mode) {
+#pragma clang fp contract(off)
+  const long long total = (long long)B.N * SDX_FORCE_ROW;
+  const long long i0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i0 >= total) return;
+  const int n = total - i0 < 4 ? (int)(total - i0) : 4;
+  const uint64_t step = (uint64_t)B.step_count[0];
+  const sdx_scene_desc& sc = C->sc;
+  float x[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (mode != SDX_FP_DRAW) {
+    if (n == 4) {
+      const f4v v = *reinterpret_cast<const f4v*>(F + i0);
+      x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+    } else {
+      for (int k = 0; k < n; ++k) x[k] = F[i0 + k];
+    }
+  }
+  for (int k = 0; k < n; ++k) {
+    const int e = (int)((i0 + k) / SDX_FORCE_ROW), c = (int)((i0 + k) - (long long)e * SDX_FORCE_ROW);
+    const bool reset = mode == SDX_FP_STEP ? B.reset[e] != 0 : (mode == SDX_FP_RESET && (mask ? mask[e] != 0 : true));
+    if (reset) x[k] = 0.0f;
+    if (mode == SDX_FP_STEP) {
+      x[k] *= factor;
+      const int segb = seg_actor(e) - SDX_ACTOR_BRICK0;
+      if (c / 3 == SDX_BODY_BRICK0 + segb) {
+        const float p = reset ? force_prob(a, B.seed, e, step) : prob[e];
+        if (dr_u(force_hash(B.seed, e, 0, step), 0) < p) {
+          const int r = c % 3;
+          const float z = noise_normal(force_hash(B.seed, e, r < 2 ? 1 : 2, step), r == 1);
+          float m = sc.brick_mass[sc.brick_type[segb]] * sc.seg_mass_scale;   // the mass k_physics gives this brick (load_constants)
+          if (B.dr_on) m *= B.dr_brick[(size_t)e * 2 * SDX_NFREE + segb];
+          x[k] = z * m * a.force_scale;
+        }
+      }
+    }
+    if (c == 0 && (reset || mode == SDX_FP_DRAW)) prob[e] = force_prob(a, B.seed, e, step);
+  }
+  if (mode == SDX_FP_DRAW) return;
+  if (n == 4) {
+    f4v v;
+    v.x = x[0]; v.y = x[1]; v.z = x[2]; v.w = x[3];
+    *reinterpret_cast<f4v*>(F + i0) = v;
+  } else {
+    for (int k = 0; k < n; ++k) F[i0 + k] = x[k];
+  }
+}
+extern "C" void sdxk_force_perturb(const SdxConst* C, const SdxBuf* B, const sdx_force_perturb_attr* attr, float factor, float* rb_forces, float* prob,
+                                   const uint8_t* mask, int mode, hipStream_t st) {
+  const long long groups = ((long long)B->N * SDX_FORCE_ROW + 3) / 4;
+  hipLaunchKernelGGL(k_force_perturb, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, C, *B, *attr, factor, rb_forces, prob, mask, mode);
 }

@@ -328,6 +328,46 @@ class SdxSim:
         self._check(self.lib.sdx_set_noise(self.h, ptr[0], ptr[1], self._stream_or_none()))
         return report
 
+    # ------------------------------------------------------------------ external wrenches (include/seqdex.h)
+    def _wrench_tensor(self, t, what, shape):
+        if t is None:
+            return None
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() \
+                or t.device.type != self.device.type or (t.device.type == "cuda" and t.device.index not in (None, self.device.index or 0)):
+            raise ValueError("%s: expected a contiguous float32 tensor of shape %s on %s, got %s" % (
+                what, shape, self.device, "%s %s on %s" % (t.dtype, tuple(t.shape), t.device) if torch.is_tensor(t) else type(t).__name__))
+        return t
+
+    def apply_rigid_body_forces(self, forces=None, torques=None, space="env"):
+        """gym.apply_rigid_body_force_tensors: forces / torques float32 [N, BODIES, 3] indexed like RB (either may be None) act on the NEXT
+        physics launch (simulate() or step()) only; at the centre of mass, in the env's axes ("env") or the body's ("local", rotated once
+        with the start-of-step orientation).  A second call before that launch replaces the wrench, both None clears it.  Nothing is
+        enqueued: the tensors are read by that launch, so they are kept referenced here until it has been enqueued."""
+        spaces = {"env": _abi.SPACE_ENV, "local": _abi.SPACE_LOCAL}
+        if space not in spaces and space not in spaces.values():
+            raise ValueError("apply_rigid_body_forces: space must be 'env' or 'local', got %r" % (space,))
+        shape = (self.num_envs, _abi.BODIES, 3)
+        f = self._wrench_tensor(forces, "apply_rigid_body_forces: forces", shape)
+        t = self._wrench_tensor(torques, "apply_rigid_body_forces: torques", shape)
+        self._wrench = (f, t)
+        self._check(self.lib.sdx_apply_rigid_body_forces(self.h, C.c_void_p(f.data_ptr()) if f is not None else None,
+                                                         C.c_void_p(t.data_ptr()) if t is not None else None,
+                                                         C.c_int32(spaces.get(space, space)), self._stream_or_none()))
+
+    def set_force_perturbation(self, attr, rb_forces=None, prob=None):
+        """random pushes on the target brick (sdx_set_force_perturbation): attr an _abi.ForcePerturbAttr, or None / force_scale <= 0 for
+        off; rb_forces float32 [N, BODIES, 3] and prob float32 [N] are the CALLER'S tensors (the task's rb_forces / random_force_prob),
+        read and written by every step() / pre_physics() / reset_idx() while on; they are kept referenced here.  Not part of a snapshot."""
+        if attr is None:
+            self._check(self.lib.sdx_set_force_perturbation(self.h, None, None, None, self._stream_or_none()))
+            self._perturb = None
+            return
+        f = self._wrench_tensor(rb_forces, "set_force_perturbation: rb_forces", (self.num_envs, _abi.BODIES, 3))
+        p = self._wrench_tensor(prob, "set_force_perturbation: prob", (self.num_envs,))
+        self._check(self.lib.sdx_set_force_perturbation(self.h, C.byref(attr), C.c_void_p(f.data_ptr()) if f is not None else None,
+                                                        C.c_void_p(p.data_ptr()) if p is not None else None, self._stream_or_none()))
+        self._perturb = (attr, f, p) if attr.force_scale > 0 else None
+
     # ------------------------------------------------------------------ sim snapshots (include/seqdex.h sdx_state_*, DESIGN.md section 20)
     def _stream_or_none(self):
         return _stream_ptr(self.device) if self.device.type == "cuda" else None

@@ -101,6 +101,20 @@ class BlockAssemblyGraspSim:
             # the `observations` / `actions` blocks, which BaseTask.step applies for every task (BT:131-132,149-150): OBS_CLAMPED (what the
             # agent is handed, VR:171) carries the observation noise, ACTIONS the action noise; obs_buf stays the clean row
             self.randomization_report["noise"] = s.set_noise(self.randomization_params)
+        # random pushes on the target brick (GS:129-132,347-352; the rule of utils/morb.py:1495-1516 runs on the device inside sdx_step):
+        # the task owns the two tensors, as in the reference; extra forces of a script are added into rb_forces
+        self.force_scale = float(env.get("forceScale", 0.0))
+        self.force_prob_range = [float(v) for v in env.get("forceProbRange", [0.001, 0.1])]
+        self.force_decay = float(env.get("forceDecay", 0.99))
+        self.force_decay_interval = float(env.get("forceDecayInterval", 0.08))
+        if len(self.force_prob_range) != 2:
+            raise ValueError("env.forceProbRange: expected [lo, hi], got %r" % (env.get("forceProbRange"),))
+        self.rb_forces = torch.zeros(self.num_envs, _abi.BODIES, 3, dtype=torch.float32, device=self.device)
+        self.random_force_prob = torch.zeros(self.num_envs, dtype=torch.float32, device=self.device)
+        if self.force_scale > 0.0:
+            a = _abi.ForcePerturbAttr(self.force_scale, self.force_prob_range[0], self.force_prob_range[1], self.force_decay,
+                                      self.force_decay_interval)
+            s.set_force_perturbation(a, self.rb_forces, self.random_force_prob)
 
     # ------------------------------------------------------------------ BaseTask.step, BT:130-150
     def step(self, actions):

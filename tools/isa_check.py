@@ -3,8 +3,9 @@ solver's iteration loop (the ISA between the source lines of the loop head and o
 per-pass stage functions the loop calls: the lines of the same file between the comments `// isa_check: loop stage begin` and
 `// isa_check: loop stage end` (any number of such ranges).  The loop is looked for in sdx_physics.hip and the sdx_phys_*.h it includes;
 code inlined from any other line of those files is not part of the loop.
-usage: python tools/isa_check.py [--randomize] [extra hipcc flags...]      (cross-compiles; no GPU needed)
---randomize: the same report for the domain-randomization variant k_physics<512 | SDX_PHYS_DR> (= k_physics<513>)"""
+usage: python tools/isa_check.py [--randomize] [--force] [extra hipcc flags...]      (cross-compiles; no GPU needed)
+--randomize: the same report for the domain-randomization variant k_physics<512 | SDX_PHYS_DR> (= k_physics<513>)
+--force: ... for the external-wrench variant k_physics<512 | SDX_PHYS_FORCE> (514; with --randomize 515)"""
 import os
 import re
 import subprocess
@@ -17,7 +18,11 @@ SRC = os.path.join(CSRC, "sdx_physics.hip")
 RANDOMIZE = "--randomize" in sys.argv
 if RANDOMIZE:
     sys.argv.remove("--randomize")
-KERN = "_Z9k_physicsILi513EEvPK8SdxConst6SdxBuf" if RANDOMIZE else "_Z9k_physicsILi512EEvPK8SdxConst6SdxBuf"
+FORCE = "--force" in sys.argv
+if FORCE:
+    sys.argv.remove("--force")
+TAG = "k_physicsILi%dE" % (512 + (1 if RANDOMIZE else 0) + (2 if FORCE else 0))
+KERN = "_Z9%sEvPK8SdxConst6SdxBuf" % TAG
 
 # the unit's files: the .hip and the private headers it includes; the one with the loop markers is where the loop's lines are counted
 UNIT = ["sdx_physics.hip"] + re.findall(r'^#include "(sdx_phys_\w+\.h)"', open(SRC).read(), flags=re.M)
@@ -35,7 +40,7 @@ with tempfile.TemporaryDirectory() as td:
            "-Rpass-analysis=kernel-resource-usage", "-save-temps=obj", "-c", SRC, "-o", os.path.join(td, "p.o")] + sys.argv[1:]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=td)
     rem = r.stderr
-    blk = rem[rem.index("k_physicsILi513" if RANDOMIZE else "k_physicsILi512"):]
+    blk = rem[rem.index(TAG):]
     for key in ("VGPRs:", "ScratchSize [bytes/lane]:", "SGPRs Spill:", "VGPRs Spill:", "Occupancy [waves/SIMD]:"):
         m = re.search(re.escape(key) + r"\s*(\d+)", blk)
         print(key, m.group(1) if m else "?")

@@ -8,7 +8,9 @@ next to its verdict, not as dropped and added.  Comments, debug / .loc / .file l
     python tools/kernel_identity.py /tmp/parent/seqdex_amd/csrc [--out profiles/kernel_identity.txt] [--work DIR] [--jobs 8] [--flags "-DSDX_PHASE_CLOCK"]
 
 --flags: extra hipcc flags appended on both sides (the profiling builds: "-DSDX_PHASE_CLOCK", "-DSDX_PHASE_CLOCK -DSDX_LANE_CLOCK"); give
-each set of flags a --work of its own.  Cross-compiles; no GPU needed.  --work keeps the assembly between runs (a side is recompiled when one of its sources is newer).  Exit 1 on a difference."""
+each set of flags a --work of its own.  --ignore-kernarg-size: the .amdhsa_kernarg_size line is left out of the comparison and a kernel whose
+size changed says so next to its verdict (a struct passed by value - SdxBuf - grew at its end: the offsets of everything in front of the
+new fields, and so every instruction, stay what they were).  Cross-compiles; no GPU needed.  --work keeps the assembly between runs (a side is recompiled when one of its sources is newer).  Exit 1 on a difference."""
 import argparse
 import concurrent.futures
 import glob
@@ -44,6 +46,9 @@ def compile_one(csrc, name, out, extra=()):
     return asm[0]
 
 
+KERNARG = re.compile(r"^\.amdhsa_kernarg_size (\d+)$", flags=re.M)
+
+
 def kernels(asm):
     """{kernel symbol: normalised text from its label to .end_amdhsa_kernel}"""
     lines = open(asm).read().split("\n")
@@ -70,6 +75,7 @@ def main():
     ap.add_argument("--work", default="")
     ap.add_argument("--jobs", type=int, default=8)
     ap.add_argument("--flags", default="", help="extra hipcc flags for every file of both sides")
+    ap.add_argument("--ignore-kernarg-size", action="store_true", help="compare everything but .amdhsa_kernarg_size; report the sizes that changed")
     argv = sys.argv[1:]
     if "--flags" in argv[:-1]:   # (argparse takes a lone value that begins with "-" for an option: hand it over as --flags=VALUE)
         i = argv.index("--flags")
@@ -92,18 +98,21 @@ def main():
         o, t = [fk for fk in left_o if fk[1] == sym], [fk for fk in left_t if fk[1] == sym]
         pairs += [(o[0], t[0])] if len(o) == 1 and len(t) == 1 else [(fk, None) for fk in o] + [(None, fk) for fk in t]
     report, bad, nmoved = [], 0, 0
+    strip = (lambda text: KERNARG.sub(".amdhsa_kernarg_size -", text)) if a.ignore_kernarg_size else (lambda text: text)
     for o, t in sorted(pairs, key=lambda p: p[1] or p[0]):
-        verdict = "identical" if o and t and ko[o] == kt[t] else ("DIFFERS" if o and t else ("ADDED" if t else "DROPPED"))
+        verdict = "identical" if o and t and strip(ko[o]) == strip(kt[t]) else ("DIFFERS" if o and t else ("ADDED" if t else "DROPPED"))
         bad += verdict != "identical"
         moved = "   moved %s.hip -> %s.hip" % (o[0], t[0]) if o and t and o[0] != t[0] else ""
         nmoved += bool(moved)
+        if verdict == "identical" and ko[o] != kt[t]:
+            moved += "   kernarg size %s -> %s" % (KERNARG.search(ko[o]).group(1), KERNARG.search(kt[t]).group(1))
         report.append("%-18s %-10s %s%s" % ((t or o)[0] + ".hip", verdict, (t or o)[1], moved))
     report.append("%d kernels, %d not identical, %d moved" % (len(report), bad, nmoved))
     text = "\n".join(report) + "\n"
     sys.stdout.write(text)
     if a.out:
         with open(a.out, "w") as fh:
-            fh.write("# python tools/kernel_identity.py <csrc of the parent commit>: gfx950 instruction text + .amdhsa_* resources per kernel, parent vs this tree%s\n" % (a.flags and "; extra flags on both sides: " + a.flags) + text)
+            fh.write("# python tools/kernel_identity.py <csrc of the parent commit>: gfx950 instruction text + .amdhsa_* resources per kernel, parent vs this tree%s%s\n" % (a.flags and "; extra flags on both sides: " + a.flags, "; .amdhsa_kernarg_size not compared (--ignore-kernarg-size)" if a.ignore_kernarg_size else "") + text)
     return 1 if bad else 0
 
 
