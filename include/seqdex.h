@@ -439,6 +439,26 @@ int sdx_set_noise(sdx_handle h, const sdx_noise_attr* observations, const sdx_no
 typedef enum { SDX_SPACE_ENV = 0, SDX_SPACE_LOCAL = 1 } sdx_force_space;
 int sdx_apply_rigid_body_forces(sdx_handle h, const float* forces_dev, const float* torques_dev, int32_t space, void* stream);
 
+/* Joint torques (gym.set_dof_actuation_force_tensor with DOF_MODE_EFFORT per DOF).  dof_forces_dev: caller-owned
+ * device f32 [N, SDX_NDOF] or NULL; drive_off_mask bit j: the PD drive of DOF j is off (a bit >= SDX_NDOF: SDX_ERR_INVALID).  The rules of
+ * sdx_apply_rigid_body_forces: nothing is enqueued (`stream` is unused), pointer and mask travel by value with the NEXT physics launch -
+ * sdx_simulate, or sdx_step's own, not the settling launches - and are then forgotten; a second call before it REPLACES them, NULL with
+ * mask 0 clears them; the buffer must stay alive and unchanged until that launch has run.  A pending slot of its own: neither
+ * sdx_apply_rigid_body_forces nor the sampler of sdx_set_force_perturbation touches it.  Not part of a snapshot.
+ *   torque    every substep tau_j = (bit j ? 0 : clamp(PD_j, +-effort_j)) + clamp(u_j, +-effort_j) - tc_j, u held constant over the substeps.
+ *   off       a DOF whose drive is off also drops the implicit terms h kd + h^2 kp from the diagonal of H (the env's SDX_T_DR_DOF gains
+ *             while randomization is on); its armature, joint limits and velocity limit keep applying.
+ *   zero      a DOF whose u_j is zero (of either sign) and whose bit is clear is stepped bit for bit as without the call. */
+int sdx_apply_dof_forces(sdx_handle h, const float* dof_forces_dev, uint32_t drive_off_mask, void* stream);
+/* Joint-space dynamics of the robot (acquire_mass_matrix_tensor, the DOF force tensor) from the CURRENT SDX_T_DOF and
+ * SDX_T_TARGETS: one launch on `stream`, part of no step.  Caller-owned device buffers, any of them NULL (all three: SDX_ERR_INVALID):
+ *   mass_dev  f32 [N, SDX_NDOF, SDX_NDOF]  M(q) + armature, symmetric bit for bit, without the implicit PD terms of the step's H
+ *   bias_dev  f32 [N, SDX_NDOF]            C(q, qd) qd (no gravity acts on the robot): the step's tc
+ *   drive_dev f32 [N, SDX_NDOF]            the clamped PD torque that the first substep of the next launch would apply (h = dt / substeps;
+ *                                          the drive-off mask is not applied)
+ * While randomization is on, the gains are the env's SDX_T_DR_DOF rows and masses and inertias carry the SDX_T_DR_LINK factors, as in the step. */
+int sdx_dof_dynamics(sdx_handle h, float* mass_dev, float* bias_dev, float* drive_dev, void* stream);
+
 /* Random pushes on the target brick (the reference's forceScale / forceProbRange / forceDecay / forceDecayInterval, morb.py:1495-1516;
  * DESIGN.md section 21).  rb_forces_dev f32 [N, SDX_BODIES, 3] and prob_dev f32 [N] are CALLER-OWNED device buffers (the task's rb_forces
  * and random_force_prob): they are read and written by the launches of the calls that follow, must stay alive while the sampler is on,
@@ -491,7 +511,7 @@ int sdx_render_view(sdx_handle h, const sdx_view_desc* view, const int32_t* env_
  * statistics and SDX_T_CONS_SUCCESSES, SDX_T_DR_GRAVITY, SDX_T_DR_FRAME and gravity's draw counter.
  * NOT part of any snapshot: the logs (the harvest, pile and T-value rings with their counts and keys, SDX_T_CONTACT_STATS, SDX_T_DEBUG),
  * the launch-order hints of k_physics, and configuration (loaded piles, T-value weights, the randomization descriptor and whether it is
- * on), a pending external wrench and the caller-owned buffers of sdx_set_force_perturbation (the task's rb_forces and
+ * on), a pending external wrench, pending joint actuation (sdx_apply_dof_forces) and the caller-owned buffers of sdx_set_force_perturbation (the task's rb_forces and
  * random_force_prob: copy them beside the snapshot).  A restore_all rewinds the step counter: ring rows appended afterwards can REPEAT the keys of rows appended before the restore.
  * Env classes: a row may only be put into an env of the class it came from - env & 7 (the target brick), and additionally env % 3 for
  * InsertSim (the base plate and the insertion site); the RNG keys stay with the destination env.  Each row records its source env.

@@ -118,6 +118,7 @@ SDX_EXPORTS = ["sdx_create", "sdx_destroy", "sdx_tensor", "sdx_load_initial_stat
                "sdx_step", "sdx_pre_physics", "sdx_simulate", "sdx_post_physics", "sdx_compute_observations",
                "sdx_reset_idx", "sdx_set_indexed", "sdx_refresh_kinematics", "sdx_render_segmentation", "sdx_num_envs", "sdx_last_error",
                "sdx_set_randomization", "sdx_set_noise", "sdx_render_view", "sdx_apply_rigid_body_forces", "sdx_set_force_perturbation",
+               "sdx_apply_dof_forces", "sdx_dof_dynamics",
                "sdx_state_create", "sdx_state_destroy", "sdx_state_save", "sdx_state_restore", "sdx_state_save_all", "sdx_state_restore_all",
                "sdx_state_clone", "sdx_state_stats",
                "sdxp_create", "sdxp_destroy", "sdxp_tensor", "sdxp_param_count", "sdxp_act", "sdxp_store_rewards",
@@ -156,6 +157,8 @@ def load_library():
     lib.sdx_render_view.argtypes = [vp, C.POINTER(ViewDesc), vp, i32, vp, vp, vp, vp]
     lib.sdx_apply_rigid_body_forces.argtypes = [vp, vp, vp, i32, vp]
     lib.sdx_set_force_perturbation.argtypes = [vp, C.POINTER(ForcePerturbAttr), vp, vp, vp]
+    lib.sdx_apply_dof_forces.argtypes = [vp, vp, C.c_uint32, vp]
+    lib.sdx_dof_dynamics.argtypes = [vp, vp, vp, vp, vp]
     lib.sdx_state_create.argtypes = [vp, i32, C.POINTER(vp)]
     lib.sdx_state_destroy.argtypes = [vp]
     lib.sdx_state_save.argtypes = [vp, vp, vp, vp, i32, vp]

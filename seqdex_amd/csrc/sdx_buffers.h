@@ -91,8 +91,8 @@
   X(tvt_w, search ? 1024 * 652 + 1024 + 512 * 1024 + 512 + 128 * 512 + 128 + 2 * 128 + 2 : 0, CONFIG, 0, NO_TENSOR)
 
 // Compile-time check: a row whose class is none of these does not compile, and every pointer of SdxBuf but dr_on (an alias of dr_draw) and
-// ext_force / ext_torque (the caller's buffers of one launch) has a row.
+// ext_force / ext_torque / dof_force (the caller's buffers of one launch) has a row.
 enum SdxSnap { SDX_SNAP_ENV = 1, SDX_SNAP_ENV_WARM, SDX_SNAP_GLOBAL, SDX_SNAP_LOG, SDX_SNAP_SCRATCH, SDX_SNAP_CONFIG };
 #define SDX_BUF_ROW_CLASS(field, count, snap, n, tensor) SDX_SNAP_##snap,
 static constexpr SdxSnap sdx_buf_snap[] = {SDX_BUFFERS(SDX_BUF_ROW_CLASS)};
-static_assert(sizeof(SdxBuf) == 48 /* its scalars and padding */ + sizeof(void*) * (sizeof(sdx_buf_snap) / sizeof(sdx_buf_snap[0]) + 3), "sdx_buffers.h: a pointer of SdxBuf has no row in SDX_BUFFERS, or a row no pointer (or SdxBuf's scalars changed: then adjust the 48)");
+static_assert(sizeof(SdxBuf) == 48 /* its scalars and padding */ + sizeof(void*) * (sizeof(sdx_buf_snap) / sizeof(sdx_buf_snap[0]) + 4), "sdx_buffers.h: a pointer of SdxBuf has no row in SDX_BUFFERS, or a row no pointer (or SdxBuf's scalars changed: then adjust the 48)");

@@ -28,6 +28,10 @@ struct sdx_sim {
   // sdx_apply_rigid_body_forces: the wrench of the next physics launch (the caller's buffers; both nullptr: none pending)
   const float *ext_force = nullptr, *ext_torque = nullptr;
   int32_t ext_space = SDX_SPACE_ENV;
+  // sdx_apply_dof_forces: the actuation torques and the drives that are off in the next physics launch (a slot of its own: neither
+  // sdx_apply_rigid_body_forces nor the force-perturbation sampler touches it)
+  const float* dof_force = nullptr;
+  uint32_t dof_off = 0;
   // sdx_set_force_perturbation: on while fp_forces != nullptr; fp_factor = decay^(dt / decay_interval)
   sdx_force_perturb_attr fp{};
   float fp_factor = 1.0f;
@@ -103,13 +107,15 @@ static void post_physics_step(sdx_sim* h, hipStream_t st) {
   if (h->noise_obs.distribution != SDX_DR_NONE) sdxk_noise(h->d_const, &h->buf, &h->noise_obs, h->buf.obs, h->buf.obs_c, h->buf.obs_w, 0, st);
 }
 
-// the physics launch a pending external wrench applies to (sdx_simulate; sdx_step's own, not the settling launches of a reset event): the
+// the physics launch a pending external wrench and pending joint actuation apply to (sdx_simulate; sdx_step's own, not the settling launches of a reset event): the
 // caller's pointers travel by value in that launch's copy of the buffer table, and the wrench is forgotten
 static void physics_step(sdx_sim* h, hipStream_t st) {
-  if (!h->ext_force && !h->ext_torque) { sdxk_physics(h->d_const, &h->buf, st); return; }
+  if (!h->ext_force && !h->ext_torque && !h->dof_force && !h->dof_off) { sdxk_physics(h->d_const, &h->buf, st); return; }
   SdxBuf b = h->buf;
   b.ext_force = h->ext_force; b.ext_torque = h->ext_torque; b.ext_space = h->ext_space;
-  h->ext_force = h->ext_torque = nullptr;
+  b.dof_force = h->dof_force; b.dof_off = h->dof_off;
+  h->ext_force = h->ext_torque = h->dof_force = nullptr;
+  h->dof_off = 0;
   sdxk_physics(h->d_const, &b, st);
 }
 // the random pushes of this step (sdx_set_force_perturbation), before the step's resets clear the flags: the task's rb_forces become the
@@ -562,6 +568,20 @@ extern "C" int sdx_apply_rigid_body_forces(sdx_handle h, const float* forces_dev
   h->ext_torque = torques_dev;
   h->ext_space = space;
   return SDX_OK;
+}
+extern "C" int sdx_apply_dof_forces(sdx_handle h, const float* dof_forces_dev, uint32_t drive_off_mask, void* stream) {
+  if (!h) return SDX_ERR_INVALID;
+  (void)stream;   // nothing to enqueue: pointer and mask travel with the next physics launch
+  if (drive_off_mask >> SDX_NDOF) { h->err = "sdx_apply_dof_forces: drive_off_mask has a bit beyond DOF 22"; return SDX_ERR_INVALID; }
+  h->dof_force = dof_forces_dev;
+  h->dof_off = drive_off_mask;
+  return SDX_OK;
+}
+extern "C" int sdx_dof_dynamics(sdx_handle h, float* mass_dev, float* bias_dev, float* drive_dev, void* stream) {
+  if (!h) return SDX_ERR_INVALID;
+  if (!mass_dev && !bias_dev && !drive_dev) { h->err = "sdx_dof_dynamics: mass_dev, bias_dev and drive_dev are all NULL"; return SDX_ERR_INVALID; }
+  sdxk_dof_dynamics(h->d_const, &h->buf, mass_dev, bias_dev, drive_dev, (hipStream_t)stream);
+  return check_launch(h, "sdx_dof_dynamics");
 }
 extern "C" int sdx_set_force_perturbation(sdx_handle h, const sdx_force_perturb_attr* attr, float* rb_forces_dev, float* prob_dev, void* stream) {
   if (!h) return SDX_ERR_INVALID;

@@ -86,6 +86,9 @@ struct SdxBuf {
   const float *ext_force, *ext_torque;   // [N, SDX_BODIES, 3] or nullptr
   float* ext_world;        // [N, SDX_NFREE + SDX_NLINK, 6] scratch: a SDX_SPACE_LOCAL wrench in world axes, written by the first substep for the later ones
   int32_t ext_space;       // sdx_force_space
+  // joint actuation of ONE physics launch (include/seqdex.h sdx_apply_dof_forces), carried and read like the wrench
+  uint32_t dof_off;        // bit j: the PD drive of dof j is off
+  const float* dof_force;  // [N, SDX_NDOF] or nullptr
 };
 #define SDX_DR_SLOTS 287   // RNG slots per env: 4 x 23 DOF, 2 x 24 link, 2 x 72 brick quantities (284), gravity in slots 284..286 of env 0
 

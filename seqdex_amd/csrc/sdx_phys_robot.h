@@ -9,7 +9,8 @@ __device__ __forceinline__ f3 inertia_mul(f4 q, const float* I, f3 x) {
 }
 // link twists from qd, on wave 0: w_k = sum_j a_j qd_j, v_k = sum_j (a_j qd_j) x (p_k - p_j) over the dofs j on the path (<= 11 of them:
 // 7 arm joints + 4 of one finger).  Fixed trip count, no branches: an exhausted path reads dof ND, whose velocity slot is zero
-__device__ __forceinline__ void twists_wave0(PhysLds& S, int tid) {
+template <class LDS>
+__device__ __forceinline__ void twists_wave0(LDS& S, int tid) {
   if (tid > 0 && tid < NL) {
     f3 w = F3(0, 0, 0), v = F3(0, 0, 0);
     const f3 pk = ld3(S.bp[NF + tid]);
@@ -48,7 +49,9 @@ __device__ __forceinline__ void twists_wave0(PhysLds& S, int tid) {
 // acceleration, fixed base, no gravity on the robot).  with_bias: the velocity-product wrenches the drive needs; with_inertia: the world
 // inertia tensors the mass matrix needs.
 // lmf: scale link masses and inertias by S.lmf (domain randomization; false = the scene's masses and inertias)
-__device__ __forceinline__ void fk_wave0(const SdxConst* C, PhysLds& S, int tid, bool with_inertia, bool with_bias, long long* dbg = nullptr,
+// LDS: PhysLds, or the rows of it that k_dof_dynamics keeps (sdx_phys_dynamics.h DynLds)
+template <class LDS>
+__device__ __forceinline__ void fk_wave0(const SdxConst* C, LDS& S, int tid, bool with_inertia, bool with_bias, long long* dbg = nullptr,
                                          bool lmf = false) {
   const sdx_scene_desc& sc = C->sc;
   const bool link = tid > 0 && tid < NL;
@@ -211,8 +214,10 @@ __device__ __forceinline__ void fk_wave0(const SdxConst* C, PhysLds& S, int tid,
 }
 
 // ---------------------------------------------------------------- B: H = M + implicit PD terms, Hinv (once per step)
+// off: bit i = the PD drive of dof i is off for this launch (sdx_apply_dof_forces): its implicit terms stay out of H.  Constant 0 outside the
+// SDX_PHYS_FORCE instantiations of k_physics
 template <int NT, bool DR = false>
-__device__ __forceinline__ void mass_matrix(const SdxConst* C, PhysLds& S, int tid, float h, long long* dbg, const float* drow = nullptr) {
+__device__ __forceinline__ void mass_matrix(const SdxConst* C, PhysLds& S, int tid, float h, long long* dbg, const float* drow = nullptr, uint32_t off = 0u) {
   const sdx_scene_desc& sc = C->sc;
   for (int idx = tid; idx < ND * (ND + 1) / 2; idx += NT) {
     int i, j;
@@ -249,7 +254,8 @@ __device__ __forceinline__ void mass_matrix(const SdxConst* C, PhysLds& S, int t
         }
       }
     }
-    if (DR) { if (i == j) s += sc.armature[i] + h * drow[ND + i] + h * h * drow[i]; }   // drow: this env's [kp; kd; lower; upper]
+    if (off != 0u && i == j && ((off >> i) & 1u)) s += sc.armature[i];   // (the diagonal line of a dof whose drive is off)
+    else if (DR) { if (i == j) s += sc.armature[i] + h * drow[ND + i] + h * h * drow[i]; }   // drow: this env's [kp; kd; lower; upper]
     else if (i == j) s += sc.armature[i] + h * sc.kd[i] + h * h * sc.kp[i];
     S.A[i][j] = s;
     S.A[j][i] = s;

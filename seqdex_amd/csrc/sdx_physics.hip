@@ -23,7 +23,7 @@
 //     surviving body pairs are expanded into the box pairs of the two compounds (consecutive candidates per lane, separating-axis test);
 //     narrowphase: lane = box pair picks the samples, lane = contact computes their geometry.
 //
-// One translation unit in seven files.  The device code of the phases lives in headers that only this file includes, in this order (each
+// One translation unit in eight files.  The device code of the phases lives in headers that only this file includes, in this order (each
 // may use what the ones before it define; none forward-declares a function of another):
 //   sdx_phys_lds.h      constants, wave hand-offs (WAVE_SYNC, WAVES_BARRIER, WAVE_SIGNAL / WAVES_WAIT), PhysLds and the table of its overlays,
 //                       Box, the clock / ablation macros
@@ -33,6 +33,7 @@
 //   sdx_phys_collide.h  D: collide
 //   sdx_phys_solve.h    E: solve and its stages: load_rows, warm_match, csr_clear .. csr_rank, link_inertia, row_weights, pass_setup,
 //                       loop_registers; per pass contact_update [AC], gather [D], robot_section; solve_exit
+//   sdx_phys_dynamics.h k_dof_dynamics: mass matrix, bias and drive torques outside any step (sdx_dof_dynamics)
 //   this file           write_kinematics, load_constants, k_physics (C the drive and F the integration are in its body), k_order,
 //                       k_kinematics, the launchers
 #include <stdlib.h>
@@ -45,6 +46,7 @@
 #include "sdx_phys_robot.h"
 #include "sdx_phys_collide.h"
 #include "sdx_phys_solve.h"
+#include "sdx_phys_dynamics.h"
 
 // ---------------------------------------------------------------- outputs shared by step and refresh
 template <int NT>
@@ -174,6 +176,13 @@ __device__ __forceinline__ bool ext_wrench(const SdxBuf& B, int e, int body, int
   }
   return F.x != 0.0f || F.y != 0.0f || F.z != 0.0f || T.x != 0.0f || T.y != 0.0f || T.z != 0.0f;
 }
+// k_physics<.. | SDX_PHYS_FORCE>: the actuation torque of dof j in this substep (include/seqdex.h sdx_apply_dof_forces; 0: none pending, or
+// a zero row - the dof is stepped as without the call).  Addressed like DR_ROW: nothing is kept over the substeps.
+__device__ __forceinline__ float dof_force(const SdxBuf& B, int e, int j) {
+  int ee = e;
+  SDX_OPAQUE_S(ee);
+  return B.dof_force ? B.dof_force[(size_t)ee * ND + j] : 0.0f;
+}
 template <int NTD>
 __global__ __launch_bounds__(NTD & ~SDX_PHYS_FLAGS, 2 * (NTD & ~SDX_PHYS_FLAGS) / 256) void k_physics(const SdxConst* __restrict__ C, SdxBuf B) {
   constexpr int NT = NTD & ~SDX_PHYS_FLAGS;
@@ -249,7 +258,7 @@ __global__ __launch_bounds__(NTD & ~SDX_PHYS_FLAGS, 2 * (NTD & ~SDX_PHYS_FLAGS) 
       else if (!ABL(32)) broad_mask_part<NT>(Cs, S, tl, 0);
       __syncthreads();
       PSTAMP(1);
-      if (!ABL(512)) mass_matrix<NT, DR>(Cs, S, tl, h, e == B.dbg_env ? B.dbg : nullptr, DR_ROW(dr_dof, 4 * ND, 0));   // (part 1 of the mask beside its wave-0 section)
+      if (!ABL(512)) mass_matrix<NT, DR>(Cs, S, tl, h, e == B.dbg_env ? B.dbg : nullptr, DR_ROW(dr_dof, 4 * ND, 0), FORCE ? B.dof_off : 0u);   // (part 1 of the mask beside its wave-0 section)
       else { if (tl >= 64) broad_mask_part<NT>(Cs, S, tl, 1); __syncthreads(); }
       PSTAMP(2);
     }
@@ -289,6 +298,14 @@ __global__ __launch_bounds__(NTD & ~SDX_PHYS_FLAGS, 2 * (NTD & ~SDX_PHYS_FLAGS) 
             }
           }
         }
+        if (FORCE) {   // sdx_apply_dof_forces: a drive that is off gives nothing; the actuation torque has the effort limit of its own
+          int jl = tl;
+          SDX_OPAQUE_AFTER(jl, tc);   // (nothing of this block is hoisted in front of the bias sum, whose operands fill the registers)
+          float drive = (B.dof_off >> jl) & 1u ? 0.0f : fminf(scl.effort[tl], fmaxf(-scl.effort[tl], t));
+          const float u = dof_force(B, e, jl);
+          if (u != 0.0f) drive += fminf(scl.effort[tl], fmaxf(-scl.effort[tl], u));
+          S.tau[tl] = drive - tc;
+        } else
         S.tau[tl] = fminf(scl.effort[tl], fmaxf(-scl.effort[tl], t)) - tc;   // the effort limit applies to the drive only
       }
       WAVE_SYNC();
@@ -490,7 +507,8 @@ static void physics_init() {
 extern "C" int sdxk_physics_threads() { return 512; }
 extern "C" void sdxk_physics(const SdxConst* C, const SdxBuf* B, hipStream_t st) {
   physics_init();
-  const bool force = B->ext_force || B->ext_torque;   // an external wrench rides with this launch (sdx_apply_rigid_body_forces)
+  // an external wrench (sdx_apply_rigid_body_forces), actuation torques or drives that are off (sdx_apply_dof_forces) ride with this launch
+  const bool force = B->ext_force || B->ext_torque || B->dof_force || B->dof_off;
   if (force && B->dr_on) hipLaunchKernelGGL(k_physics<512 | SDX_PHYS_DR | SDX_PHYS_FORCE>, dim3(B->N), dim3(512), sizeof(PhysLds), st, C, *B);
   else if (force) hipLaunchKernelGGL(k_physics<512 | SDX_PHYS_FORCE>, dim3(B->N), dim3(512), sizeof(PhysLds), st, C, *B);
   else if (B->dr_on) hipLaunchKernelGGL(k_physics<512 | SDX_PHYS_DR>, dim3(B->N), dim3(512), sizeof(PhysLds), st, C, *B);   // domain randomization on
@@ -500,4 +518,8 @@ extern "C" void sdxk_physics(const SdxConst* C, const SdxBuf* B, hipStream_t st)
 extern "C" void sdxk_kinematics(const SdxConst* C, const SdxBuf* B, hipStream_t st) {
   physics_init();
   hipLaunchKernelGGL(k_kinematics, dim3(B->N), dim3(64), sizeof(PhysLds), st, C, *B);
+}
+extern "C" void sdxk_dof_dynamics(const SdxConst* C, const SdxBuf* B, float* mass, float* bias, float* drive, hipStream_t st) {
+  if (B->dr_on) hipLaunchKernelGGL(k_dof_dynamics<true>, dim3(B->N), dim3(DYN_NT), 0, st, C, *B, mass, bias, drive);
+  else hipLaunchKernelGGL(k_dof_dynamics<false>, dim3(B->N), dim3(DYN_NT), 0, st, C, *B, mass, bias, drive);
 }

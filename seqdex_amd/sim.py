@@ -368,6 +368,46 @@ class SdxSim:
                                                         C.c_void_p(p.data_ptr()) if p is not None else None, self._stream_or_none()))
         self._perturb = (attr, f, p) if attr.force_scale > 0 else None
 
+    # ------------------------------------------------------------------ joint torques and dynamics (include/seqdex.h)
+    def apply_dof_forces(self, forces=None, drive_off=None):
+        """gym.set_dof_actuation_force_tensor with DOF_MODE_EFFORT per DOF: forces float32 [N, NDOF] (or None) are added to the joint
+        torques of the NEXT physics launch (simulate() or step()) only, each clamped to its DOF's effort limit; drive_off: an int mask or
+        an iterable of DOF indices whose PD drive is off in that launch.  A second call before the launch replaces both, no arguments
+        clears them.  Nothing is enqueued: the tensor is read by that launch, so it is kept referenced here until it has been enqueued."""
+        if drive_off is None:
+            mask = 0
+        elif isinstance(drive_off, (int, np.integer)):
+            mask = int(drive_off)
+        else:
+            mask = 0
+            for j in drive_off:
+                if not 0 <= int(j) < _abi.NDOF:
+                    raise ValueError("apply_dof_forces: drive_off names DOF %d outside [0, %d)" % (int(j), _abi.NDOF))
+                mask |= 1 << int(j)
+        if not 0 <= mask < 1 << 32:
+            raise ValueError("apply_dof_forces: drive_off mask %r is no uint32" % (mask,))
+        f = self._wrench_tensor(forces, "apply_dof_forces: forces", (self.num_envs, _abi.NDOF))
+        self._dof_forces = f
+        self._check(self.lib.sdx_apply_dof_forces(self.h, C.c_void_p(f.data_ptr()) if f is not None else None, C.c_uint32(mask),
+                                                  self._stream_or_none()))
+
+    def dof_dynamics(self, mass=True, bias=True, drive=True):
+        """acquire_mass_matrix_tensor / the DOF force tensor, from the current DOF and TARGETS in one launch: DofDynamics(mass [N, NDOF,
+        NDOF] = M(q) + armature, bias [N, NDOF] = C(q, qd) qd, drive [N, NDOF] = the clamped PD torque the next launch's first substep would
+        apply); None for an output not asked for.  The tensors are allocated once and rewritten by every call.  Stream-ordered."""
+        from .torque_control import DofDynamics
+        n, nd = self.num_envs, _abi.NDOF
+        if not hasattr(self, "_dyn"):
+            self._dyn = {}
+        out = []
+        for name, on, shape in (("mass", mass, (n, nd, nd)), ("bias", bias, (n, nd)), ("drive", drive, (n, nd))):
+            if on and name not in self._dyn:
+                self._dyn[name] = torch.empty(shape, dtype=torch.float32, device=self.device)
+            out.append(self._dyn[name] if on else None)
+        self._check(self.lib.sdx_dof_dynamics(self.h, *[C.c_void_p(t.data_ptr()) if t is not None else None for t in out],
+                                              self._stream_or_none()))
+        return DofDynamics(*out)
+
     # ------------------------------------------------------------------ sim snapshots (include/seqdex.h sdx_state_*, DESIGN.md section 20)
     def _stream_or_none(self):
         return _stream_ptr(self.device) if self.device.type == "cuda" else None
