@@ -459,6 +459,28 @@ int sdx_apply_dof_forces(sdx_handle h, const float* dof_forces_dev, uint32_t dri
  * While randomization is on, the gains are the env's SDX_T_DR_DOF rows and masses and inertias carry the SDX_T_DR_LINK factors, as in the step. */
 int sdx_dof_dynamics(sdx_handle h, float* mass_dev, float* bias_dev, float* drive_dev, void* stream);
 
+/* Operational-space (end-effector impedance) torques of the arm: from the CURRENT SDX_T_DOF to a torque row for
+ * sdx_apply_dof_forces in one launch on `stream`, part of no step; it reads SDX_T_DOF (and SDX_T_DR_LINK while randomization is on) and
+ * writes the caller's buffers only.  With the 7 arm DOFs and the hand base link (the link of SDX_T_JAC_EEF), per env:
+ *   M7 = sdx_dof_dynamics' mass[0:7, 0:7] (the hand's links at their current pose in it), b = its bias[0:7]
+ *   J  = [6, 7], what sdx_refresh_kinematics would put in SDX_T_JAC_EEF at this q (computed here: no refresh needed), v = J qd[0:7]
+ *   A  = J M7^-1 J^T + damping^2 I;  F = kp . dpose - kd . v;  w = A^-1 F  (both solves Cholesky)
+ *   u_null = M7 (kp_null . (q_null - q) - kd_null . qd)
+ *   u  = J^T w + u_null - J^T A^-1 J M7^-1 u_null + (compensate_bias ? b : 0)
+ *   dpose_dev   f32 [N, 6]         the pose error control_ik takes: position difference, then the rotation vector
+ *   torques_dev f32 [N, SDX_NDOF]  u clamped to +-effort on DOFs 0..6, +0.0f on the 16 hand DOFs: with drive_off_mask 0x7f the hand keeps
+ *                                  its PD drives
+ *   wrench_dev  f32 [N, 6] or NULL w
+ * SDX_ERR_INVALID with a message: attr, dpose_dev or torques_dev NULL; a gain, q_null or damping that is not finite; a negative gain or
+ * damping. */
+typedef struct {
+  float kp[6], kd[6];                       /* task-space stiffness and damping: rows 0..2 linear, 3..5 angular */
+  float kp_null[7], kd_null[7], q_null[7];  /* the posture spring-damper acting in the null space of J */
+  float damping;                            /* the damped-least-squares term of A (control_ik uses 0.05) */
+  int32_t compensate_bias;                  /* non-zero: add the velocity-product bias */
+} sdx_osc_attr;
+int sdx_osc_torques(sdx_handle h, const sdx_osc_attr* attr, const float* dpose_dev, float* torques_dev, float* wrench_dev, void* stream);
+
 /* Random pushes on the target brick (the reference's forceScale / forceProbRange / forceDecay / forceDecayInterval, morb.py:1495-1516;
  * DESIGN.md section 21).  rb_forces_dev f32 [N, SDX_BODIES, 3] and prob_dev f32 [N] are CALLER-OWNED device buffers (the task's rb_forces
  * and random_force_prob): they are read and written by the launches of the calls that follow, must stay alive while the sampler is on,

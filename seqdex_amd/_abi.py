@@ -96,6 +96,12 @@ class ForcePerturbAttr(C.Structure):
 SPACE_ENV, SPACE_LOCAL = 0, 1         # sdx_force_space
 
 
+class OscAttr(C.Structure):
+    """sdx_osc_attr"""
+    _fields_ = [("kp", f32 * 6), ("kd", f32 * 6), ("kp_null", f32 * 7), ("kd_null", f32 * 7), ("q_null", f32 * 7), ("damping", f32),
+                ("compensate_bias", i32)]
+
+
 class OptState(C.Structure):
     """sdxp_opt_state"""
     _fields_ = [("rms_count", C.c_double), ("ac_t", i32), ("cv_t", i32), ("ac_lr", f32), ("cv_lr", f32)]
@@ -118,7 +124,7 @@ SDX_EXPORTS = ["sdx_create", "sdx_destroy", "sdx_tensor", "sdx_load_initial_stat
                "sdx_step", "sdx_pre_physics", "sdx_simulate", "sdx_post_physics", "sdx_compute_observations",
                "sdx_reset_idx", "sdx_set_indexed", "sdx_refresh_kinematics", "sdx_render_segmentation", "sdx_num_envs", "sdx_last_error",
                "sdx_set_randomization", "sdx_set_noise", "sdx_render_view", "sdx_apply_rigid_body_forces", "sdx_set_force_perturbation",
-               "sdx_apply_dof_forces", "sdx_dof_dynamics",
+               "sdx_apply_dof_forces", "sdx_dof_dynamics", "sdx_osc_torques",
                "sdx_state_create", "sdx_state_destroy", "sdx_state_save", "sdx_state_restore", "sdx_state_save_all", "sdx_state_restore_all",
                "sdx_state_clone", "sdx_state_stats",
                "sdxp_create", "sdxp_destroy", "sdxp_tensor", "sdxp_param_count", "sdxp_act", "sdxp_store_rewards",
@@ -159,6 +165,7 @@ def load_library():
     lib.sdx_set_force_perturbation.argtypes = [vp, C.POINTER(ForcePerturbAttr), vp, vp, vp]
     lib.sdx_apply_dof_forces.argtypes = [vp, vp, C.c_uint32, vp]
     lib.sdx_dof_dynamics.argtypes = [vp, vp, vp, vp, vp]
+    lib.sdx_osc_torques.argtypes = [vp, C.POINTER(OscAttr), vp, vp, vp, vp]
     lib.sdx_state_create.argtypes = [vp, i32, C.POINTER(vp)]
     lib.sdx_state_destroy.argtypes = [vp]
     lib.sdx_state_save.argtypes = [vp, vp, vp, vp, i32, vp]

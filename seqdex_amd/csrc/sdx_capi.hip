@@ -583,6 +583,28 @@ extern "C" int sdx_dof_dynamics(sdx_handle h, float* mass_dev, float* bias_dev, 
   sdxk_dof_dynamics(h->d_const, &h->buf, mass_dev, bias_dev, drive_dev, (hipStream_t)stream);
   return check_launch(h, "sdx_dof_dynamics");
 }
+extern "C" int sdx_osc_torques(sdx_handle h, const sdx_osc_attr* attr, const float* dpose_dev, float* torques_dev, float* wrench_dev, void* stream) {
+  if (!h) return SDX_ERR_INVALID;
+  const char* why = nullptr;
+  if (!attr) why = "sdx_osc_torques: attr is NULL";
+  else if (!dpose_dev) why = "sdx_osc_torques: dpose_dev is NULL";
+  else if (!torques_dev) why = "sdx_osc_torques: torques_dev is NULL";
+  else {
+    const auto gain = [](float v) { return std::isfinite(v) && v >= 0.0f; };
+    bool gains = true, posture = true;
+    for (int r = 0; r < 6; ++r) gains = gains && gain(attr->kp[r]) && gain(attr->kd[r]);
+    for (int j = 0; j < 7; ++j) {
+      gains = gains && gain(attr->kp_null[j]) && gain(attr->kd_null[j]);
+      posture = posture && std::isfinite(attr->q_null[j]);
+    }
+    if (!gains) why = "sdx_osc_torques: kp, kd, kp_null and kd_null must be finite and not negative";
+    else if (!posture) why = "sdx_osc_torques: q_null must be finite";
+    else if (!gain(attr->damping)) why = "sdx_osc_torques: damping must be finite and not negative";
+  }
+  if (why) { h->err = why; return SDX_ERR_INVALID; }
+  sdxk_osc_torques(h->d_const, &h->buf, attr, dpose_dev, torques_dev, wrench_dev, (hipStream_t)stream);
+  return check_launch(h, "sdx_osc_torques");
+}
 extern "C" int sdx_set_force_perturbation(sdx_handle h, const sdx_force_perturb_attr* attr, float* rb_forces_dev, float* prob_dev, void* stream) {
   if (!h) return SDX_ERR_INVALID;
   if (!attr || !(attr->force_scale > 0.0f || std::isnan(attr->force_scale))) {   // off (a NaN scale is an error, below)

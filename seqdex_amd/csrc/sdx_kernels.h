@@ -25,6 +25,8 @@ void sdxk_dr_sample(const SdxConst* C, const SdxBuf* B, const sdx_dr_desc* desc,
 void sdxk_noise(const SdxConst* C, const SdxBuf* B, const sdx_noise_attr* attr, const float* src, float* dst, int W, int act, hipStream_t st);
 // sdx_physics.hip k_dof_dynamics: mass [N,23,23], bias [N,23], drive [N,23] (device, any of them nullptr) from the current dof / targets
 void sdxk_dof_dynamics(const SdxConst* C, const SdxBuf* B, float* mass, float* bias, float* drive, hipStream_t st);
+// sdx_physics.hip k_osc_torques: torques [N,23] and wrench [N,6] (device, wrench may be nullptr) from the current dof and dpose [N,6]
+void sdxk_osc_torques(const SdxConst* C, const SdxBuf* B, const sdx_osc_attr* attr, const float* dpose, float* torques, float* wrench, hipStream_t st);
 // mode SDX_FP_STEP: the whole rule for one step (resets from reset_buf); SDX_FP_RESET: rows <- 0 and a new probability for the envs of mask
 // (nullptr: every env); SDX_FP_DRAW: a new probability for every env, rows untouched.  factor: decay^(dt / decay_interval)
 enum { SDX_FP_STEP = 0, SDX_FP_RESET = 1, SDX_FP_DRAW = 2 };

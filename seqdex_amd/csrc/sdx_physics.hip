@@ -23,7 +23,7 @@
 //     surviving body pairs are expanded into the box pairs of the two compounds (consecutive candidates per lane, separating-axis test);
 //     narrowphase: lane = box pair picks the samples, lane = contact computes their geometry.
 //
-// One translation unit in eight files.  The device code of the phases lives in headers that only this file includes, in this order (each
+// One translation unit in nine files.  The device code of the phases lives in headers that only this file includes, in this order (each
 // may use what the ones before it define; none forward-declares a function of another):
 //   sdx_phys_lds.h      constants, wave hand-offs (WAVE_SYNC, WAVES_BARRIER, WAVE_SIGNAL / WAVES_WAIT), PhysLds and the table of its overlays,
 //                       Box, the clock / ablation macros
@@ -34,6 +34,7 @@
 //   sdx_phys_solve.h    E: solve and its stages: load_rows, warm_match, csr_clear .. csr_rank, link_inertia, row_weights, pass_setup,
 //                       loop_registers; per pass contact_update [AC], gather [D], robot_section; solve_exit
 //   sdx_phys_dynamics.h k_dof_dynamics: mass matrix, bias and drive torques outside any step (sdx_dof_dynamics)
+//   sdx_phys_osc.h      k_osc_torques: operational-space torques of the arm outside any step (sdx_osc_torques)
 //   this file           write_kinematics, load_constants, k_physics (C the drive and F the integration are in its body), k_order,
 //                       k_kinematics, the launchers
 #include <stdlib.h>
@@ -47,6 +48,7 @@
 #include "sdx_phys_collide.h"
 #include "sdx_phys_solve.h"
 #include "sdx_phys_dynamics.h"
+#include "sdx_phys_osc.h"
 
 // ---------------------------------------------------------------- outputs shared by step and refresh
 template <int NT>
@@ -522,4 +524,9 @@ extern "C" void sdxk_kinematics(const SdxConst* C, const SdxBuf* B, hipStream_t 
 extern "C" void sdxk_dof_dynamics(const SdxConst* C, const SdxBuf* B, float* mass, float* bias, float* drive, hipStream_t st) {
   if (B->dr_on) hipLaunchKernelGGL(k_dof_dynamics<true>, dim3(B->N), dim3(DYN_NT), 0, st, C, *B, mass, bias, drive);
   else hipLaunchKernelGGL(k_dof_dynamics<false>, dim3(B->N), dim3(DYN_NT), 0, st, C, *B, mass, bias, drive);
+}
+extern "C" void sdxk_osc_torques(const SdxConst* C, const SdxBuf* B, const sdx_osc_attr* attr, const float* dpose, float* torques, float* wrench,
+                                 hipStream_t st) {
+  if (B->dr_on) hipLaunchKernelGGL(k_osc_torques<true>, dim3(B->N), dim3(DYN_NT), 0, st, C, *B, *attr, dpose, torques, wrench);
+  else hipLaunchKernelGGL(k_osc_torques<false>, dim3(B->N), dim3(DYN_NT), 0, st, C, *B, *attr, dpose, torques, wrench);
 }

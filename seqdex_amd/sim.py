@@ -408,6 +408,32 @@ class SdxSim:
                                               self._stream_or_none()))
         return DofDynamics(*out)
 
+    def osc_torques(self, dpose, gains, out=None, wrench=False):
+        """operational-space (end-effector impedance) torques of the arm from the current DOF state in one launch (include/seqdex.h
+        sdx_osc_torques).  dpose float32 [N, 6] (torque_control.pose_error); gains: a torque_control.OscGains or a
+        ready _abi.OscAttr; out: float32 [N, NDOF] to write (default: a tensor allocated once and rewritten by every call).  Returns the
+        torques, or (torques, wrench [N, 6]) with wrench=True; the row goes to apply_dof_forces(u, drive_off=0x7f) as it is.  Stream-ordered."""
+        n = self.num_envs
+        d = self._wrench_tensor(dpose, "osc_torques: dpose", (n, 6))
+        if d is None:
+            raise ValueError("osc_torques: dpose: expected a contiguous float32 tensor of shape %s on %s, got None" % ((n, 6), self.device))
+        u = self._wrench_tensor(out, "osc_torques: out", (n, _abi.NDOF))
+        if not hasattr(self, "_osc"):
+            self._osc = {}
+        if u is None:
+            if "torques" not in self._osc:
+                self._osc["torques"] = torch.empty((n, _abi.NDOF), dtype=torch.float32, device=self.device)
+            u = self._osc["torques"]
+        w = None
+        if wrench:
+            if "wrench" not in self._osc:
+                self._osc["wrench"] = torch.empty((n, 6), dtype=torch.float32, device=self.device)
+            w = self._osc["wrench"]
+        attr = gains if isinstance(gains, _abi.OscAttr) else gains.to_attr()
+        self._check(self.lib.sdx_osc_torques(self.h, C.byref(attr), C.c_void_p(d.data_ptr()), C.c_void_p(u.data_ptr()),
+                                             C.c_void_p(w.data_ptr()) if w is not None else None, self._stream_or_none()))
+        return (u, w) if wrench else u
+
     # ------------------------------------------------------------------ sim snapshots (include/seqdex.h sdx_state_*, DESIGN.md section 20)
     def _stream_or_none(self):
         return _stream_ptr(self.device) if self.device.type == "cuda" else None

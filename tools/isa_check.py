@@ -5,7 +5,8 @@ per-pass stage functions the loop calls: the lines of the same file between the 
 code inlined from any other line of those files is not part of the loop.
 usage: python tools/isa_check.py [--randomize] [--force] [extra hipcc flags...]      (cross-compiles; no GPU needed)
 --randomize: the same report for the domain-randomization variant k_physics<512 | SDX_PHYS_DR> (= k_physics<513>)
---force: ... for the external-wrench variant k_physics<512 | SDX_PHYS_FORCE> (514; with --randomize 515)"""
+--force: ... for the external-wrench variant k_physics<512 | SDX_PHYS_FORCE> (514; with --randomize 515)
+--osc: registers, scratch and occupancy of k_osc_torques<false> and k_osc_torques<true> (sdx_phys_osc.h) instead, nothing about the loop"""
 import os
 import re
 import subprocess
@@ -21,6 +22,11 @@ if RANDOMIZE:
 FORCE = "--force" in sys.argv
 if FORCE:
     sys.argv.remove("--force")
+OSC = "--osc" in sys.argv
+if OSC:
+    sys.argv.remove("--osc")
+OSC_TAGS = [("k_osc_torques<false>", "k_osc_torquesILb0E"), ("k_osc_torques<true>", "k_osc_torquesILb1E")]
+KEYS = ("VGPRs:", "AGPRs:", "ScratchSize [bytes/lane]:", "SGPRs Spill:", "VGPRs Spill:", "Occupancy [waves/SIMD]:", "LDS Size [bytes/block]:")
 TAG = "k_physicsILi%dE" % (512 + (1 if RANDOMIZE else 0) + (2 if FORCE else 0))
 KERN = "_Z9%sEvPK8SdxConst6SdxBuf" % TAG
 
@@ -40,6 +46,11 @@ with tempfile.TemporaryDirectory() as td:
            "-Rpass-analysis=kernel-resource-usage", "-save-temps=obj", "-c", SRC, "-o", os.path.join(td, "p.o")] + sys.argv[1:]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=td)
     rem = r.stderr
+    if OSC:
+        for name, tag in OSC_TAGS:
+            blk = rem[rem.index(tag):]
+            print(name + ":", ", ".join("%s %s" % (key, (re.search(re.escape(key) + r"\s*(\d+)", blk) or [None, "?"])[1]) for key in KEYS))
+        sys.exit(0)
     blk = rem[rem.index(TAG):]
     for key in ("VGPRs:", "ScratchSize [bytes/lane]:", "SGPRs Spill:", "VGPRs Spill:", "Occupancy [waves/SIMD]:"):
         m = re.search(re.escape(key) + r"\s*(\d+)", blk)
