@@ -23,7 +23,8 @@
 //   W1 columns   : CU g owns columns 4g..4g+3 of the three nets, thread = row       (backward; duplicate copy, same Adam)
 //   W2 rows      : wave w owns eighth w of row g of the three nets                  (forward)
 //   W2 columns   : CU g owns columns 2g, 2g+1: lanes l / l ^ 32 of wave w = row 32w + (l & 31) of the two columns (backward; duplicate copy)
-//   heads        : CU g runs Adam for 25 of the 6 400 head weights and publishes them; every CU reads the matrix back in phase D
+//   heads        : CU g runs Adam for 25 of the 6 400 head weights - rows (g >> 5) + {0, 8, 16} of columns 8 (g & 31) .. + 7, column g of row 24 - and
+//                  publishes them, three rows of a column per 16-byte word (head_owned / head_publish); every CU reads the matrix back in phase D
 // Row and column copies receive the same gradient g[n][k] = sum_s dY_s[n] X_s[k] (same operands, same order), so they
 // stay bit-identical without communication.  The multi-kernel path (sdxp_update.hip) remains the fallback for other shapes
 // and the explicit-gradient multi-rank path.
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     r0w = wave >> 1; h0 = wave & 1; n0 = 4 * g + r0w;
     r1w = wave >> 2; q1 = wave & 3; r1 = 2 * g + r1w;
     c2c = (t >> 5) & 1; c2n = 32 * (t >> 6) + (t & 31);   // column c2n: lanes l and l ^ 32 of one wave hold its two row halves
-    he = HPC * g + t; hrow = he >> 8; hk = he & (U2 - 1);
+    head_owned(b, t, he, hrow, hk);   // this CU's HPC head elements: three rows of eight columns and one column of row 24
   };
   refresh();
 #define TS(i) if (stamps && g == (stamps >> 8) && tid == 0) { const long long t_ = __builtin_amdgcn_s_memtime(); S.tacc[i] += t_ - S.tlast; S.tlast = t_; }
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
   if (tid == 0) S.fail = 0;
   if (tid == 0) S.tlast = __builtin_amdgcn_s_memtime();
   const int A = ACT;
-  u64* const LL = D.ll;   // 8-byte exchange words of the head matrix (LL_HW)
+  u64* const LL = D.ll;   // 8-byte exchange words of the head matrix's row 24 (LL_H24)
   const __amdgpu_buffer_rsrc_t LQ = lq_rsrc(D.ll);   // 16-byte packed words of the chain edges, layout LQ_*: [s][unit], the three networks per word
 
   // ------------------------------------------------------------------ resident parameters
@@ -88,8 +89,8 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
   float w2[3], m2[3], v2[3];
   // layer 2 columns: col 2g + c2c, row n = c2n (c2c = lane >> 5, c2n = 32 wave + (lane & 31): refresh())
   float c2[3], cm2[3], cv2[3];
-  // heads ((A+2) x U2 = 6400 weights): CU g runs Adam for the HPC flat elements [HPC g, HPC g + HPC) on its first HPC threads and
-  // publishes the new weight in the parameter array; phase D of every CU reads the whole head matrix back through L2.
+  // heads ((A+2) x U2 = 6400 weights): CU g runs Adam for HPC elements (hrow, hk) on its first HPC threads (head_owned, sdxp_persist_exchange.h) and
+  // publishes the new weights as exchange words; phase D of every CU reads the whole head matrix back through L2.
   float hw = 0.0f, hm = 0.0f, hv = 0.0f;
 
   auto ldm = [&](const float* p, size_t o) -> float { return SINGLE ? 0.0f : p[o]; };   // Adam moments: not needed for one forward/backward
@@ -291,6 +292,12 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       }
       TS(1)
     }
+    // s_waitcnt vmcnt(0) as an instruction the compiler's counter model SEES (the asm one below it does not see): the first look at the norm
+    // words is taken only `if (pending)`, so behind that merge the model holds their loads for outstanding, and where their registers are next
+    // written - the top of the x1 or the x2 shadow, as the allocation falls - it waits for vmcnt(0) itself: there, wave 0 has just stored its
+    // x1 / x2 word and the wait is that store's round trip (0.2 us per shadow on the phase clock).  Here nothing is in flight but the row loads,
+    // which are waited for below anyway
+    __builtin_amdgcn_s_waitcnt(0x0F70);
     if (!last) {
       // ---- forward L0 of the owned rows (two half-row waves per row, combined through LDS) once this step's rows have landed
       SDX_WAIT_VMCNT0();
@@ -423,8 +430,8 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
 #pragma unroll
         for (int s = 0; s < MB; ++s) gg += (hrow < A ? S.dmu[s][hrow] : S.dv[hrow - A][s]) * gs * S.x3[net][s][hk];
         adam1(hw, gg, hm, hv, lrb, isq);
-        ll_store(LL + LL_HW + he, hw, tag_prev);
       }
+      if (wave == 0) head_publish(LQ, LL, tid, he, hw, tag_prev);   // the three rows of a column meet in one lane: eight packed words and row 24's
       if (tid >= BIAS_L2 && tid < BIAS_HEAD + A + 2) {   // layer-2 and head biases
         int net; float gg = 0.0f;
         if (tid < BIAS_HEAD) { net = tid - BIAS_L2; for (int s = 0; s < MB; ++s) gg += S.dyown[net][s][DY_L2]; }
@@ -491,6 +498,8 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     // (this minibatch's actions and old (mu, sigma) go to LDS before the Grams: three registers fewer across the 60-value reduction)
     if (tid < MB * 32) { S.act[tid / 32][tid % 32] = pf_act; S.omu[tid / 32][tid % 32] = pf_omu; S.osg[tid / 32][tid % 32] = pf_osg; }
     if (tid >= T_LS && tid < T_LS + 32) { const float l_ = (tid - T_LS < A) ? s_b2[0][tid - T_LS] : 0.0f; S.ls[tid - T_LS] = l_; S.sgm[tid - T_LS] = expf(l_); }
+    u32x4 ph[4];
+    u64 p24[4];
     if constexpr (!SINGLE)
     {   // ---- (shadow of x3) Grams of x2 and x1 (S.x1 stays valid until the next step's gather).  Two butterflies, ONE pass through LDS
         // and its two barriers: out[0..29] = [x2: net][10], out[32..61] = [x1: net][10]
@@ -523,6 +532,11 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
         row_butterfly<30>(p, ub, lane);
       }
       rows_store<8>(S, ub, 32, wave, lane);
+      // first look at this wave's head rows (phase D's row view): the words left their CUs a phase ago, in the x2 shadow, and what the top of
+      // phase D paid for them was the round trip of its own loads.  Four packed words and row 24's four 8-byte words are 24 registers across
+      // rows_reduce; the 8-byte form of the whole matrix was 32 + 8 with the x3 words and spilled here.  Unconditional: at step 0 nobody has
+      // published, the words are not taken (a first look behind `if (step != 0)` cost 56 bytes of scratch: its registers then meet at a merge)
+      head_rows_peek(LQ, wave, lane, ph); head_row24_peek(LL, wave, lane, tag_prev, p24);
       rows_reduce(S, 64, S.part, tid);
       if (tid < 48) S.gx[tid >> 4][2][tid & 15] = S.part[(tid >> 4) * 10 + tri16(tid & 15)];
       else if (tid >= 64 && tid < 64 + 48) { const int t = tid - 64; S.gx[t >> 4][1][t & 15] = S.part[32 + (t >> 4) * 10 + tri16(t & 15)]; }
@@ -531,40 +545,22 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     refresh();
     // ================================================================== phase D: gather x3 and the heads, losses, backward to dY1
     float wh[HR][4];   // this wave's head rows for the forward (row = wave + 8 j, columns lane + 64 e)
-    // The head words were published a phase ago (shadow of x2), so they are normally all there.  Row view (head forward): all 16 loads
-    // of a lane are issued before the first tag is looked at, and they share their round trip with the first look at the lane's x3
-    // words (round 3: five chained gathers, then the x3 gather: 2.4 us between the x3 publish and the head forward, 0.7 of them the
-    // x3 edge itself).  If a word is missing the polling gathers below wait.  The column view is first used by the heads' backward:
-    // it is requested after the head forward, under the loss phase (both views at once - 58 registers in flight - spilled).
+    // The head words were published a phase ago (shadow of x2), so they are normally all there.  Row view (head forward): the lane's four
+    // packed words - rows wave, wave + 8, wave + 16 of columns lane + 64 e - and, on wave 0, row 24's four words were requested inside the x3
+    // shadow (above) and are taken here; what this point still waits for is the first look at the lane's two x3 words (round 3: five chained
+    // gathers, then the x3 gather: 2.4 us between the x3 publish and the head forward, 0.7 of them the x3 edge itself).  If a word is missing
+    // the polling gathers below wait.  The column view is first used by the heads' backward: it is requested after the head forward, under
+    // the loss phase.  (One minibatch: no shadow, and only step 0, which takes the weights from the parameter array.)
     bool row_done = false;
     {
-      // first look at this lane's two x3 words, issued BEFORE the head-word loads: both round trips overlap; if the x3 words of a slow
-      // producer are not there yet, the polling gather below continues after the head words have been taken
+      // first look at this lane's two x3 words; if the x3 words of a slow producer are not there yet, the polling gather below continues
+      // after the head words have been taken
       u32x4 w3[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) w3[i] = load16(LQ, LQ_X3 + tid + i * NTH);
       if (step != 0) {
-        u64 ww[HR][4];
-        const u64 absent = (u64)tag_prev << 32;        // rows past the 25 head rows: value 0 with the expected tag
-#pragma unroll
-        for (int j = 0; j < HR; ++j) {
-          const int row = wave + 8 * j;
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            ww[j][e] = row < A + 2 ? __hip_atomic_load(LL + LL_HW + (size_t)row * U2 + lane + 64 * e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : absent;
-        }
-        bool ok = true;
-#pragma unroll
-        for (int j = 0; j < HR; ++j)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) ok = ok && (unsigned)(ww[j][e] >> 32) == tag_prev;
-        if (__builtin_amdgcn_ballot_w64(!ok) == 0) {
-#pragma unroll
-          for (int j = 0; j < HR; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) wh[j][e] = __uint_as_float((unsigned)ww[j][e]);
-          row_done = true;
-        }
+        if constexpr (SINGLE) { head_rows_peek(LQ, wave, lane, ph); head_row24_peek(LL, wave, lane, tag_prev, p24); }
+        row_done = head_rows_take(ph, p24, tag_prev, wh);
       }
       float v0[2], v1[2], v2[2];
 #pragma unroll
@@ -575,19 +571,19 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
       image_store(S.x3, v0, v1, v2, tid);
     }
     if (!row_done) {
+      if (step == 0) {   // nothing has been published yet: the weights the launch started from
 #pragma unroll
-    for (int j = 0; j < HR; ++j) {
-      const int row = wave + 8 * j;
+        for (int j = 0; j < HR; ++j) {
+          const int row = wave + 8 * j;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) wh[j][e] = 0.0f;
-      if (row < A + 2) {
-        if (step == 0) {
-          const float* hp = P_of(head_net(row)) + head_woff(row) + lane;
+          for (int e = 0; e < 4; ++e) wh[j][e] = 0.0f;
+          if (row < A + 2) {
+            const float* hp = P_of(head_net(row)) + head_woff(row) + lane;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) wh[j][e] = hp[64 * e];
-        } else if (!ll_gather<4>(LL + LL_HW + (size_t)row * U2 + lane, 64, tag_prev, wh[j], failflag)) S.fail = 1;   // lane-contiguous words
-      }
-    }
+            for (int e = 0; e < 4; ++e) wh[j][e] = hp[64 * e];
+          }
+        }
+      } else if (!head_rows_gather(LQ, LL, wave, lane, tag_prev, wh, failflag)) S.fail = 1;
     }
     TS(10)
     __syncthreads();
@@ -596,9 +592,10 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     __syncthreads();
     TS(11)
     // Column view of the head words (this lane's column c2n, rows 13 c2c .. 13 c2c + 12; first used by the heads' backward): requested
-    // here, under the loss phase.  No tags: between them the row views of the eight waves cover every head word, each wave has seen
-    // its words' tags (fast path or polling gather) before the barrier in front of the head forward, and the words are not rewritten
-    // before every CU has finished this step - so the low halves (the values) are read as plain agent-scope dwords, 13 registers.
+    // here, under the loss phase.  No tags: between them the row views of the eight waves cover every head word - wave w words 256 w ..
+    // 256 w + 255 of LQ_HW, wave 0 also the 256 words of row 24 - each wave has seen its words' tags (first look or polling gather) before
+    // the barrier in front of the head forward, and the words are not rewritten before every CU has finished this step - so the values are
+    // read as plain agent-scope loads: eight 8-byte pieces of packed words and one dword of row 24, 17 registers (head_cols_load).
     // (the per-sample scalars prefetched in phase C are taken NOW: the loads below sit behind lane-dependent conditions, and after such a
     // merge the compiler's counter model waits for everything outstanding at the next use of any loaded register - that use would be
     // pf_adv in the loss phase, i.e. the column loads' whole round trip: 0.6 us on the chain)
@@ -607,18 +604,15 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     ZOps zo;
     loss_request(S, tid, zo);
     __builtin_amdgcn_sched_barrier(0);
-    float wc[13];      // (row 25 = 13 + 12 does not exist: its slot repeats row 24 and is never used)
+    HeadCols hc;       // rows w + 8 c2c and w + 8 + 8 c2c of the column, w < 8, and row 24: head_cols_take picks wc[] out of them behind the loss phase
     if (step == 0) {
 #pragma unroll
-      for (int j = 0; j < 13; ++j) { const int row = min(13 * c2c + j, A + 1); wc[j] = P_of(head_net(row))[head_woff(row) + c2n]; }
-    } else {           // 13 unconditional loads, nothing between them that looks at a loaded value
-      const unsigned* hwv = reinterpret_cast<const unsigned*>(LL + LL_HW) + 2 * c2n;
-#pragma unroll
-      for (int j = 0; j < 13; ++j) {
-        const int row = min(13 * c2c + j, A + 1);
-        wc[j] = __uint_as_float(__hip_atomic_load(hwv + (size_t)row * (2 * U2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+      for (int w = 0; w < 8; ++w) {
+        const int ra = w + 8 * c2c, rb = ra + 8;
+        hc.pair[w].x = __float_as_uint(P_of(head_net(ra))[head_woff(ra) + c2n]); hc.pair[w].y = __float_as_uint(P_of(head_net(rb))[head_woff(rb) + c2n]);
       }
-    }
+      hc.r24 = __float_as_uint(P_of(2)[head_woff(A + 1) + c2n]);
+    } else head_cols_load(LQ, c2c, c2n, hc);   // 9 unconditional loads, nothing between them that looks at a loaded value
     const float invM = 1.0f / (float)MB;
     // (the loss phase restates sdxp_ppo_terms.h: loss_front / loss_back, sdxp_persist_phase_d.h.  Only what the gradients need: the KL, bounds and
     // entropy terms of the statistics are formed in the dY1 shadow, on waves 5 and 7)
@@ -647,6 +641,8 @@ __global__ __launch_bounds__(NTH, 2) void k_update_persistent(SdxpDev D, int tot
     // stores below sit in front of block_sum's barriers, their readers - the Gram of dY2, dyown[.][.][DY_L2], the next step's Adam of layer 2 -
     // behind them.)
     float d2[3][MB];
+    float wc[13];      // (row 25 = 13 + 12 does not exist: its slot repeats row 24 and is never used)
+    head_cols_take(hc, c2c, wc);
     head_backward(S, wc, c2c, c2n, d2);   // (its LDS operands requested ahead of the chains: sdxp_persist_phase_d.h)
     TS(13)
     // backward L2 with the column copy: dY1[net][s][2g+c] = (sum_n dY2[net][s][n] W2[n][2g+c]) * elu'(x2[net][s][2g+c])

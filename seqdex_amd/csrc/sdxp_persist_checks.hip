@@ -1,8 +1,10 @@
-// sdxp_persist_checks.hip — test entries for the machinery of the persistent PPO update (sdxp_persist_sums.h, sdxp_persist_adam.h, sdxp_persist_tails.h, sdxp_persist_phase_d.h): each runs the
+// sdxp_persist_checks.hip — test entries for the machinery of the persistent PPO update (sdxp_persist_sums.h, sdxp_persist_adam.h, sdxp_persist_tails.h, sdxp_persist_phase_d.h,
+// the head_* helpers of sdxp_persist_exchange.h): each runs the
 // helper k_update_persistent uses beside the form it stands for, in one workgroup, and hands both results back.  Built with the flags of
 // sdxp_persist.hip (Makefile), so that the helpers are compiled here as they are inside the kernel.
 #include "sdx_common.h"
 #include "sdxp_launch.h"
+#include "sdxp_persist_exchange.h"
 #include "sdxp_persist_sums.h"
 #include "sdxp_persist_adam.h"
 #include "sdxp_persist_tails.h"
@@ -679,5 +681,52 @@ extern "C" int sdxpk_loss_phase_check(const float* in, int n, float* out, hipStr
   if (n < 1) return -1;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_loss_phase_check), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PLds)) != hipSuccess) return -1;
   hipLaunchKernelGGL(k_loss_phase_check, dim3(n), dim3(NTH), sizeof(PLds), st, in, out);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// Test entries (tests/test_gpu_persist_head_words.py): the head matrix between the CUs (sdxp_persist_exchange.h: head_owned, head_publish, head_rows_peek /
+// head_row24_peek / head_rows_take, head_cols_load), as two launches in stream order - no workgroup waits for another inside a launch.
+// sdxpk_head_publish_check: NWG workgroups of one wave; thread t < HPC of workgroup g takes element (hrow, hk) of W [ACT + 2][U2] (bit patterns) as the
+// ownership map gives it, writes (hrow, hk) to own [NWG][HPC][2], and the wave publishes with `tag` - workgroup `stale_cu` (if >= 0) with tag - 1.  ll is an
+// exchange buffer of sdxpk_head_words_ll_words() 8-byte words.
+__global__ __launch_bounds__(64) void k_head_publish_check(const float* W, unsigned tag, int stale_cu, u64* ll, int* own) {
+  const int t = threadIdx.x, g = blockIdx.x;
+  int he, hrow, hk;
+  head_owned(g, t, he, hrow, hk);
+  float hw = 0.0f;
+  if (t < HPC) { hw = W[hrow * U2 + hk]; own[(g * HPC + t) * 2] = hrow; own[(g * HPC + t) * 2 + 1] = hk; }
+  head_publish(lq_rsrc(ll), ll, t, he, hw, g == stale_cu ? tag - 1u : tag);
+}
+// sdxpk_head_views_check: ONE workgroup of NTH threads takes the row view with the non-polling take and loads the column view, as phase D does:
+// wh [NTH][HR][4], wc [NTH][13] (bit patterns), verdict [NWV]: 1 if the wave's take found `tag` on all its words, else 0.
+__global__ __launch_bounds__(NTH) void k_head_views_check(u64* ll, unsigned tag, float* wh_out, float* wc_out, int* verdict) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const __amdgpu_buffer_rsrc_t q = lq_rsrc(ll);
+  u32x4 ph[4];
+  u64 p24[4];
+  float wh[HR][4];
+  head_rows_peek(q, wave, lane, ph);
+  head_row24_peek(ll, wave, lane, tag, p24);
+  const bool hit = head_rows_take(ph, p24, tag, wh);
+  if (lane == 0) verdict[wave] = hit ? 1 : 0;
+#pragma unroll
+  for (int j = 0; j < HR; ++j)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) wh_out[(tid * HR + j) * 4 + e] = wh[j][e];
+  const int c2c = (tid >> 5) & 1, c2n = 32 * (tid >> 6) + (tid & 31);
+  HeadCols hc;
+  float wc[13];
+  head_cols_load(q, c2c, c2n, hc);
+  head_cols_take(hc, c2c, wc);
+#pragma unroll
+  for (int j = 0; j < 13; ++j) wc_out[tid * 13 + j] = wc[j];
+}
+extern "C" size_t sdxpk_head_words_ll_words() { return SDXP_LL_WORDS; }
+extern "C" int sdxpk_head_publish_check(const float* W, unsigned tag, int stale_cu, unsigned long long* ll, int* own, hipStream_t st) {
+  if (stale_cu >= NWG) return -1;
+  hipLaunchKernelGGL(k_head_publish_check, dim3(NWG), dim3(64), 0, st, W, tag, stale_cu, ll, own);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int sdxpk_head_views_check(unsigned long long* ll, unsigned tag, float* wh, float* wc, int* verdict, hipStream_t st) {
+  hipLaunchKernelGGL(k_head_views_check, dim3(1), dim3(NTH), 0, st, ll, tag, wh, wc, verdict);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
