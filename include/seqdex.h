@@ -501,6 +501,51 @@ int sdx_osc_torques(sdx_handle h, const sdx_osc_attr* attr, const float* dpose_d
 typedef struct { float force_scale, prob_lo, prob_hi, decay, decay_interval; } sdx_force_perturb_attr;
 int sdx_set_force_perturbation(sdx_handle h, const sdx_force_perturb_attr* attr, float* rb_forces_dev, float* prob_dev, void* stream);
 
+/* Contact report (gym.get_env_rigid_contacts, per contact and on the device): the contact list of a step's LAST
+ * solve - the last substep's, the list whose impulses SDX_T_CONTACT and the warm-start cache describe - written by the physics launch
+ * itself into CALLER-OWNED device buffers.  Per env e the first count[e] columns of every row are written, in the solver's list order;
+ * columns beyond count[e] are left as they are.  count[e] = min(SDX_T_NCONTACTS[e], SDX_MAX_CONTACTS), and with the warm start on it is
+ * SDX_T_WARM_COUNT[e] and key is SDX_T_WARM_KEYS & 0x0fffffff column by column; key is written whether or not the solver is warm.
+ *   sides     a contact has a side a and a side b (the narrowphase samples a box of side a against a box of side b).  normal points out of
+ *             side b towards side a: the normal impulse pushes side a along +normal.  force acts on side a, side b receives -force.
+ *   force     (normal lam0 + t1 lam1 + t2 lam2) / h with the accumulated impulses the last solve ended with, h = dt / substeps, and the
+ *             solver's own tangent basis: an impulse of ONE substep over its length, like SDX_T_CONTACT.
+ * sdx_set_contact_report arms the report: while armed it is written by EVERY physics launch of sdx_simulate / sdx_step, on that launch's
+ * stream (not by the settling launches of an Orient / Search reset event); the buffers must stay alive until the report is disarmed
+ * (report == NULL) and the last such launch has run.  Any pointer but count may be NULL (that column is not written); a non-NULL report
+ * with count == NULL: SDX_ERR_INVALID with a message.  Nothing is enqueued by the call itself (`stream` is unused); the struct is copied.
+ * Armed or not, every other result of a step is bit for bit the same.  Not part of a snapshot. */
+#define SDX_MAX_CONTACTS 1536   /* contacts per env a solve can take: the capacity of the report's rows */
+typedef struct {
+  int32_t*  count;       /* i32 [N]                        required */
+  int32_t*  body;        /* i32 [N, 2, SDX_MAX_CONTACTS]   side a, side b: row of SDX_T_RB (link k -> k, free brick i -> SDX_BODY_BRICK0 + i), static world -> -1 */
+  uint32_t* key;         /* u32 [N, SDX_MAX_CONTACTS]      identity = bits 0..27 of the SDX_T_WARM_KEYS entry, age nibble zero */
+  float*    point;       /* f32 [N, 3, SDX_MAX_CONTACTS]   env frame */
+  float*    normal;      /* f32 [N, 3, SDX_MAX_CONTACTS]   unit; the direction in which the normal impulse pushes side a */
+  float*    force;       /* f32 [N, 3, SDX_MAX_CONTACTS]   on side a (side b receives the negative), env axes: impulse of the last substep / h */
+  float*    separation;  /* f32 [N, SDX_MAX_CONTACTS]      the narrowphase's separation (negative: penetration) */
+} sdx_contact_report;
+int sdx_set_contact_report(sdx_handle h, const sdx_contact_report* report, void* stream);
+
+/* Per-body contact wrenches and sensor / filter force matrices from a report (acquire_net_contact_force_tensor for all SDX_BODIES rows
+ * plus the torque a force sensor would feel; IsaacLab's ContactSensor.force_matrix_w): one launch on `stream`, part of no step.  It reads
+ * the report's count / body / point / force (count[e] clamped to [0, SDX_MAX_CONTACTS]; columns beyond it are never touched and may hold
+ * anything) and the positions of the CURRENT SDX_T_RB.
+ *   net_dev   f32 [N, SDX_BODIES, 6] or NULL: per body row the sum of the contact forces on it (side a +force, side b -force), then the
+ *             sum of (point - x) x force about the position x of its SDX_T_RB row.  Rows of bodies without contacts are +0.
+ *   pair_dev  f32 [N, n_sensor, n_filter, 3] or NULL: the force on sensor body s from filter body f: +force where (a, b) = (s, f),
+ *             -force where (a, b) = (f, s).  A filter row that no contact side can have matches nothing.
+ * Deterministic: every sum runs over ascending contact index with a fixed combination tree, without float atomics; two calls on the same
+ * report agree bit for bit.  SDX_ERR_INVALID with a message: report NULL or its count / body / point / force NULL; both outputs NULL;
+ * pair_dev without pairs; n_sensor / n_filter outside 0..32; a sensor row outside [0, SDX_BODIES). */
+typedef struct {
+  int32_t n_sensor, n_filter;      /* 0..32 each */
+  int32_t sensor_body[32];         /* rows of SDX_T_RB */
+  int32_t filter_body[32];         /* rows of SDX_T_RB, or -1 = the static world */
+} sdx_contact_pairs;
+int sdx_contact_wrenches(sdx_handle h, const sdx_contact_report* report, float* net_dev, const sdx_contact_pairs* pairs, float* pair_dev,
+                         void* stream);
+
 /* View camera: depth, label and colour images of the listed envs from the current SDX_T_ROOT / SDX_T_RB, for
  * looking at the engine; no task's step launches it.  k_seg_camera's pinhole model: f = normalize(target - pos), r = normalize(f x up),
  * u = r x f, ray through pixel centre (row, col) d = f + r px + u py, row 0 on top; since d . f = 1 the depth of a hit is its distance
@@ -534,7 +579,8 @@ int sdx_render_view(sdx_handle h, const sdx_view_desc* view, const int32_t* env_
  * NOT part of any snapshot: the logs (the harvest, pile and T-value rings with their counts and keys, SDX_T_CONTACT_STATS, SDX_T_DEBUG),
  * the launch-order hints of k_physics, and configuration (loaded piles, T-value weights, the randomization descriptor and whether it is
  * on), a pending external wrench, pending joint actuation (sdx_apply_dof_forces) and the caller-owned buffers of sdx_set_force_perturbation (the task's rb_forces and
- * random_force_prob: copy them beside the snapshot).  A restore_all rewinds the step counter: ring rows appended afterwards can REPEAT the keys of rows appended before the restore.
+ * random_force_prob: copy them beside the snapshot), and the contact report (sdx_set_contact_report: whether it is armed, and the caller's
+ * buffers; the next physics launch rewrites them).  A restore_all rewinds the step counter: ring rows appended afterwards can REPEAT the keys of rows appended before the restore.
  * Env classes: a row may only be put into an env of the class it came from - env & 7 (the target brick), and additionally env % 3 for
  * InsertSim (the base plate and the insertion site); the RNG keys stay with the destination env.  Each row records its source env.
  * restore and clone never fault on a bad entry: they skip it and count it in sdx_state_stats - [0] env id or row index out of range

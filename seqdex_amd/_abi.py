@@ -102,6 +102,20 @@ class OscAttr(C.Structure):
                 ("compensate_bias", i32)]
 
 
+MAX_CONTACTS = 1536                   # SDX_MAX_CONTACTS
+
+
+class ContactReportStruct(C.Structure):
+    """sdx_contact_report: seven caller-owned device pointers"""
+    _fields_ = [("count", C.c_void_p), ("body", C.c_void_p), ("key", C.c_void_p), ("point", C.c_void_p), ("normal", C.c_void_p),
+                ("force", C.c_void_p), ("separation", C.c_void_p)]
+
+
+class ContactPairs(C.Structure):
+    """sdx_contact_pairs"""
+    _fields_ = [("n_sensor", i32), ("n_filter", i32), ("sensor_body", i32 * 32), ("filter_body", i32 * 32)]
+
+
 class OptState(C.Structure):
     """sdxp_opt_state"""
     _fields_ = [("rms_count", C.c_double), ("ac_t", i32), ("cv_t", i32), ("ac_lr", f32), ("cv_lr", f32)]
@@ -124,7 +138,7 @@ SDX_EXPORTS = ["sdx_create", "sdx_destroy", "sdx_tensor", "sdx_load_initial_stat
                "sdx_step", "sdx_pre_physics", "sdx_simulate", "sdx_post_physics", "sdx_compute_observations",
                "sdx_reset_idx", "sdx_set_indexed", "sdx_refresh_kinematics", "sdx_render_segmentation", "sdx_num_envs", "sdx_last_error",
                "sdx_set_randomization", "sdx_set_noise", "sdx_render_view", "sdx_apply_rigid_body_forces", "sdx_set_force_perturbation",
-               "sdx_apply_dof_forces", "sdx_dof_dynamics", "sdx_osc_torques",
+               "sdx_apply_dof_forces", "sdx_dof_dynamics", "sdx_osc_torques", "sdx_set_contact_report", "sdx_contact_wrenches",
                "sdx_state_create", "sdx_state_destroy", "sdx_state_save", "sdx_state_restore", "sdx_state_save_all", "sdx_state_restore_all",
                "sdx_state_clone", "sdx_state_stats",
                "sdxp_create", "sdxp_destroy", "sdxp_tensor", "sdxp_param_count", "sdxp_act", "sdxp_store_rewards",
@@ -166,6 +180,8 @@ def load_library():
     lib.sdx_apply_dof_forces.argtypes = [vp, vp, C.c_uint32, vp]
     lib.sdx_dof_dynamics.argtypes = [vp, vp, vp, vp, vp]
     lib.sdx_osc_torques.argtypes = [vp, C.POINTER(OscAttr), vp, vp, vp, vp]
+    lib.sdx_set_contact_report.argtypes = [vp, C.POINTER(ContactReportStruct), vp]
+    lib.sdx_contact_wrenches.argtypes = [vp, C.POINTER(ContactReportStruct), vp, C.POINTER(ContactPairs), vp, vp]
     lib.sdx_state_create.argtypes = [vp, i32, C.POINTER(vp)]
     lib.sdx_state_destroy.argtypes = [vp]
     lib.sdx_state_save.argtypes = [vp, vp, vp, vp, i32, vp]

@@ -81,7 +81,7 @@
   X(tv_fail, SDX_TV_LOG_SLOTS * 4, LOG, 0, TENSOR(TV_FAILURE, F32, SDX_TV_LOG_SLOTS, 4))                                                   \
   X(tv_count, 2, LOG, 0, TENSOR(TV_COUNT, I32, 2))                                                                                         \
   X(tv_key, 2 * SDX_TV_LOG_SLOTS, LOG, 0, TENSOR(TV_KEYS, I64, 2, SDX_TV_LOG_SLOTS))                                                       \
-  X(cscratch, 4, SCRATCH, 0, NO_TENSOR) /* (contact rows now live in LDS / registers) */                                                   \
+  X(cscratch, 16, SCRATCH, 0, NO_TENSOR) /* the pointer table of an armed contact report (a sdx_contact_report: 56 bytes) */               \
   X(order, N, SCRATCH, 0, NO_TENSOR)                                                                                                       \
   X(cost, N, SCRATCH, 0, NO_TENSOR)                                                                                                        \
   X(tvt_h, search ? N * (1024 + 512 + 128 + 4) : 0, SCRATCH, 0, NO_TENSOR)                                                                 \

@@ -36,6 +36,7 @@ struct sdx_sim {
   sdx_force_perturb_attr fp{};
   float fp_factor = 1.0f;
   float *fp_forces = nullptr, *fp_prob = nullptr;
+  sdx_contact_report report{};   // sdx_set_contact_report: armed while report.count != nullptr (the caller's buffers)
   float* act_pre = nullptr;   // [N,23] the clamped and noised actions of this step (scratch of k_noise -> k_pre_physics)
   SdxStateTab st_tab{};       // what an env's state is (sdx_state.h); d_st_tab: its device copy
   SdxStateTab* d_st_tab = nullptr;
@@ -108,15 +109,16 @@ static void post_physics_step(sdx_sim* h, hipStream_t st) {
 }
 
 // the physics launch a pending external wrench and pending joint actuation apply to (sdx_simulate; sdx_step's own, not the settling launches of a reset event): the
-// caller's pointers travel by value in that launch's copy of the buffer table, and the wrench is forgotten
+// caller's pointers travel by value in that launch's copy of the buffer table, and the wrench is forgotten.  An armed contact report
+// (sdx_set_contact_report) travels by value too, as an argument of its own, with every such launch until it is disarmed.
 static void physics_step(sdx_sim* h, hipStream_t st) {
-  if (!h->ext_force && !h->ext_torque && !h->dof_force && !h->dof_off) { sdxk_physics(h->d_const, &h->buf, st); return; }
+  if (!h->ext_force && !h->ext_torque && !h->dof_force && !h->dof_off) { sdxk_physics_report(h->d_const, &h->buf, &h->report, st); return; }
   SdxBuf b = h->buf;
   b.ext_force = h->ext_force; b.ext_torque = h->ext_torque; b.ext_space = h->ext_space;
   b.dof_force = h->dof_force; b.dof_off = h->dof_off;
   h->ext_force = h->ext_torque = h->dof_force = nullptr;
   h->dof_off = 0;
-  sdxk_physics(h->d_const, &b, st);
+  sdxk_physics_report(h->d_const, &b, &h->report, st);
 }
 // the random pushes of this step (sdx_set_force_perturbation), before the step's resets clear the flags: the task's rb_forces become the
 // pending wrench, replacing the caller's own
@@ -605,6 +607,32 @@ extern "C" int sdx_osc_torques(sdx_handle h, const sdx_osc_attr* attr, const flo
   sdxk_osc_torques(h->d_const, &h->buf, attr, dpose_dev, torques_dev, wrench_dev, (hipStream_t)stream);
   return check_launch(h, "sdx_osc_torques");
 }
+extern "C" int sdx_set_contact_report(sdx_handle h, const sdx_contact_report* report, void* stream) {
+  if (!h) return SDX_ERR_INVALID;
+  (void)stream;
+  if (!report) { h->report = sdx_contact_report{}; return SDX_OK; }
+  if (!report->count) { h->err = "sdx_set_contact_report: report->count is NULL (pass report = NULL to disarm)"; return SDX_ERR_INVALID; }
+  h->report = *report;
+  return SDX_OK;
+}
+extern "C" int sdx_contact_wrenches(sdx_handle h, const sdx_contact_report* report, float* net_dev, const sdx_contact_pairs* pairs, float* pair_dev,
+                                    void* stream) {
+  if (!h) return SDX_ERR_INVALID;
+  const char* why = nullptr;
+  if (!report) why = "sdx_contact_wrenches: report is NULL";
+  else if (!report->count || !report->body || !report->point || !report->force) why = "sdx_contact_wrenches: the report's count, body, point and force must not be NULL";
+  else if (!net_dev && !pair_dev) why = "sdx_contact_wrenches: net_dev and pair_dev are both NULL";
+  else if (pair_dev && !pairs) why = "sdx_contact_wrenches: pair_dev without pairs";
+  else if (pairs) {
+    if (pairs->n_sensor < 0 || pairs->n_sensor > 32 || pairs->n_filter < 0 || pairs->n_filter > 32) why = "sdx_contact_wrenches: n_sensor and n_filter must lie in 0..32";
+    else
+      for (int i = 0; i < pairs->n_sensor; ++i)
+        if (pairs->sensor_body[i] < 0 || pairs->sensor_body[i] >= SDX_BODIES) why = "sdx_contact_wrenches: a sensor body is not a row of SDX_T_RB in [0, SDX_BODIES)";
+  }
+  if (why) { h->err = why; return SDX_ERR_INVALID; }
+  sdxk_contact_wrenches(&h->buf, report, net_dev, pairs, pair_dev, (hipStream_t)stream);
+  return check_launch(h, "sdx_contact_wrenches");
+}
 extern "C" int sdx_set_force_perturbation(sdx_handle h, const sdx_force_perturb_attr* attr, float* rb_forces_dev, float* prob_dev, void* stream) {
   if (!h) return SDX_ERR_INVALID;
   if (!attr || !(attr->force_scale > 0.0f || std::isnan(attr->force_scale))) {   // off (a NaN scale is an error, below)
@@ -729,7 +757,7 @@ extern "C" int sdx_step(sdx_handle h, const float* actions_dev, void* stream) {
   physics_step(h, st);   // controlFrequencyInv = 1 (EG:18); with the pending external wrench, if any
   if (kind == SDX_TASK_SEARCH && (float)(p0 + 1) >= h->h_const.sc.max_episode_length - 1.0f) {   // SE:992-1019: park the hand, one more step, render
     sdxk_search_set_hand(h->d_const, &h->buf, nullptr, 1, st);
-    sdxk_physics(h->d_const, &h->buf, st);
+    physics_step(h, st);   // (nothing is pending any more; an armed contact report describes this launch, as SDX_T_CONTACT does)
     sdxk_seg_camera(h->d_const, &h->buf, st);
   }
   post_physics_step(h, st);

@@ -39,7 +39,8 @@ struct SdxBuf {
   float* piles;            // [8,K,132,13]
   float* tv_w;             // packed + transposed T-value weights
   float* cam_rot;          // [N,4] camera-frame target quaternion (input of the T-value MLP)
-  float* cscratch;         // [N, SDX_CFIELDS, SDX_MAXC]
+  float* cscratch;         // [16] device copy of the sdx_contact_report (seven pointers) that the NEXT k_physics<.. | SDX_PHYS_REPORT> launch writes: filled by
+                           // k_report_table in front of it (include/seqdex.h sdx_set_contact_report); nothing else reads it
   float* stat;             // [2][2] double-buffered (num_resets, finished successes) for cons_successes
   uint32_t* step_count;    // device counter, incremented by the post-physics kernel
   long long* dbg;          // [64] phase time stamps of env dbg_env (profiling aid)
@@ -90,6 +91,7 @@ struct SdxBuf {
   uint32_t dof_off;        // bit j: the PD drive of dof j is off
   const float* dof_force;  // [N, SDX_NDOF] or nullptr
 };
+static_assert(SDX_MAX_CONTACTS == SDX_MAXC, "the rows of a contact report hold what a solve can take");
 #define SDX_DR_SLOTS 287   // RNG slots per env: 4 x 23 DOF, 2 x 24 link, 2 x 72 brick quantities (284), gravity in slots 284..286 of env 0
 
 // An empty asm the compiler must assume rewrites x: values derived from x afterwards (LDS addresses of the same rows in every

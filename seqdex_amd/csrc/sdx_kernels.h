@@ -15,6 +15,8 @@ void sdxk_scripted_grasp(const SdxConst* C, const SdxBuf* B, float* state, float
 void sdxk_set_indexed(const SdxBuf* B, int id, const float* src, const int32_t* ids, int n, hipStream_t st);
 // sdx_physics.hip
 void sdxk_physics(const SdxConst* C, const SdxBuf* B, hipStream_t st);
+// the same launch with an armed contact report (sdx_set_contact_report): its last substep also writes the caller's buffers
+void sdxk_physics_report(const SdxConst* C, const SdxBuf* B, const sdx_contact_report* report, hipStream_t st);
 void sdxk_kinematics(const SdxConst* C, const SdxBuf* B, hipStream_t st);
 // sdx_camera.hip
 void sdxk_seg_camera(const SdxConst* C, const SdxBuf* B, hipStream_t st);
@@ -27,6 +29,9 @@ void sdxk_noise(const SdxConst* C, const SdxBuf* B, const sdx_noise_attr* attr, 
 void sdxk_dof_dynamics(const SdxConst* C, const SdxBuf* B, float* mass, float* bias, float* drive, hipStream_t st);
 // sdx_physics.hip k_osc_torques: torques [N,23] and wrench [N,6] (device, wrench may be nullptr) from the current dof and dpose [N,6]
 void sdxk_osc_torques(const SdxConst* C, const SdxBuf* B, const sdx_osc_attr* attr, const float* dpose, float* torques, float* wrench, hipStream_t st);
+// sdx_physics.hip k_contact_wrenches: net [N,165,6] and pair [N,n_sensor,n_filter,3] (device, either may be nullptr; pairs is read only
+// with pair) from the caller's contact report and the current body positions
+void sdxk_contact_wrenches(const SdxBuf* B, const sdx_contact_report* report, float* net, const sdx_contact_pairs* pairs, float* pair, hipStream_t st);
 // mode SDX_FP_STEP: the whole rule for one step (resets from reset_buf); SDX_FP_RESET: rows <- 0 and a new probability for the envs of mask
 // (nullptr: every env); SDX_FP_DRAW: a new probability for every env, rows untouched.  factor: decay^(dt / decay_interval)
 enum { SDX_FP_STEP = 0, SDX_FP_RESET = 1, SDX_FP_DRAW = 2 };

@@ -47,6 +47,60 @@ __device__ __forceinline__ void load_rows(const sdx_scene_desc& sc, PhysLds& S, 
   if (WARM) for (int i = tid; i < nold; i += NT) S.P[2][i] = __int_as_float((int)wkey[i]);
 }
 
+// ---- k_physics<.. | SDX_PHYS_REPORT>, last substep, beside load_rows(): the set-up columns of the contact report (include/seqdex.h
+// sdx_contact_report) from the staging rows the lane reads anyway - body pair, identity (S_CKEY, which collide()
+// writes whether or not the solver is warm), separation.  Before the barrier of csr_clear(), after which the staging rows are reused.
+// Column c is lane c % NT's: every store is coalesced.  The env's rows are addressed from an opaque copy of e (dr_row()): nothing of the
+// report lives outside this function.  A row of the body table -> a row of SDX_T_RB: brick i -> SDX_BODY_BRICK0 + i, link k -> k, world -> -1.
+__device__ __forceinline__ int report_body_row(int id) { return id < NF ? SDX_BODY_BRICK0 + id : (id != BODY_W ? id - NF : -1); }
+template <int NT, int CPT>
+__device__ __forceinline__ void report_setup(const sdx_contact_report* table, int e, PhysLds& S, int tid, int nc, const int (&ab)[CPT]) {
+  int ee = e;
+  SDX_OPAQUE_S(ee);
+  const size_t row = (size_t)ee * MAXC;
+  int32_t* const body = table->body;   // (the launch's pointers, from their device table: block-uniform loads, here and nowhere earlier)
+  uint32_t* const key = table->key;
+  float* const separation = table->separation;
+#pragma unroll
+  for (int q = 0; q < CPT; ++q) {
+    const int c = tid + q * NT;
+    if (c < nc) {
+      if (body) { body[2 * row + c] = report_body_row(ab[q] & 0xff); body[2 * row + MAXC + c] = report_body_row((ab[q] >> 8) & 0xff); }
+      if (key) key[row + c] = S_CKEY(S)[c] & 0x0fffffffu;
+      if (separation) separation[row + c] = S.P[0][c];
+    }
+  }
+}
+// ---- the same, beside solve_exit(): the result columns - point and normal (cp / cn live for the whole solve), the force on side a
+// (n lam0 + t1 lam1 + t2 lam2) / h with the basis contact_update() uses, and the count.  Two write sites, so that no register of the
+// report is alive across the solver loop.
+template <int NT, int CPT>
+__device__ __forceinline__ void report_result(const sdx_contact_report* table, int e, const PhysLds& S, int tid, int nc, float h, const float (&lam)[CPT][3]) {
+  int ee = e;
+  SDX_OPAQUE_S(ee);
+  const size_t row = (size_t)ee * 3 * MAXC;
+  float* const point = table->point;
+  float* const normal = table->normal;
+  float* const force = table->force;
+  int32_t* const count = table->count;
+#pragma unroll
+  for (int q = 0; q < CPT; ++q) {
+    const int c = tid + q * NT;
+    if (c < nc) {
+      const f3 p = F3(S.cp[0][c], S.cp[1][c], S.cp[2][c]), n = F3(S.cn[0][c], S.cn[1][c], S.cn[2][c]);
+      if (point) { point[row + c] = p.x; point[row + MAXC + c] = p.y; point[row + 2 * MAXC + c] = p.z; }
+      if (normal) { normal[row + c] = n.x; normal[row + MAXC + c] = n.y; normal[row + 2 * MAXC + c] = n.z; }
+      if (force) {
+        f3 t1, t2;
+        tangents(n, &t1, &t2);
+        const f3 f = (n * lam[q][0] + t1 * lam[q][1] + t2 * lam[q][2]) * (1.0f / h);   // (x 1 / h, as SDX_T_CONTACT is formed)
+        force[row + c] = f.x; force[row + MAXC + c] = f.y; force[row + 2 * MAXC + c] = f.z;
+      }
+    }
+  }
+  if (tid == 0) count[ee] = nc;
+}
+
 // ---- CSR of contact sides per body (bricks AND robot links), ascending contact index inside a body: csr_clear() .. csr_rank()
 // stamps 23 -> 24, first part: zero the counts (and, in the last substep, the links' net contact impulses cf)
 template <int NT>
@@ -771,9 +825,12 @@ __device__ __forceinline__ void solve_exit(PhysLds& S, int tid, int nc, int qpar
 // in the previous solve (same pair, direction and sample) starts from sc.warm_start x the impulses it ended with; iteration -1 of the
 // loop below spreads those impulses over the bodies with the gather machinery of a normal iteration.  WARM is a template parameter:
 // the default (cold) solver carries none of this code (it cost 2.6 % of the kernel as a run-time switch).
-template <int NT, bool WARM, bool DR = false>
+// REPORT (k_physics<.. | SDX_PHYS_REPORT>): the last substep also writes this env's columns of the contact report whose pointers stand in
+// the device table rp (report_setup(), report_result()); like WARM a template parameter, so that the kernels without the flag carry none of it.
+template <int NT, bool WARM, bool DR = false, bool REPORT = false>
 __device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, float h, bool last_substep, long long* dbg,
-                                      int32_t* wcount, uint32_t* wkey, float* wlam, int abl_bits, const float* bfr = nullptr, const float* lfr = nullptr) {
+                                      int32_t* wcount, uint32_t* wkey, float* wlam, int abl_bits, const float* bfr = nullptr, const float* lfr = nullptr,
+                                      const sdx_contact_report* rp = nullptr, int e = 0) {
   constexpr int CPT = MAXC / NT;   // contact rows owned by one lane
   static_assert(CPT * NT == MAXC, "NT must divide SDX_MAXC");
   static_assert(CPT * 11 <= 64 && MAXC < 0x7ff, "11-bit cache positions of a lane's contacts in one 64-bit word");
@@ -791,6 +848,7 @@ __device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, fl
   int nold = WARM ? *wcount : 0;   // block-uniform
   if (nold > MAXC) nold = MAXC;
   load_rows<NT, WARM>(sc, S, tid, nc, h, nold, wkey, R);
+  if (REPORT) { if (last_substep) report_setup<NT>(rp, e, S, tid, nc, R.ab); }
   SSTAMP(23);
   csr_clear<NT>(S, tid, last_substep);
   uint64_t wmatch;
@@ -837,4 +895,5 @@ __device__ __forceinline__ void solve(const SdxConst* C, PhysLds& S, int tid, fl
     SSTAMP(22);
   }
   solve_exit<NT, WARM>(S, tid, nc, qpar, R.lam, wcount, wlam);
+  if (REPORT) { if (last_substep) report_result<NT>(rp, e, S, tid, nc, h, R.lam); }
 }

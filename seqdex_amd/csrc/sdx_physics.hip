@@ -23,7 +23,7 @@
 //     surviving body pairs are expanded into the box pairs of the two compounds (consecutive candidates per lane, separating-axis test);
 //     narrowphase: lane = box pair picks the samples, lane = contact computes their geometry.
 //
-// One translation unit in nine files.  The device code of the phases lives in headers that only this file includes, in this order (each
+// One translation unit in ten files.  The device code of the phases lives in headers that only this file includes, in this order (each
 // may use what the ones before it define; none forward-declares a function of another):
 //   sdx_phys_lds.h      constants, wave hand-offs (WAVE_SYNC, WAVES_BARRIER, WAVE_SIGNAL / WAVES_WAIT), PhysLds and the table of its overlays,
 //                       Box, the clock / ablation macros
@@ -32,9 +32,11 @@
 //   sdx_phys_robot.h    A / B: inertia_mul, twists_wave0, fk_wave0, mass_matrix
 //   sdx_phys_collide.h  D: collide
 //   sdx_phys_solve.h    E: solve and its stages: load_rows, warm_match, csr_clear .. csr_rank, link_inertia, row_weights, pass_setup,
-//                       loop_registers; per pass contact_update [AC], gather [D], robot_section; solve_exit
+//                       loop_registers; per pass contact_update [AC], gather [D], robot_section; solve_exit; the contact report's two
+//                       write sites report_setup, report_result
 //   sdx_phys_dynamics.h k_dof_dynamics: mass matrix, bias and drive torques outside any step (sdx_dof_dynamics)
 //   sdx_phys_osc.h      k_osc_torques: operational-space torques of the arm outside any step (sdx_osc_torques)
+//   sdx_phys_report.h   k_contact_wrenches: per-body wrenches and sensor / filter forces from a contact report (sdx_contact_wrenches)
 //   this file           write_kinematics, load_constants, k_physics (C the drive and F the integration are in its body), k_order,
 //                       k_kinematics, the launchers
 #include <stdlib.h>
@@ -49,6 +51,7 @@
 #include "sdx_phys_solve.h"
 #include "sdx_phys_dynamics.h"
 #include "sdx_phys_osc.h"
+#include "sdx_phys_report.h"
 
 // ---------------------------------------------------------------- outputs shared by step and refresh
 template <int NT>
@@ -142,7 +145,13 @@ __device__ __forceinline__ void load_constants(const SdxConst* C, PhysLds& S, in
 // k_physics<.. | SDX_PHYS_FORCE>: the external wrench of include/seqdex.h sdx_apply_rigid_body_forces acts on the
 // free bricks beside gravity and on the robot links beside their velocity-product wrenches.  A second flag bit, for the same reason.
 #define SDX_PHYS_FORCE 2
-#define SDX_PHYS_FLAGS (SDX_PHYS_DR | SDX_PHYS_FORCE)
+// k_physics<.. | SDX_PHYS_REPORT>: the last substep's solve also writes the contact report of include/seqdex.h sdx_set_contact_report (DESIGN.md
+// section 24) into the caller's buffers.  Their seven pointers are read from B.cscratch, a device copy of the struct that k_report_table
+// (sdx_phys_report.h) writes in front of every such launch: SdxBuf does not grow, so no kernel that takes arguments behind the buffer
+// table sees them move, and the pointers are loaded where they are used instead of living in the argument registers.  A third flag
+// bit, for the same reason as the other two: k_physics<512 .. 515> keep symbol and code.
+#define SDX_PHYS_REPORT 4
+#define SDX_PHYS_FLAGS (SDX_PHYS_DR | SDX_PHYS_FORCE | SDX_PHYS_REPORT)
 // k_physics<.. | SDX_PHYS_DR>: row e of one of the SDX_T_DR_* tensors, addressed from an opaque copy of e at the point of use (nothing is
 // hoisted to the kernel's entry and kept alive over the substeps)
 __device__ __forceinline__ const float* dr_row(const float* base, int e, int width, int off) {
@@ -190,6 +199,7 @@ __global__ __launch_bounds__(NTD & ~SDX_PHYS_FLAGS, 2 * (NTD & ~SDX_PHYS_FLAGS) 
   constexpr int NT = NTD & ~SDX_PHYS_FLAGS;
   constexpr bool DR = (NTD & SDX_PHYS_DR) != 0;
   constexpr bool FORCE = (NTD & SDX_PHYS_FORCE) != 0;
+  constexpr bool REPORT = (NTD & SDX_PHYS_REPORT) != 0;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   PhysLds& S = *reinterpret_cast<PhysLds*>(smem);
   // launch order: B.order lists the envs by the cost of their previous step, longest first (k_order below)
@@ -355,9 +365,9 @@ __global__ __launch_bounds__(NTD & ~SDX_PHYS_FLAGS, 2 * (NTD & ~SDX_PHYS_FLAGS) 
     }
     PSTAMP(4);
     if (scl.warm_start > 0.0f)
-      solve<NT, true, DR>(Cs, S, tl, h, sub == nsub - 1, (sub == 0 && e == B.dbg_env) ? B.dbg : nullptr, B.wcount + e, B.wkey + (size_t)e * MAXC, B.wlam + (size_t)e * 3 * MAXC, abl_bits, DR_ROW(dr_brick, 2 * NF, NF), DR_ROW(dr_link, 2 * NL, NL));
+      solve<NT, true, DR, REPORT>(Cs, S, tl, h, sub == nsub - 1, (sub == 0 && e == B.dbg_env) ? B.dbg : nullptr, B.wcount + e, B.wkey + (size_t)e * MAXC, B.wlam + (size_t)e * 3 * MAXC, abl_bits, DR_ROW(dr_brick, 2 * NF, NF), DR_ROW(dr_link, 2 * NL, NL), REPORT ? reinterpret_cast<const sdx_contact_report*>(B.cscratch) : nullptr, e);
     else
-      solve<NT, false, DR>(Cs, S, tl, h, sub == nsub - 1, (sub == 0 && e == B.dbg_env) ? B.dbg : nullptr, nullptr, nullptr, nullptr, abl_bits, DR_ROW(dr_brick, 2 * NF, NF), DR_ROW(dr_link, 2 * NL, NL));
+      solve<NT, false, DR, REPORT>(Cs, S, tl, h, sub == nsub - 1, (sub == 0 && e == B.dbg_env) ? B.dbg : nullptr, nullptr, nullptr, nullptr, abl_bits, DR_ROW(dr_brick, 2 * NF, NF), DR_ROW(dr_link, 2 * NL, NL), REPORT ? reinterpret_cast<const sdx_contact_report*>(B.cscratch) : nullptr, e);
     PSTAMP(5);
     // F: integrate
     if (tl < ND) {
@@ -503,20 +513,35 @@ static void physics_init() {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_physics<512 | SDX_PHYS_DR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PhysLds));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_physics<512 | SDX_PHYS_FORCE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PhysLds));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_physics<512 | SDX_PHYS_DR | SDX_PHYS_FORCE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PhysLds));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_physics<512 | SDX_PHYS_REPORT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PhysLds));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_physics<512 | SDX_PHYS_REPORT | SDX_PHYS_DR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PhysLds));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_physics<512 | SDX_PHYS_REPORT | SDX_PHYS_FORCE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PhysLds));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_physics<512 | SDX_PHYS_REPORT | SDX_PHYS_DR | SDX_PHYS_FORCE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PhysLds));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_kinematics), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PhysLds));
   }
 }
 extern "C" int sdxk_physics_threads() { return 512; }
-extern "C" void sdxk_physics(const SdxConst* C, const SdxBuf* B, hipStream_t st) {
+// report: the armed contact report of this launch (sdx_set_contact_report), or nullptr / count == nullptr: none - the kernels without the flag run
+extern "C" void sdxk_physics_report(const SdxConst* C, const SdxBuf* B, const sdx_contact_report* report, hipStream_t st) {
   physics_init();
   // an external wrench (sdx_apply_rigid_body_forces), actuation torques or drives that are off (sdx_apply_dof_forces) ride with this launch
   const bool force = B->ext_force || B->ext_torque || B->dof_force || B->dof_off;
-  if (force && B->dr_on) hipLaunchKernelGGL(k_physics<512 | SDX_PHYS_DR | SDX_PHYS_FORCE>, dim3(B->N), dim3(512), sizeof(PhysLds), st, C, *B);
+  if (report && report->count && B->cscratch) {   // the same four, with the report's stores in the last substep
+    // the pointers of THIS launch, by value into the device table the kernel reads them from (stream-ordered: a later call that arms other
+    // buffers or disarms does not reach a launch that is already enqueued)
+    hipLaunchKernelGGL(k_report_table, dim3(1), dim3(64), 0, st, *report, reinterpret_cast<sdx_contact_report*>(B->cscratch));
+    if (force && B->dr_on) hipLaunchKernelGGL(k_physics<512 | SDX_PHYS_REPORT | SDX_PHYS_DR | SDX_PHYS_FORCE>, dim3(B->N), dim3(512), sizeof(PhysLds), st, C, *B);
+    else if (force) hipLaunchKernelGGL(k_physics<512 | SDX_PHYS_REPORT | SDX_PHYS_FORCE>, dim3(B->N), dim3(512), sizeof(PhysLds), st, C, *B);
+    else if (B->dr_on) hipLaunchKernelGGL(k_physics<512 | SDX_PHYS_REPORT | SDX_PHYS_DR>, dim3(B->N), dim3(512), sizeof(PhysLds), st, C, *B);
+    else hipLaunchKernelGGL(k_physics<512 | SDX_PHYS_REPORT>, dim3(B->N), dim3(512), sizeof(PhysLds), st, C, *B);
+  }
+  else if (force && B->dr_on) hipLaunchKernelGGL(k_physics<512 | SDX_PHYS_DR | SDX_PHYS_FORCE>, dim3(B->N), dim3(512), sizeof(PhysLds), st, C, *B);
   else if (force) hipLaunchKernelGGL(k_physics<512 | SDX_PHYS_FORCE>, dim3(B->N), dim3(512), sizeof(PhysLds), st, C, *B);
   else if (B->dr_on) hipLaunchKernelGGL(k_physics<512 | SDX_PHYS_DR>, dim3(B->N), dim3(512), sizeof(PhysLds), st, C, *B);   // domain randomization on
   else hipLaunchKernelGGL(k_physics<512>, dim3(B->N), dim3(512), sizeof(PhysLds), st, C, *B);
   if (B->order && B->cost) hipLaunchKernelGGL(k_order, dim3(1), dim3(1024), 0, st, *B);
 }
+extern "C" void sdxk_physics(const SdxConst* C, const SdxBuf* B, hipStream_t st) { sdxk_physics_report(C, B, nullptr, st); }
 extern "C" void sdxk_kinematics(const SdxConst* C, const SdxBuf* B, hipStream_t st) {
   physics_init();
   hipLaunchKernelGGL(k_kinematics, dim3(B->N), dim3(64), sizeof(PhysLds), st, C, *B);
@@ -529,4 +554,9 @@ extern "C" void sdxk_osc_torques(const SdxConst* C, const SdxBuf* B, const sdx_o
                                  hipStream_t st) {
   if (B->dr_on) hipLaunchKernelGGL(k_osc_torques<true>, dim3(B->N), dim3(DYN_NT), 0, st, C, *B, *attr, dpose, torques, wrench);
   else hipLaunchKernelGGL(k_osc_torques<false>, dim3(B->N), dim3(DYN_NT), 0, st, C, *B, *attr, dpose, torques, wrench);
+}
+extern "C" void sdxk_contact_wrenches(const SdxBuf* B, const sdx_contact_report* report, float* net, const sdx_contact_pairs* pairs, float* pair,
+                                      hipStream_t st) {
+  sdx_contact_pairs none = {};
+  hipLaunchKernelGGL(k_contact_wrenches, dim3(B->N), dim3(CW_NT), 0, st, B->rb, *report, net, pair ? *pairs : none, pair);
 }

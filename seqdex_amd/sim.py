@@ -434,6 +434,25 @@ class SdxSim:
                                              C.c_void_p(w.data_ptr()) if w is not None else None, self._stream_or_none()))
         return (u, w) if wrench else u
 
+    # ------------------------------------------------------------------ contact report (include/seqdex.h)
+    def contact_report(self, enable=True):
+        """gym.get_env_rigid_contacts on the device: allocates a contact_report.ContactReport (count, body, key, point, normal, force,
+        separation of every contact of a step's last solve), arms it and returns it; while armed every simulate() / step() rewrites it
+        on its stream and changes nothing else.  A second call returns the armed report.  enable=False disarms and drops it (returns
+        None); close() disarms too.  Not part of a snapshot."""
+        from .contact_report import ContactReport
+        rep = getattr(self, "_contact_report", None)
+        if not enable:
+            if getattr(self, "h", None) is not None and self.h.value:
+                self._check(self.lib.sdx_set_contact_report(self.h, None, self._stream_or_none()))
+            self._contact_report = None
+            return None
+        if rep is None:
+            rep = ContactReport(self)
+            self._check(self.lib.sdx_set_contact_report(self.h, C.byref(rep.struct), self._stream_or_none()))
+            self._contact_report = rep
+        return rep
+
     # ------------------------------------------------------------------ sim snapshots (include/seqdex.h sdx_state_*, DESIGN.md section 20)
     def _stream_or_none(self):
         return _stream_ptr(self.device) if self.device.type == "cuda" else None
@@ -495,6 +514,8 @@ class SdxSim:
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h.value:
+            if getattr(self, "_contact_report", None) is not None:
+                self.contact_report(False)
             self._tensors.clear()
             self.lib.sdx_destroy(self.h)
             self.h = C.c_void_p()

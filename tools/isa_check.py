@@ -3,7 +3,8 @@ solver's iteration loop (the ISA between the source lines of the loop head and o
 per-pass stage functions the loop calls: the lines of the same file between the comments `// isa_check: loop stage begin` and
 `// isa_check: loop stage end` (any number of such ranges).  The loop is looked for in sdx_physics.hip and the sdx_phys_*.h it includes;
 code inlined from any other line of those files is not part of the loop.
-usage: python tools/isa_check.py [--randomize] [--force] [extra hipcc flags...]      (cross-compiles; no GPU needed)
+usage: python tools/isa_check.py [--randomize] [--force] [--report] [extra hipcc flags...]      (cross-compiles; no GPU needed)
+--report: ... for the contact-report variant k_physics<512 | SDX_PHYS_REPORT> (516; with --randomize / --force 517 .. 519)
 --randomize: the same report for the domain-randomization variant k_physics<512 | SDX_PHYS_DR> (= k_physics<513>)
 --force: ... for the external-wrench variant k_physics<512 | SDX_PHYS_FORCE> (514; with --randomize 515)
 --osc: registers, scratch and occupancy of k_osc_torques<false> and k_osc_torques<true> (sdx_phys_osc.h) instead, nothing about the loop"""
@@ -22,12 +23,15 @@ if RANDOMIZE:
 FORCE = "--force" in sys.argv
 if FORCE:
     sys.argv.remove("--force")
+REPORT = "--report" in sys.argv
+if REPORT:
+    sys.argv.remove("--report")
 OSC = "--osc" in sys.argv
 if OSC:
     sys.argv.remove("--osc")
 OSC_TAGS = [("k_osc_torques<false>", "k_osc_torquesILb0E"), ("k_osc_torques<true>", "k_osc_torquesILb1E")]
 KEYS = ("VGPRs:", "AGPRs:", "ScratchSize [bytes/lane]:", "SGPRs Spill:", "VGPRs Spill:", "Occupancy [waves/SIMD]:", "LDS Size [bytes/block]:")
-TAG = "k_physicsILi%dE" % (512 + (1 if RANDOMIZE else 0) + (2 if FORCE else 0))
+TAG = "k_physicsILi%dE" % (512 + (1 if RANDOMIZE else 0) + (2 if FORCE else 0) + (4 if REPORT else 0))
 KERN = "_Z9%sEvPK8SdxConst6SdxBuf" % TAG
 
 # the unit's files: the .hip and the private headers it includes; the one with the loop markers is where the loop's lines are counted
