@@ -481,6 +481,50 @@ typedef struct {
 } sdx_osc_attr;
 int sdx_osc_torques(sdx_handle h, const sdx_osc_attr* attr, const float* dpose_dev, float* torques_dev, float* wrench_dev, void* stream);
 
+/* Pose solver: the 23 joint angles that put the hand base at a pose and the four fingertips at points, by damped
+ * least squares iterated inside ONE launch on `stream`, part of no step.  It reads SDX_T_DOF positions only when q0_dev is NULL, and rows
+ * 2 and 3 of SDX_T_DR_DOF while randomization is on: the limits it honours are the ones the physics enforces (the scene's lower / upper
+ * otherwise).  It writes the caller's buffers only; q0_dev and q_out_dev may be the same buffer.  Caller-owned device buffers:
+ *   q0_dev        f32 [N, SDX_NDOF] or NULL   start configuration (NULL: the positions of SDX_T_DOF)
+ *   base_pos_dev  f32 [N, 3]                  hand-base target position, env frame          (may be NULL when bit 0 is clear)
+ *   base_quat_dev f32 [N, 4] xyzw             hand-base target orientation, as an SDX_T_RB row holds it (may be NULL when bit 0 is clear)
+ *   tip_pos_dev   f32 [N, 4, 3]               fingertip targets ff, mf, rf, th, env frame   (may be NULL when bits 1..4 are clear)
+ *   q_out_dev     f32 [N, SDX_NDOF]           the solution
+ *   err_out_dev   f32 [N, 6] or NULL          error norms at q_out from a final forward kinematics: |position error| and |rotation error|
+ *                                             of the base, |position error| of the four tips; +0.0f for a task that is not selected
+ *   info_out_dev  i32 [N, 6] or NULL          column 0: bit t set = task t met its tolerance (the bits of task_mask); column 1: iterations
+ *                                             of the arm; columns 2..5: iterations of each finger
+ * The law, per env.  Forward kinematics and link axes are those of sdx_refresh_kinematics: q_out written to SDX_T_DOF and refreshed shows
+ * the solved pose in SDX_T_RB.  With p_k, R_k the frame of link k and a_k the world axis of its joint:
+ *   stage 1 (bit 0), on DOFs 0..6, from q <- q0, up to max_iters times:
+ *     e  = [target_pos - p7 ; r],  r = s 2 xyz(target_quat (x) conj(quat7)), s = -1 if that product's w < 0, else +1
+ *          (the pose error of control_ik and of torque_control.pose_error)
+ *     stop, converged, if |e_pos| <= pos_tol and |r| <= rot_tol (a tolerance of 0 is never met, not even by an error of 0)
+ *     J  = [6, 7], column j = [a_{j+1} x (p7 - p_{j+1}) ; a_{j+1}]: the terms of SDX_T_JAC_EEF
+ *     dq = J^T (J J^T + damping_arm^2 I)^-1 e   (Cholesky);   dq <- dq / max(1, max_j |dq_j| / max_step)
+ *     q[0:7] <- clamp(q[0:7] + dq, lower, upper)
+ *   stage 2 (bits 1..4), for each selected finger f on its DOFs 7 + 4 f .. 10 + 4 f (links 8 + 4 f .. 11 + 4 f), with the arm at the result
+ *   of stage 1 (at q0 when bit 0 is clear): the same loop with the point c = p_tip + R_tip tip_offset[f] of link fingertip_body[f],
+ *     e = target - c,  J = [3, 4], column i = a_i x (c - p_i),  a 3 x 3 system with damping_finger,  stop when |e| <= pos_tol.
+ * The iteration count of a task is the number of steps it took.  DOFs of tasks that are not selected leave as the bits of q0; a task that
+ * meets its tolerance at q0 takes 0 iterations and leaves its DOFs bit-equal.  For finite targets and q0 inside the limits every output is
+ * finite and inside the limits.  There is no null-space posture term, no collision check, and arm and fingers are not solved together.
+ * SDX_ERR_INVALID with a message: attr or q_out_dev NULL; a NULL target that a selected task needs; task_mask 0 or with a bit above 4;
+ * max_iters outside 1..256; a number of attr that is not finite or is negative; max_step <= 0; a scene whose robot is not a 7-link arm
+ * chain carrying four 4-link finger chains that end in fingertip_body. */
+typedef struct {
+  uint32_t task_mask;        /* bit 0: hand-base pose (solves DOFs 0..6); bits 1..4: fingertip ff, mf, rf, th (solves that finger's 4 DOFs) */
+  int32_t  max_iters;        /* 1..256 */
+  float    damping_arm;      /* DLS term of the 6x6 arm system   (control_ik uses 0.05) */
+  float    damping_finger;   /* DLS term of the 3x3 finger systems (lever arms are centimetres: 0.01) */
+  float    max_step;         /* rad: a step is scaled down so that its largest |dq_j| is at most this; > 0 */
+  float    pos_tol, rot_tol; /* m, and the length of the rotation part of the pose error; 0 = never stop early */
+  float    tip_offset[4][3]; /* the controlled point of each fingertip, in the frame of sdx_scene_desc.fingertip_body[f] */
+} sdx_ik_attr;
+int sdx_solve_ik(sdx_handle h, const sdx_ik_attr* attr, const float* q0_dev,
+                 const float* base_pos_dev, const float* base_quat_dev, const float* tip_pos_dev,
+                 float* q_out_dev, float* err_out_dev, int32_t* info_out_dev, void* stream);
+
 /* Random pushes on the target brick (the reference's forceScale / forceProbRange / forceDecay / forceDecayInterval, morb.py:1495-1516;
  * DESIGN.md section 21).  rb_forces_dev f32 [N, SDX_BODIES, 3] and prob_dev f32 [N] are CALLER-OWNED device buffers (the task's rb_forces
  * and random_force_prob): they are read and written by the launches of the calls that follow, must stay alive while the sampler is on,

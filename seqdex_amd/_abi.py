@@ -102,6 +102,12 @@ class OscAttr(C.Structure):
                 ("compensate_bias", i32)]
 
 
+class IkAttr(C.Structure):
+    """sdx_ik_attr"""
+    _fields_ = [("task_mask", C.c_uint32), ("max_iters", i32), ("damping_arm", f32), ("damping_finger", f32), ("max_step", f32),
+                ("pos_tol", f32), ("rot_tol", f32), ("tip_offset", (f32 * 3) * 4)]
+
+
 MAX_CONTACTS = 1536                   # SDX_MAX_CONTACTS
 
 
@@ -138,7 +144,7 @@ SDX_EXPORTS = ["sdx_create", "sdx_destroy", "sdx_tensor", "sdx_load_initial_stat
                "sdx_step", "sdx_pre_physics", "sdx_simulate", "sdx_post_physics", "sdx_compute_observations",
                "sdx_reset_idx", "sdx_set_indexed", "sdx_refresh_kinematics", "sdx_render_segmentation", "sdx_num_envs", "sdx_last_error",
                "sdx_set_randomization", "sdx_set_noise", "sdx_render_view", "sdx_apply_rigid_body_forces", "sdx_set_force_perturbation",
-               "sdx_apply_dof_forces", "sdx_dof_dynamics", "sdx_osc_torques", "sdx_set_contact_report", "sdx_contact_wrenches",
+               "sdx_apply_dof_forces", "sdx_dof_dynamics", "sdx_osc_torques", "sdx_solve_ik", "sdx_set_contact_report", "sdx_contact_wrenches",
                "sdx_state_create", "sdx_state_destroy", "sdx_state_save", "sdx_state_restore", "sdx_state_save_all", "sdx_state_restore_all",
                "sdx_state_clone", "sdx_state_stats",
                "sdxp_create", "sdxp_destroy", "sdxp_tensor", "sdxp_param_count", "sdxp_act", "sdxp_store_rewards",
@@ -180,6 +186,7 @@ def load_library():
     lib.sdx_apply_dof_forces.argtypes = [vp, vp, C.c_uint32, vp]
     lib.sdx_dof_dynamics.argtypes = [vp, vp, vp, vp, vp]
     lib.sdx_osc_torques.argtypes = [vp, C.POINTER(OscAttr), vp, vp, vp, vp]
+    lib.sdx_solve_ik.argtypes = [vp, C.POINTER(IkAttr), vp, vp, vp, vp, vp, vp, vp, vp]
     lib.sdx_set_contact_report.argtypes = [vp, C.POINTER(ContactReportStruct), vp]
     lib.sdx_contact_wrenches.argtypes = [vp, C.POINTER(ContactReportStruct), vp, C.POINTER(ContactPairs), vp, vp]
     lib.sdx_state_create.argtypes = [vp, i32, C.POINTER(vp)]

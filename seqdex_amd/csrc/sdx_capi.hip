@@ -607,6 +607,39 @@ extern "C" int sdx_osc_torques(sdx_handle h, const sdx_osc_attr* attr, const flo
   sdxk_osc_torques(h->d_const, &h->buf, attr, dpose_dev, torques_dev, wrench_dev, (hipStream_t)stream);
   return check_launch(h, "sdx_osc_torques");
 }
+extern "C" int sdx_solve_ik(sdx_handle h, const sdx_ik_attr* attr, const float* q0_dev, const float* base_pos_dev, const float* base_quat_dev,
+                            const float* tip_pos_dev, float* q_out_dev, float* err_out_dev, int32_t* info_out_dev, void* stream) {
+  if (!h) return SDX_ERR_INVALID;
+  const char* why = nullptr;
+  if (!attr) why = "sdx_solve_ik: attr is NULL";
+  else if (!q_out_dev) why = "sdx_solve_ik: q_out_dev is NULL";
+  else if (attr->task_mask == 0u || (attr->task_mask >> 5)) why = "sdx_solve_ik: task_mask must select at least one of the tasks 0..4 and nothing above them";
+  else if ((attr->task_mask & 1u) && (!base_pos_dev || !base_quat_dev)) why = "sdx_solve_ik: task_mask selects the hand base, base_pos_dev or base_quat_dev is NULL";
+  else if ((attr->task_mask & 0x1eu) && !tip_pos_dev) why = "sdx_solve_ik: task_mask selects a fingertip, tip_pos_dev is NULL";
+  else if (attr->max_iters < 1 || attr->max_iters > 256) why = "sdx_solve_ik: max_iters must lie in 1..256";
+  else {
+    const auto ok = [](float v) { return std::isfinite(v) && v >= 0.0f; };
+    bool all = ok(attr->damping_arm) && ok(attr->damping_finger) && ok(attr->max_step) && ok(attr->pos_tol) && ok(attr->rot_tol), offsets = true;
+    for (int f = 0; f < 4; ++f)
+      for (int c = 0; c < 3; ++c) offsets = offsets && std::isfinite(attr->tip_offset[f][c]);
+    if (!all) why = "sdx_solve_ik: damping_arm, damping_finger, max_step, pos_tol and rot_tol must be finite and not negative";
+    else if (!offsets) why = "sdx_solve_ik: tip_offset must be finite";
+    else if (!(attr->max_step > 0.0f)) why = "sdx_solve_ik: max_step must be > 0";
+    else {   // the shape of the robot that k_solve_ik walks with static indices
+      const sdx_scene_desc& sc = h->h_const.sc;
+      bool shape = sc.hand_base_body == 7;
+      for (int k = 1; k <= 7; ++k) shape = shape && sc.parent[k] == k - 1;
+      for (int f = 0; f < 4; ++f) {
+        shape = shape && sc.parent[8 + 4 * f] == 7 && sc.fingertip_body[f] == 11 + 4 * f;
+        for (int i = 1; i < 4; ++i) shape = shape && sc.parent[8 + 4 * f + i] == 7 + 4 * f + i;
+      }
+      if (!shape) why = "sdx_solve_ik: the scene's robot is not a 7-link arm chain carrying four 4-link finger chains that end in fingertip_body";
+    }
+  }
+  if (why) { h->err = why; return SDX_ERR_INVALID; }
+  sdxk_solve_ik(h->d_const, &h->buf, attr, q0_dev, base_pos_dev, base_quat_dev, tip_pos_dev, q_out_dev, err_out_dev, info_out_dev, (hipStream_t)stream);
+  return check_launch(h, "sdx_solve_ik");
+}
 extern "C" int sdx_set_contact_report(sdx_handle h, const sdx_contact_report* report, void* stream) {
   if (!h) return SDX_ERR_INVALID;
   (void)stream;

@@ -29,6 +29,10 @@ void sdxk_noise(const SdxConst* C, const SdxBuf* B, const sdx_noise_attr* attr, 
 void sdxk_dof_dynamics(const SdxConst* C, const SdxBuf* B, float* mass, float* bias, float* drive, hipStream_t st);
 // sdx_physics.hip k_osc_torques: torques [N,23] and wrench [N,6] (device, wrench may be nullptr) from the current dof and dpose [N,6]
 void sdxk_osc_torques(const SdxConst* C, const SdxBuf* B, const sdx_osc_attr* attr, const float* dpose, float* torques, float* wrench, hipStream_t st);
+// sdx_physics.hip k_solve_ik: q_out [N,23], err_out [N,6] and info_out [N,6] (device, the last two may be nullptr) from q0 [N,23] (nullptr: the
+// current dof positions) and the targets base_pos [N,3], base_quat [N,4], tip_pos [N,4,3] (nullptr where attr->task_mask does not select them)
+void sdxk_solve_ik(const SdxConst* C, const SdxBuf* B, const sdx_ik_attr* attr, const float* q0, const float* base_pos, const float* base_quat,
+                   const float* tip_pos, float* q_out, float* err_out, int32_t* info_out, hipStream_t st);
 // sdx_physics.hip k_contact_wrenches: net [N,165,6] and pair [N,n_sensor,n_filter,3] (device, either may be nullptr; pairs is read only
 // with pair) from the caller's contact report and the current body positions
 void sdxk_contact_wrenches(const SdxBuf* B, const sdx_contact_report* report, float* net, const sdx_contact_pairs* pairs, float* pair, hipStream_t st);

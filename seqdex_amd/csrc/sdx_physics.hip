@@ -23,7 +23,7 @@
 //     surviving body pairs are expanded into the box pairs of the two compounds (consecutive candidates per lane, separating-axis test);
 //     narrowphase: lane = box pair picks the samples, lane = contact computes their geometry.
 //
-// One translation unit in ten files.  The device code of the phases lives in headers that only this file includes, in this order (each
+// One translation unit in eleven files.  The device code of the phases lives in headers that only this file includes, in this order (each
 // may use what the ones before it define; none forward-declares a function of another):
 //   sdx_phys_lds.h      constants, wave hand-offs (WAVE_SYNC, WAVES_BARRIER, WAVE_SIGNAL / WAVES_WAIT), PhysLds and the table of its overlays,
 //                       Box, the clock / ablation macros
@@ -36,6 +36,7 @@
 //                       write sites report_setup, report_result
 //   sdx_phys_dynamics.h k_dof_dynamics: mass matrix, bias and drive torques outside any step (sdx_dof_dynamics)
 //   sdx_phys_osc.h      k_osc_torques: operational-space torques of the arm outside any step (sdx_osc_torques)
+//   sdx_phys_ik.h       k_solve_ik: arm and fingertip inverse kinematics outside any step (sdx_solve_ik)
 //   sdx_phys_report.h   k_contact_wrenches: per-body wrenches and sensor / filter forces from a contact report (sdx_contact_wrenches)
 //   this file           write_kinematics, load_constants, k_physics (C the drive and F the integration are in its body), k_order,
 //                       k_kinematics, the launchers
@@ -51,6 +52,7 @@
 #include "sdx_phys_solve.h"
 #include "sdx_phys_dynamics.h"
 #include "sdx_phys_osc.h"
+#include "sdx_phys_ik.h"
 #include "sdx_phys_report.h"
 
 // ---------------------------------------------------------------- outputs shared by step and refresh
@@ -554,6 +556,10 @@ extern "C" void sdxk_osc_torques(const SdxConst* C, const SdxBuf* B, const sdx_o
                                  hipStream_t st) {
   if (B->dr_on) hipLaunchKernelGGL(k_osc_torques<true>, dim3(B->N), dim3(DYN_NT), 0, st, C, *B, *attr, dpose, torques, wrench);
   else hipLaunchKernelGGL(k_osc_torques<false>, dim3(B->N), dim3(DYN_NT), 0, st, C, *B, *attr, dpose, torques, wrench);
+}
+extern "C" void sdxk_solve_ik(const SdxConst* C, const SdxBuf* B, const sdx_ik_attr* attr, const float* q0, const float* base_pos, const float* base_quat,
+                              const float* tip_pos, float* q_out, float* err_out, int32_t* info_out, hipStream_t st) {
+  hipLaunchKernelGGL(k_solve_ik, dim3(B->N), dim3(IK_NT), 0, st, C, *B, *attr, q0, base_pos, base_quat, tip_pos, q_out, err_out, info_out);
 }
 extern "C" void sdxk_contact_wrenches(const SdxBuf* B, const sdx_contact_report* report, float* net, const sdx_contact_pairs* pairs, float* pair,
                                       hipStream_t st) {

@@ -434,6 +434,41 @@ class SdxSim:
                                              C.c_void_p(w.data_ptr()) if w is not None else None, self._stream_or_none()))
         return (u, w) if wrench else u
 
+    # ------------------------------------------------------------------ pose solver (include/seqdex.h)
+    def solve_ik(self, base_pos=None, base_quat=None, tip_pos=None, params=None, q0=None, out=None):
+        """arm and fingertip inverse kinematics in one launch (include/seqdex.h sdx_solve_ik): the joint angles that
+        put the hand base at base_pos [N, 3] / base_quat [N, 4] (xyzw, as a row of RB) and the four fingertips at tip_pos [N, 4, 3], env
+        frame, float32.  params: an ik.IkParams (default: all five tasks) or a ready _abi.IkAttr; a target may be None when params does
+        not select its task.  q0 float32 [N, NDOF]: the start (None: the positions of DOF); out: float32 [N, NDOF] to write, q0 itself is
+        allowed (default: a tensor allocated once and rewritten by every call).  Returns ik.IkSolution(q, err [N, 6], converged bool
+        [N, 5], iters int32 [N, 5]); err, converged and iters are rewritten by every call.  Reads nothing but DOF (when q0 is None) and
+        the limits; writes no tensor of the simulator.  Stream-ordered."""
+        from .ik import IkParams, IkSolution
+        n, nd = self.num_envs, _abi.NDOF
+        attr = params if isinstance(params, _abi.IkAttr) else (IkParams() if params is None else params).to_attr()
+        bp = self._wrench_tensor(base_pos, "solve_ik: base_pos", (n, 3))
+        bq = self._wrench_tensor(base_quat, "solve_ik: base_quat", (n, 4))
+        tp = self._wrench_tensor(tip_pos, "solve_ik: tip_pos", (n, 4, 3))
+        if (attr.task_mask & 1) and (bp is None or bq is None):
+            raise ValueError("solve_ik: %s: the hand-base task is selected, expected a contiguous float32 tensor on %s, got None" % (
+                "base_pos" if bp is None else "base_quat", self.device))
+        if (attr.task_mask & 0x1e) and tp is None:
+            raise ValueError("solve_ik: tip_pos: a fingertip task is selected, expected a contiguous float32 tensor of shape %s on %s, got None" % (
+                (n, 4, 3), self.device))
+        start = self._wrench_tensor(q0, "solve_ik: q0", (n, nd))
+        q = self._wrench_tensor(out, "solve_ik: out", (n, nd))
+        if not hasattr(self, "_ik"):
+            self._ik = {"q": torch.empty((n, nd), dtype=torch.float32, device=self.device),
+                        "err": torch.empty((n, 6), dtype=torch.float32, device=self.device),
+                        "info": torch.empty((n, 6), dtype=torch.int32, device=self.device)}
+        if q is None:
+            q = self._ik["q"]
+        err, info = self._ik["err"], self._ik["info"]
+        P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+        self._check(self.lib.sdx_solve_ik(self.h, C.byref(attr), P(start), P(bp), P(bq), P(tp), P(q), P(err), P(info), self._stream_or_none()))
+        bits = torch.arange(5, dtype=torch.int32, device=self.device)
+        return IkSolution(q, err, ((info[:, 0:1] >> bits) & 1).bool(), info[:, 1:])
+
     # ------------------------------------------------------------------ contact report (include/seqdex.h, DESIGN.md section 24)
     def contact_report(self, enable=True):
         """gym.get_env_rigid_contacts on the device: allocates a contact_report.ContactReport (count, body, key, point, normal, force,

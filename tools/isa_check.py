@@ -7,7 +7,8 @@ usage: python tools/isa_check.py [--randomize] [--force] [--report] [extra hipcc
 --report: ... for the contact-report variant k_physics<512 | SDX_PHYS_REPORT> (516; with --randomize / --force 517 .. 519)
 --randomize: the same report for the domain-randomization variant k_physics<512 | SDX_PHYS_DR> (= k_physics<513>)
 --force: ... for the external-wrench variant k_physics<512 | SDX_PHYS_FORCE> (514; with --randomize 515)
---osc: registers, scratch and occupancy of k_osc_torques<false> and k_osc_torques<true> (sdx_phys_osc.h) instead, nothing about the loop"""
+--osc: registers, scratch and occupancy of k_osc_torques<false> and k_osc_torques<true> (sdx_phys_osc.h) instead, nothing about the loop
+--ik: the same for k_solve_ik (sdx_phys_ik.h)"""
 import os
 import re
 import subprocess
@@ -29,6 +30,9 @@ if REPORT:
 OSC = "--osc" in sys.argv
 if OSC:
     sys.argv.remove("--osc")
+IK = "--ik" in sys.argv
+if IK:
+    sys.argv.remove("--ik")
 OSC_TAGS = [("k_osc_torques<false>", "k_osc_torquesILb0E"), ("k_osc_torques<true>", "k_osc_torquesILb1E")]
 KEYS = ("VGPRs:", "AGPRs:", "ScratchSize [bytes/lane]:", "SGPRs Spill:", "VGPRs Spill:", "Occupancy [waves/SIMD]:", "LDS Size [bytes/block]:")
 TAG = "k_physicsILi%dE" % (512 + (1 if RANDOMIZE else 0) + (2 if FORCE else 0) + (4 if REPORT else 0))
@@ -50,8 +54,8 @@ with tempfile.TemporaryDirectory() as td:
            "-Rpass-analysis=kernel-resource-usage", "-save-temps=obj", "-c", SRC, "-o", os.path.join(td, "p.o")] + sys.argv[1:]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=td)
     rem = r.stderr
-    if OSC:
-        for name, tag in OSC_TAGS:
+    if OSC or IK:
+        for name, tag in (OSC_TAGS if OSC else []) + ([("k_solve_ik", "k_solve_ikPK8SdxConst")] if IK else []):
             blk = rem[rem.index(tag):]
             print(name + ":", ", ".join("%s %s" % (key, (re.search(re.escape(key) + r"\s*(\d+)", blk) or [None, "?"])[1]) for key in KEYS))
         sys.exit(0)
