@@ -23,10 +23,11 @@ _M64 = (1 << 64) - 1
 
 
 def sdx_hash(seed, a, b):
-    """the counter RNG of DESIGN.md section 6 on uint64 arrays `a` (seed, b: Python ints)"""
-    a = np.asarray(a, np.uint64)
+    """the counter RNG of DESIGN.md section 6 on uint64 arrays `a` and `b` that broadcast together (seed: a Python int; non-negative
+    Python ints serve as `a` or `b` too)"""
+    a, b = np.asarray(a, np.uint64), np.asarray(b, np.uint64)
     with np.errstate(over="ignore"):
-        z = np.uint64(seed & _M64) + np.uint64(0x9E3779B97F4A7C15) * (a + np.uint64(1)) + np.uint64((0xBF58476D1CE4E5B9 * (b + 1)) & _M64)
+        z = np.uint64(seed & _M64) + np.uint64(0x9E3779B97F4A7C15) * (a + np.uint64(1)) + np.uint64(0xBF58476D1CE4E5B9) * (b + np.uint64(1))
         z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
         z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
     return z ^ (z >> np.uint64(31))

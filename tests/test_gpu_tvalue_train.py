@@ -76,6 +76,44 @@ def test_sampler_statistics_and_oracle_agreement(golden_dir):
         tr.close()
 
 
+@pytest.mark.parametrize("batch", [1024, 6])
+def test_sampler_draws_the_restated_batch(golden_dir, batch):
+    """k_tv_sample draw by draw against tests/helpers/device_rng.py tv_batch: batch row r of draw `iter` is dataset
+    row sdx_hash(seed, iter, r) % n - the first B / 2 rows from the success set without its last 100 (held out for validation), the rest
+    from the failure set - moved by +-0.05 per component and normalised; the two draws of a fresh trainer use iter 0 and iter 1.
+    Bound 4 x 2^-23 absolute on rows of unit length: one contraction ambiguity (v_j^2 accumulated with or without a fused multiply-add),
+    four roundings in the norm, the square root and the divide."""
+    from helpers import device_rng as R
+    from seqdex_amd.tvalue_trainer import TValue_Trainer
+    g = np.load(os.path.join(golden_dir, "TV1_train.npz"))
+    seed = 9
+    tr = TValue_Trainer((g["succ"], g["fail"]), seed=seed)
+    try:
+        tr.init_TValue_function(state_dict=_sd(g, "w0_"), batch_size=batch)
+        succ, fail = np.ascontiguousarray(g["succ"][:-100], np.float32), np.ascontiguousarray(g["fail"], np.float32)
+        assert tr.num_success_data == succ.shape[0] and tr.num_failure_data == fail.shape[0]
+        assert tuple(tr.t["BATCH"].shape) == (batch, 4)
+        draws = []
+        for it in range(2):
+            tr.sample()
+            torch.cuda.synchronize()
+            x = tr.t["BATCH"].cpu().numpy().copy()
+            want = R.tv_batch(seed, it, succ, fail, batch)
+            err = np.abs(x.astype(np.float64) - want.astype(np.float64)).max()
+            print("batch %d iter %d: largest |BATCH - tv_batch| = %.3g (bound %.3g)" % (batch, it, err, 4 * 2.0 ** -23))
+            assert err <= 4 * 2.0 ** -23, (it, err)
+            idx = R.tv_rows(seed, it, succ.shape[0], fail.shape[0], batch)
+            half = batch // 2
+            # a noisy copy of its own dataset row: +-0.05 per component, renormalised by at most 1 +- 0.1
+            assert np.abs(x[:half] - succ[idx[:half]]).max() < 0.05 + 0.11 / 0.9
+            assert np.abs(x[half:] - fail[idx[half:]]).max() < 0.05 + 0.11 / 0.9
+            draws.append(x)
+        assert np.abs(draws[0] - R.tv_batch(seed, 1, succ, fail, batch)).max() > 0.01      # iter 0 is not iter 1
+        assert np.abs(draws[0] - R.tv_batch(seed, 0, g["succ"], fail, batch))[:batch // 2].max() > 0.01   # ... and the held-out rows are not drawn from
+    finally:
+        tr.close()
+
+
 def test_train_rollout_separates_the_classes(golden_dir):
     from seqdex_amd.tvalue_trainer import TValue_Trainer
     g = np.load(os.path.join(golden_dir, "TV1_train.npz"))
