@@ -53,6 +53,7 @@ int sdxpk_wave_sums_check(const float* in, float* ref, float* got, int n, hipStr
 int sdxpk_fwd2_sums_check(const float* w, const float* x, float* ref, float* got, hipStream_t st);   // test entry: fwd2_sums beside the twelve trees it replaces
 int sdxpk_input_grams_reference(const float* obs, int obs_dim, const float* cvx, int n_mb, float* out, hipStream_t st);   // test entry: the input Grams as the epoch kernel formed them in its x1 shadow
 int sdxpk_adam_ahead_check(const float* x1, const float* dy1, const float* dyr, const float* scal, int g, const float* state, float* out, hipStream_t st);   // test entry: adam_l1_ahead beside the serial loops it replaces
+int sdxpk_packed_adam_check(const float* x1, const float* dy1, const float* dyr, const float* scal, int g, const float* state, float* out, hipStream_t st);   // test entry: adam_l1_ahead (element pairs, packed f32) beside its one-element form
 // sdxp_bigmb.hip.  sdxpk_big_setup lowers the large-minibatch options of `o` to what shapes and device allow, sets the LDS attributes of
 // the kernels that stay and lays out the workspace of one minibatch of MB rows in `ws`, every buffer through `alloc`
 int sdxpk_big_setup(const SdxpDev* D, int MB, SdxpOpts* o, SdxpAllocFn alloc, void* ctx, SdxpBigWs* ws);

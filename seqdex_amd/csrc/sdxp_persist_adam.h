@@ -47,79 +47,94 @@ __device__ __forceinline__ void adam_bias(PLds& S, const StepScal& sc, int slot,
 #define SDX_PIN4X(a, b, c, d) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
 #define SDX_PIN3X(a, b, c) asm volatile("" : "+v"(a), "+v"(b), "+v"(c))
 
-// ---- Adam with the operands of the next element in flight (the x1 shadow)
+// ---- Adam with the operands of the next elements in flight (the x1 shadow), two elements at a time
 // adam1 with every rounding written out: the three products a contraction could take either way go through an opaque copy, the fmas are
 // explicit.  These are the forms hipcc gives adam1 inside the serial loops (tests/test_gpu_persist_adam_ahead.py holds the two to each other):
 //   m = fma(0.1, g, rn(0.9 m)), v = fma(g, rn(0.001 g), rn(0.999 v)), w = fma(-rn(lrb m), rcp(fma(isq, sqrt(v), 1e-8)), w)
-__device__ __forceinline__ float rounded(float x) { asm volatile("" : "+v"(x)); return x; }
-__device__ __forceinline__ void adam1x(float& w, float g, float& m, float& v, float lr_bc1, float isq_bc2) {
-  const float m9 = rounded(0.9f * m), v999 = rounded(0.999f * v), t = rounded(0.001f * g);
-  m = __builtin_fmaf(0.1f, g, m9);
-  v = __builtin_fmaf(g, t, v999);
-  const float lm = rounded(lr_bc1 * m);
-  w = __builtin_fmaf(-lm, __builtin_amdgcn_rcpf(__builtin_fmaf(isq_bc2, __builtin_amdgcn_sqrtf(v), 1e-8f)), w);
+// adam2x takes TWO elements through these forms as packed f32 (v_pk_mul_f32 / v_pk_fma_f32: two independent IEEE operations per lane and
+// instruction, each component rounded as the plain instruction rounds it, so a pair ends with the bits of its two elements run one after the
+// other; the one-element form adam1x is kept as the reference in sdxp_persist_checks.hip).  Only operations whose operands are pairs already -
+// or one splat built once for several uses - are paired: v_sqrt_f32 / v_rcp_f32 have no packed form and stay per component.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 rounded2(f32x2 x) { asm volatile("" : "+v"(x)); return x; }
+__device__ __forceinline__ f32x2 splat2(float x) { return f32x2{x, x}; }
+__device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
+__device__ __forceinline__ void adam2x(f32x2& w, f32x2 g, f32x2& m, f32x2& v, float lr_bc1, float isq_bc2) {
+  const f32x2 m9 = rounded2(splat2(0.9f) * m), v999 = rounded2(splat2(0.999f) * v), t = rounded2(splat2(0.001f) * g);
+  m = fma2(splat2(0.1f), g, m9);
+  v = fma2(g, t, v999);
+  const f32x2 lm = rounded2(splat2(lr_bc1) * m);
+  const f32x2 sq = {__builtin_amdgcn_sqrtf(v.x), __builtin_amdgcn_sqrtf(v.y)};
+  const f32x2 dn = fma2(splat2(isq_bc2), sq, splat2(1e-8f));
+  const f32x2 rc = {__builtin_amdgcn_rcpf(dn.x), __builtin_amdgcn_rcpf(dn.y)};
+  w = fma2(-lm, rc, w);
   __builtin_amdgcn_sched_barrier(0);
 }
-// the gradient element sum_s d_s x_s, from 0 in ascending order of s, one fma per sample
-__device__ __forceinline__ float grad4(const float (&d)[MB], const float (&x)[MB]) {
+// the gradient elements sum_s d_s x_s of two elements that share the factors d_s (splats), from 0 in ascending order of s, one fma per sample
+__device__ __forceinline__ f32x2 grad4x2(const f32x2 (&d)[MB], const f32x2 (&x)[MB]) {
   static_assert(MB == 4, "four samples");
-  return __builtin_fmaf(d[3], x[3], __builtin_fmaf(d[2], x[2], __builtin_fmaf(d[1], x[1], __builtin_fmaf(d[0], x[0], 0.0f))));
+  return fma2(d[3], x[3], fma2(d[2], x[2], fma2(d[1], x[1], fma2(d[0], x[0], splat2(0.0f)))));
 }
-// Adam of layer 1 as ONE loop over the lane's 24 elements: per network the row elements 0..3 (columns kr + 64 i of S.x1, factors
-// S.dyown[net][.][DY_L1 + o_row]), then the column elements 0..3 (columns kc + c, factors S.dy1[net][.][o_thr]) - the serial loops' order.
-// The four operands of element e are pinned together (one wait), then the four S.x1 operands of element e + 1 are requested - through an
-// index made opaque against the weight element e - 1 wrote, so the request can rise no further, and with a sched_barrier behind it, so it
-// cannot sink into the arithmetic of element e - and fly under that arithmetic.  The pin stands IN FRONT of the request on purpose: every wait
+// Adam of layer 1 as ONE loop over the lane's 24 elements, taken two at a time: per network the row elements (0, 1), (2, 3) (columns kr + 64 i of
+// S.x1, factors S.dyown[net][.][DY_L1 + o_row]), then the column elements (0, 1), (2, 3) (columns kc + c, factors S.dy1[net][.][o_thr]) - the
+// serial loops' order.  The two elements of a pair share their factors and their scalars; their weights, moments and S.x1 operands are pairs.
+// The eight operands of pair p are pinned together (one wait), then the eight S.x1 operands of pair p + 1 are requested - through an
+// index made opaque against the weight pair p - 1 wrote, so the request can rise no further, and with a sched_barrier behind it, so it
+// cannot sink into the arithmetic of pair p - and fly under that arithmetic.  The pin stands IN FRONT of the request on purpose: every wait
 // hipcc places in this region is lgkmcnt(0), never a partial count, so a wait behind the request would drain the reads just issued; in front of
-// it, it finds reads that were requested a whole element ago.  The factors are requested a network ahead, into the registers their
-// predecessors left: the row factors under column element 1 of the network in front, the column factors under row element 1; each is scaled
-// by the clip factor where it is first used.
-// sink(net, j, gg): the gradient element, for the test entry; the kernel passes an empty one.
+// it, it finds reads that were requested a whole pair ago.  The factors are requested a network ahead, into the registers their
+// predecessors left: the row factors under the first column pair of the network in front, the column factors under the first row pair; each is
+// scaled by the clip factor (plain products, as before) and splatted where it is first used.
+// sink(net, j, gg): the gradient element, for the test entries; the kernel passes an empty one.
 template <class Sink>
 __device__ __forceinline__ void adam_l1_ahead(const PLds& S, const StepScal& sc, int kr, int kc, int o_row, int o_thr, float (&w1)[3][4],
                                               float (&m1)[3][4], float (&v1)[3][4], float (&c1)[3][4], float (&cm1)[3][4], float (&cv1)[3][4],
                                               Sink&& sink) {
-  float dr[MB], dn[MB], x[2][MB], dep = 0.0f;   // x[e & 1]: the operands of element e
+  float dr[MB], dn[MB], dep = 0.0f;
+  f32x2 x[2][MB], d2[MB];   // x[p & 1]: the operands of pair p; d2: the factors of the pair's kind, scaled and splatted
   {
     const int o_r = opaque(o_row, dep), o_t = opaque(o_thr, dep), k = opaque(kr, dep);
 #pragma unroll
-    for (int s = 0; s < MB; ++s) { dr[s] = S.dyown[0][s][DY_L1 + o_r]; dn[s] = S.dy1[0][s][o_t]; x[0][s] = S.x1[0][s][k]; }
+    for (int s = 0; s < MB; ++s) { dr[s] = S.dyown[0][s][DY_L1 + o_r]; dn[s] = S.dy1[0][s][o_t]; x[0][s] = f32x2{S.x1[0][s][k], S.x1[0][s][k + 64]}; }
   }
 #pragma unroll
-  for (int e = 0; e < 24; ++e) {
-    const int net = e / 8, j = e % 8;
-    float (&xc)[MB] = x[e & 1], (&xn)[MB] = x[(e + 1) & 1];
+  for (int p = 0; p < 12; ++p) {
+    const int net = p / 4, jp = p % 4, j = 2 * jp;   // elements j, j + 1 of the network: j < 4 rows, else columns j - 4, j - 3
+    f32x2 (&xc)[MB] = x[p & 1], (&xn)[MB] = x[(p + 1) & 1];
     SDX_PIN4X(xc[0], xc[1], xc[2], xc[3]);
-    if (e + 1 < 24) {
-      const int n1 = (e + 1) / 8, j1 = (e + 1) % 8;
+    if (p + 1 < 12) {
+      const int n1 = (p + 1) / 4, j1 = 2 * ((p + 1) % 4);
       const int k = opaque(j1 < 4 ? kr + 64 * j1 : kc + (j1 - 4), dep);
 #pragma unroll
-      for (int s = 0; s < MB; ++s) xn[s] = S.x1[n1][s][k];
+      for (int s = 0; s < MB; ++s) xn[s] = f32x2{S.x1[n1][s][k], S.x1[n1][s][k + (j1 < 4 ? 64 : 1)]};
     }
-    if (j == 5 && net < 2) {
+    if (jp == 2 && net < 2) {
       const int o_r = opaque(o_row, dep);
 #pragma unroll
       for (int s = 0; s < MB; ++s) dr[s] = S.dyown[net + 1][s][DY_L1 + o_r];
     }
-    if (j == 1 && net > 0) {
+    if (jp == 0 && net > 0) {
       const int o_t = opaque(o_thr, dep);
 #pragma unroll
       for (int s = 0; s < MB; ++s) dn[s] = S.dy1[net][s][o_t];
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (j == 0) {
+    if (jp == 0) {
 #pragma unroll
-      for (int s = 0; s < MB; ++s) dr[s] *= sc.gs(net);
+      for (int s = 0; s < MB; ++s) d2[s] = splat2(dr[s] * sc.gs(net));
     }
-    if (j == 4) {
+    if (jp == 2) {
 #pragma unroll
-      for (int s = 0; s < MB; ++s) dn[s] *= sc.gs(net);
+      for (int s = 0; s < MB; ++s) d2[s] = splat2(dn[s] * sc.gs(net));
     }
-    const float gg = grad4(j < 4 ? dr : dn, xc);
-    sink(net, j, gg);
-    float& w = j < 4 ? w1[net][j] : c1[net][j - 4];
-    adam1x(w, gg, j < 4 ? m1[net][j] : cm1[net][j - 4], j < 4 ? v1[net][j] : cv1[net][j - 4], sc.lrb(net), sc.isq(net));
-    dep = w;
+    const f32x2 gg = grad4x2(d2, xc);
+    sink(net, j, gg.x); sink(net, j + 1, gg.y);
+    float (&wa)[4] = j < 4 ? w1[net] : c1[net], (&ma)[4] = j < 4 ? m1[net] : cm1[net], (&va)[4] = j < 4 ? v1[net] : cv1[net];
+    const int i = j & 3;
+    f32x2 w = {wa[i], wa[i + 1]}, m = {ma[i], ma[i + 1]}, v = {va[i], va[i + 1]};
+    adam2x(w, gg, m, v, sc.lrb(net), sc.isq(net));
+    wa[i] = w.x; wa[i + 1] = w.y; ma[i] = m.x; ma[i + 1] = m.y; va[i] = v.x; va[i + 1] = v.y;
+    dep = w.y;
   }
 }
 }  // namespace

@@ -173,6 +173,127 @@ extern "C" int sdxpk_adam_ahead_check(const float* x1, const float* dy1, const f
   hipLaunchKernelGGL(k_adam_ahead_check, dim3(1), dim3(NTH), sizeof(PLds), st, x1, dy1, dyr, scal, g, state, out);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+// Test entry (tests/test_gpu_persist_packed_adam.py): adam_l1_ahead takes the lane's 24 layer-1 elements two at a time as packed f32 (adam2x, grad4x2).
+// The reference is the one-element form it replaced - adam1x, grad4 and the loop over 24 elements, kept here verbatim but for the loop's name.
+// Inputs and layout as sdxpk_adam_ahead_check; out [2][4][24][NTH]: (gg, m, v, w) of [0] the one-element form, [1] adam_l1_ahead.
+namespace {
+__device__ __forceinline__ float rounded(float x) { asm volatile("" : "+v"(x)); return x; }
+__device__ __forceinline__ void adam1x(float& w, float g, float& m, float& v, float lr_bc1, float isq_bc2) {
+  const float m9 = rounded(0.9f * m), v999 = rounded(0.999f * v), t = rounded(0.001f * g);
+  m = __builtin_fmaf(0.1f, g, m9);
+  v = __builtin_fmaf(g, t, v999);
+  const float lm = rounded(lr_bc1 * m);
+  w = __builtin_fmaf(-lm, __builtin_amdgcn_rcpf(__builtin_fmaf(isq_bc2, __builtin_amdgcn_sqrtf(v), 1e-8f)), w);
+  __builtin_amdgcn_sched_barrier(0);
+}
+// the gradient element sum_s d_s x_s, from 0 in ascending order of s, one fma per sample
+__device__ __forceinline__ float grad4(const float (&d)[MB], const float (&x)[MB]) {
+  static_assert(MB == 4, "four samples");
+  return __builtin_fmaf(d[3], x[3], __builtin_fmaf(d[2], x[2], __builtin_fmaf(d[1], x[1], __builtin_fmaf(d[0], x[0], 0.0f))));
+}
+// (the parent form of adam_l1_ahead) Adam of layer 1 as ONE loop over the lane's 24 elements: per network the row elements 0..3 (columns kr + 64 i of S.x1, factors
+// S.dyown[net][.][DY_L1 + o_row]), then the column elements 0..3 (columns kc + c, factors S.dy1[net][.][o_thr]) - the serial loops' order.
+// The four operands of element e are pinned together (one wait), then the four S.x1 operands of element e + 1 are requested - through an
+// index made opaque against the weight element e - 1 wrote, so the request can rise no further, and with a sched_barrier behind it, so it
+// cannot sink into the arithmetic of element e - and fly under that arithmetic.  The pin stands IN FRONT of the request on purpose: every wait
+// hipcc places in this region is lgkmcnt(0), never a partial count, so a wait behind the request would drain the reads just issued; in front of
+// it, it finds reads that were requested a whole element ago.  The factors are requested a network ahead, into the registers their
+// predecessors left: the row factors under column element 1 of the network in front, the column factors under row element 1; each is scaled
+// by the clip factor where it is first used.
+// sink(net, j, gg): the gradient element, for the test entry; the kernel passes an empty one.
+template <class Sink>
+__device__ __forceinline__ void adam_l1_ahead_scalar(const PLds& S, const StepScal& sc, int kr, int kc, int o_row, int o_thr, float (&w1)[3][4],
+                                              float (&m1)[3][4], float (&v1)[3][4], float (&c1)[3][4], float (&cm1)[3][4], float (&cv1)[3][4],
+                                              Sink&& sink) {
+  float dr[MB], dn[MB], x[2][MB], dep = 0.0f;   // x[e & 1]: the operands of element e
+  {
+    const int o_r = opaque(o_row, dep), o_t = opaque(o_thr, dep), k = opaque(kr, dep);
+#pragma unroll
+    for (int s = 0; s < MB; ++s) { dr[s] = S.dyown[0][s][DY_L1 + o_r]; dn[s] = S.dy1[0][s][o_t]; x[0][s] = S.x1[0][s][k]; }
+  }
+#pragma unroll
+  for (int e = 0; e < 24; ++e) {
+    const int net = e / 8, j = e % 8;
+    float (&xc)[MB] = x[e & 1], (&xn)[MB] = x[(e + 1) & 1];
+    SDX_PIN4X(xc[0], xc[1], xc[2], xc[3]);
+    if (e + 1 < 24) {
+      const int n1 = (e + 1) / 8, j1 = (e + 1) % 8;
+      const int k = opaque(j1 < 4 ? kr + 64 * j1 : kc + (j1 - 4), dep);
+#pragma unroll
+      for (int s = 0; s < MB; ++s) xn[s] = S.x1[n1][s][k];
+    }
+    if (j == 5 && net < 2) {
+      const int o_r = opaque(o_row, dep);
+#pragma unroll
+      for (int s = 0; s < MB; ++s) dr[s] = S.dyown[net + 1][s][DY_L1 + o_r];
+    }
+    if (j == 1 && net > 0) {
+      const int o_t = opaque(o_thr, dep);
+#pragma unroll
+      for (int s = 0; s < MB; ++s) dn[s] = S.dy1[net][s][o_t];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (j == 0) {
+#pragma unroll
+      for (int s = 0; s < MB; ++s) dr[s] *= sc.gs(net);
+    }
+    if (j == 4) {
+#pragma unroll
+      for (int s = 0; s < MB; ++s) dn[s] *= sc.gs(net);
+    }
+    const float gg = grad4(j < 4 ? dr : dn, xc);
+    sink(net, j, gg);
+    float& w = j < 4 ? w1[net][j] : c1[net][j - 4];
+    adam1x(w, gg, j < 4 ? m1[net][j] : cm1[net][j - 4], j < 4 ? v1[net][j] : cv1[net][j - 4], sc.lrb(net), sc.isq(net));
+    dep = w;
+  }
+}
+}  // namespace
+__global__ __launch_bounds__(NTH) void k_packed_adam_check(const float* x1, const float* dy1, const float* dyr, const float* scal, int g, const float* state, float* out) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  PLds& S = *reinterpret_cast<PLds*>(smem_raw);
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r1w = wave >> 2, q1 = wave & 3;
+  for (int i = tid; i < 3 * MB * U0; i += NTH) (&S.x1[0][0][0])[i] = x1[i];
+  for (int i = tid; i < 3 * MB * U1; i += NTH) (&S.dy1[0][0][0])[i] = dy1[i];
+  if (tid < 3 * MB * 2) S.dyown[tid / (2 * MB)][(tid / 2) % MB][DY_L1 + tid % 2] = dyr[tid];
+  if (tid < 6) S.scal[tid] = scal[tid];
+  __syncthreads();
+  const StepScal sc = step_scal(S);
+  float w1[3][4], m1[3][4], v1[3][4], c1[3][4], cm1[3][4], cv1[3][4];
+  auto load = [&]() {
+#pragma unroll
+    for (int net = 0; net < 3; ++net)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int r = (net * 8 + j) * NTH + tid, c = (net * 8 + 4 + j) * NTH + tid;
+        w1[net][j] = state[r]; m1[net][j] = state[24 * NTH + r]; v1[net][j] = state[48 * NTH + r];
+        c1[net][j] = state[c]; cm1[net][j] = state[24 * NTH + c]; cv1[net][j] = state[48 * NTH + c];
+      }
+  };
+  auto store = [&](float* o) {   // o: [4][24][NTH], the gradient elements are already there
+#pragma unroll
+    for (int net = 0; net < 3; ++net)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int r = (net * 8 + j) * NTH + tid, c = (net * 8 + 4 + j) * NTH + tid;
+        o[24 * NTH + r] = m1[net][j]; o[48 * NTH + r] = v1[net][j]; o[72 * NTH + r] = w1[net][j];
+        o[24 * NTH + c] = cm1[net][j]; o[48 * NTH + c] = cv1[net][j]; o[72 * NTH + c] = c1[net][j];
+      }
+  };
+  load();
+  adam_l1_ahead_scalar(S, sc, q1 * 256 + lane, 4 * g, r1w, tid, w1, m1, v1, c1, cm1, cv1, [&](int net, int j, float gg) { out[(net * 8 + j) * NTH + tid] = gg; });
+  store(out);
+  load();
+  float* got = out + 4 * 24 * NTH;
+  adam_l1_ahead(S, sc, q1 * 256 + lane, 4 * g, r1w, tid, w1, m1, v1, c1, cm1, cv1, [&](int net, int j, float gg) { got[(net * 8 + j) * NTH + tid] = gg; });
+  store(got);
+}
+extern "C" int sdxpk_packed_adam_check(const float* x1, const float* dy1, const float* dyr, const float* scal, int g, const float* state, float* out, hipStream_t st) {
+  if (g < 0 || g >= NWG) return -1;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_packed_adam_check), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PLds)) != hipSuccess) return -1;
+  hipLaunchKernelGGL(k_packed_adam_check, dim3(1), dim3(NTH), sizeof(PLds), st, x1, dy1, dyr, scal, g, state, out);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 // Test entry (tests/test_gpu_persist_gram_x.py): the Grams of x2 and x1 as the epoch kernel forms them in the shadow of its x3 edge, one
 // workgroup of NTH threads.  x1 [3][MB][U0] and x2 [3][MB][U1] go into the S.x1 / S.x2 images; the block below is the kernel's, verbatim - two
 // butterflies, ONE reduction of 64 columns, the first column's products of x1 kept rounded by an opaque copy - but for the stores of terms.
